@@ -18,6 +18,10 @@ duration measured with HIP events on the launch stream inside the timed region) 
 statement-for-statement Python port of the reference's loops — on samples of the same batch; rank 0, N = 1).  Everything else
 (the side rows of bench_rows.py, per-rank phases, probe tables, notes) goes to the detail file, `--detail`
 (default gpurun_out/bench_detail.json), of which the compact line is an extract.
+
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) does what the headline needs and nothing else: it sets up, runs W warm-up
+steps and K timed steps, writes the outputs of the last timed step if `--dump-outputs DIR` is given, and prints the line.  The
+side rows and the live traffic measurement run, and the detail file is written, only with `--full`.
 """
 import argparse
 import json
@@ -66,7 +70,15 @@ def parse_args():
     ap.add_argument("--detail", type=str, default=os.path.join(ROOT, "gpurun_out", "bench_detail.json"),
                     help="where rank 0 writes the full result (side rows, per-rank phases, notes); '' = nowhere")
     ap.add_argument("--dump", type=str, default=None, help="write this rank's results (site union, packed matrix, distance band) to DUMP.rankN.npz")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the side rows of bench_rows.py (CPU baselines, the distance step at configs[4] shape, the rows from "
+                         "files, scan shapes, call variants, site calling), the live HBM traffic and the detail file (--detail)")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 
@@ -335,6 +347,15 @@ def timed_steps(args, r, x):
     if want_union is not None and int(u_n[0]) != want_union:
         raise SystemExit("site union has %d keys, expected %d" % (int(u_n[0]), want_union))
     t.unique_sites, t.carriers = int(u_n[0]), int(u_n[1])
+    if args.dump_outputs:
+        lo, hi = bands.band_rows(rank)
+        dump_outputs(args.dump_outputs, rank, world, [
+            ("site_union_keys", u_keys[:t.unique_sites], np.float64),
+            ("site_union_offsets", u_off[:t.unique_sites + 1], np.float64),
+            ("site_union_carriers", u_car[:t.carriers], np.float64),
+            ("consensus_bases", bases, np.float32),
+            ("consensus_filters", filt, np.float32),
+            ("distance_rows", band_holder[0][:hi - lo, :n_total], np.float64)])
     if args.dump:
         lo, hi = bands.band_rows(rank)
         np.savez(args.dump + ".rank%d.npz" % rank, union=u_keys[:t.unique_sites].cpu().numpy(), union_off=u_off[:t.unique_sites + 1].cpu().numpy(),
@@ -342,6 +363,29 @@ def timed_steps(args, r, x):
                  band=band_holder[0][:hi - lo, :n_total].cpu().numpy(), band_rows=np.array([lo, hi]), bases=bases.cpu().numpy(),
                  first_sample=np.array([x.g0, x.g1]))
     return t
+
+
+DUMP_LIMIT = 64_000_000        # bytes: all the .npy files of one --dump-outputs run together (all ranks)
+
+
+def dump_outputs(path, rank, world, arrays):
+    """--dump-outputs: what the last timed step handed back (site union with its offsets and carriers, the consensus bases and
+    filter flags of this rank's samples, the distance rows of its band) as DIR/<name>.npy, rank-suffixed when N > 1.  When they
+    would pass this rank's share of DUMP_LIMIT, each array keeps every k-th row within its part of the share, and <name>_rows.npy
+    says which."""
+    os.makedirs(path, exist_ok=True)
+    suffix = ".rank%d" % rank if world > 1 else ""
+    host = [(name, tensor.cpu().numpy().astype(dtype)) for name, tensor, dtype in arrays]
+    total = sum(a.nbytes for _, a in host)
+    limit = DUMP_LIMIT // world - 2 * 128 * len(host)           # (less the .npy headers)
+    for name, a in host:
+        if total > limit and len(a):
+            row_bytes = a.nbytes // len(a)
+            keep = max(limit * a.nbytes // total // (row_bytes + 8), 1)
+            idx = np.arange(0, len(a), -(-len(a) // keep))
+            a = a[idx]
+            np.save(os.path.join(path, name + "_rows" + suffix + ".npy"), idx.astype(np.float64))
+        np.save(os.path.join(path, name + suffix + ".npy"), np.ascontiguousarray(a))
 
 
 def headline(args, r, x, t):
@@ -442,14 +486,19 @@ def main():
     x = synthetic_inputs(args, r)
     t = timed_steps(args, r, x)
     out = headline(args, r, x, t)
-    side_rows(args, r, x, t, out)
+    if args.full:
+        side_rows(args, r, x, t, out)
     line = None
     if r.rank == 0:
         out["north_star"] = rows.north_star(out, args, r.world, x.S)
-        line = json.dumps(compact(out), separators=(",", ":"))
+        c = compact(out)
+        if args.full:
+            write_detail(args.detail, out)
+        if not (args.full and args.detail):
+            del c["detail"]                                     # no detail file in this run
+        line = json.dumps(c, separators=(",", ":"))
         if len(line) >= COMPACT_LIMIT:                          # never lose the headline to its own length again (BENCH_r05: parsed = null)
             line = json.dumps(compact(out, minimal=True), separators=(",", ":"))
-        write_detail(args.detail, out)
     if r.multi:
         r.dist.destroy_process_group()
     if r.rank == 0:

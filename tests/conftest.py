@@ -3,8 +3,11 @@ import io
 import json
 import lzma
 import os
+import shutil
+import stat
 import sys
 import tarfile
+import tempfile
 
 import pytest
 
@@ -54,6 +57,12 @@ def extract_fixture(dataset, dest):
         raw = lzma.decompress(f.read())
     with tarfile.open(fileobj=io.BytesIO(raw)) as tar:
         tar.extractall(dest)
+    # the archived files are read-only (0444) and the tests rewrite copies of them: writable by their owner, so that a user
+    # other than root can do so too
+    for dirpath, _, names in os.walk(dest):
+        for name in names:
+            path = os.path.join(dirpath, name)
+            os.chmod(path, os.stat(path).st_mode | stat.S_IWUSR)
     with open(os.path.join(d, "meta.json")) as f:
         return json.load(f)
 
@@ -66,3 +75,15 @@ def fixture_trees(tmp_path_factory):
         meta = extract_fixture(ds, str(dest))
         out[ds] = (str(dest), meta)
     return out
+
+
+@pytest.fixture
+def socket_dir():
+    """A fresh directory for the service's unix sockets.  Not under tmp_path: a socket's path may have at most 107 bytes, and
+    tmp_path under a deep temporary directory is longer than that."""
+    path = tempfile.mkdtemp(prefix="snpsvc-")
+    if len(os.path.join(path, "dev000.sock")) > 100:
+        os.rmdir(path)
+        path = tempfile.mkdtemp(prefix="snpsvc-", dir="/tmp")
+    yield path
+    shutil.rmtree(path, ignore_errors=True)

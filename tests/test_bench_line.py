@@ -83,3 +83,43 @@ assert "--no-live-traffic" in a and a[a.index("--") + 2].endswith("bench.py")
     assert "exit code 7" in bench_rows.live_traffic(args, 1e6)["error"]
     monkeypatch.setenv("FAKE_ROCPROF", "no_scan")
     assert "0 launches seen" in bench_rows.live_traffic(args, 1e6)["error"]
+
+
+def test_dump_outputs_keeps_every_row_within_the_limit_and_samples_rows_beyond_it(tmp_path):
+    """--dump-outputs without a GPU: float .npy files; at the headline's size every array whole; when the arrays would pass 64 MB
+    (here: 400 samples), every k-th row of each, the kept rows in <name>_rows.npy, and all the files together stay under the limit."""
+    import numpy as np
+    import bench
+
+    class Host(object):                                                 # what bench.py calls on a device tensor
+        def __init__(self, a):
+            self.a = a
+
+        def cpu(self):
+            return self
+
+        def numpy(self):
+            return self.a
+
+    for samples, whole in ((125, True), (400, False)):
+        sites = 49_878
+        rng = np.random.default_rng(samples)
+        bases = rng.integers(0, 256, size=(samples, sites), dtype=np.uint8)
+        arrays = [("site_union_keys", Host(np.arange(sites, dtype=np.int64) * 97), np.float64),
+                  ("site_union_offsets", Host(np.arange(sites + 1, dtype=np.int32)), np.float64),
+                  ("site_union_carriers", Host(np.arange(samples * 1500, dtype=np.int32)), np.float64),
+                  ("consensus_bases", Host(bases), np.float32),
+                  ("consensus_filters", Host(bases[::-1].copy()), np.float32),
+                  ("distance_rows", Host(np.ones((samples, samples), dtype=np.int32)), np.float64)]
+        out = tmp_path / str(samples)
+        bench.dump_outputs(str(out), 0, 1, arrays)
+        files = sorted(os.listdir(str(out)))
+        assert sum(os.path.getsize(str(out / f)) for f in files) <= bench.DUMP_LIMIT
+        got = np.load(str(out / "consensus_bases.npy"))
+        assert got.dtype == np.float32
+        if whole:
+            assert len(files) == 6 and np.array_equal(got, bases)
+        else:
+            assert len(files) == 12
+            rows = np.load(str(out / "consensus_bases_rows.npy")).astype(np.int64)
+            assert rows[0] == 0 and len(set(np.diff(rows))) == 1 and np.array_equal(got, bases[rows])

@@ -21,7 +21,7 @@ def _fasta(name, seq):
     return ">%s\n" % name + "".join(seq[i:i + 60] + "\n" for i in range(0, len(seq), 60))
 
 
-def test_call_consensus_through_the_service_equals_in_process(tmp_path):
+def test_call_consensus_through_the_service_equals_in_process(tmp_path, socket_dir):
     n = 9
     samples = []
     for k in range(n):
@@ -35,7 +35,7 @@ def test_call_consensus_through_the_service_equals_in_process(tmp_path):
     with open(snplist, "w") as f:
         for c, p in sites:
             f.write("%s\t%d\t1\ts0\n" % (c.decode(), p))
-    svc = str(tmp_path / "svc")
+    svc = socket_dir
     env0 = {k: v for k, v in os.environ.items() if not k.startswith("SNPGPU_SERVICE")}
     env1 = dict(env0, SNPGPU_SERVICE=svc, SNPGPU_SERVICE_SPAWN="1", SNPGPU_SERVICE_IDLE="120")
 

@@ -42,7 +42,7 @@ def test_bench_prints_one_compact_line_last(tmp_path):
     detail = str(tmp_path / "detail.json")
     argv = ["--steps", "2", "--warmup", "1", "--samples", "4", "--genome", "60000", "--sites", "600", "--vcf-records", "60", "--dist-samples", "300",
             "--dist-sites", "2000", "--dist-reps", "1", "--cpu-samples", "2", "--cpu-procs", "2", "--cpu-dist-samples", "20", "--site-files", "2", "--e2e-files", "2",
-            "--pipeline-files", "4", "--shape-samples", "2", "--detail", detail]
+            "--pipeline-files", "4", "--shape-samples", "2", "--detail", detail, "--full"]
     env = dict(os.environ, TMPDIR=str(tmp_path))
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + argv, cwd=ROOT, env=env, capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-2500:])
@@ -77,3 +77,34 @@ def test_bench_prints_one_compact_line_last(tmp_path):
         assert row in full and "error" not in full[row], (row, full.get(row))
     assert line["value"] == pytest.approx(full["value"], rel=1e-5) and line["k2_frac"] == pytest.approx(full["call_variants"]["strict"]["roofline"]["frac"], rel=1e-5)
     assert line["site_calling_frac"] == pytest.approx(full["site_calling"]["roofline"]["frac"], rel=1e-5)
+
+
+def test_plain_bench_run_is_the_headline_alone_and_dumps_its_outputs(tmp_path):
+    """Without --full the run is the headline and nothing else: no side row, no detail file; --steps sets the timed steps and
+    --dump-outputs writes what the last step computed.  Two runs with the same arguments dump the same arrays."""
+    import json
+    import numpy as np
+    argv = ["--steps", "3", "--warmup", "1", "--samples", "4", "--genome", "60000", "--sites", "600", "--vcf-records", "60",
+            "--detail", str(tmp_path / "detail.json")]
+    env = dict(os.environ, TMPDIR=str(tmp_path))
+    dumped = []
+    for k in range(2):
+        out = tmp_path / ("out%d" % k)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + argv + ["--dump-outputs", str(out)], cwd=ROOT, env=env,
+                           capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-2500:])
+        line = json.loads(r.stdout.splitlines()[-1])
+        assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["value"] > 0
+        assert line["roofline"]["launches"] == 3
+        for key in ("cpu_baseline", "secondary", "pipeline_from_files", "end_to_end", "scan_shapes", "detail"):
+            assert key not in line, key
+        assert not os.path.exists(str(tmp_path / "detail.json"))
+        dumped.append({f: np.load(str(out / f)) for f in sorted(os.listdir(str(out)))})
+    assert sorted(dumped[0]) == ["consensus_bases.npy", "consensus_filters.npy", "distance_rows.npy", "site_union_carriers.npy",
+                                 "site_union_keys.npy", "site_union_offsets.npy"]
+    for name, a in dumped[0].items():
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, dumped[1][name]), name
+    bases = dumped[0]["consensus_bases.npy"]
+    assert bases.shape == (4, line["config"]["snp_sites"]) and 33 <= bases.min() and bases.max() <= 126          # printable bytes: bases or '-'
+    assert dumped[0]["distance_rows.npy"].shape == (4, 4)
+    assert len(dumped[0]["site_union_offsets.npy"]) == len(dumped[0]["site_union_keys.npy"]) + 1 <= line["config"]["snp_sites"] + 1

@@ -887,7 +887,7 @@ def test_mpileup2snp_files_reports_an_unwritable_vcf_per_sample_and_never_hangs(
     assert threading.active_count() == before
 
 
-def test_service_runs_the_cli_for_thin_clients(tmp_path, fixture_trees):
+def test_service_runs_the_cli_for_thin_clients(tmp_path, fixture_trees, socket_dir):
     """SNPGPU_SERVICE: the console script hands argv / cwd / environment to the per-node server and prints / exits as the server
     says.  Host-side steps only here (no GPU): outputs, exit codes (0, 2 for argparse, 100 for a global error with its
     error-log entry written where the CLIENT's environment says) equal the in-process run; eight clients at once; a client
@@ -897,7 +897,7 @@ def test_service_runs_the_cli_for_thin_clients(tmp_path, fixture_trees):
     import time
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     exe = os.path.join(root, "bin", "cfsan_snp_pipeline")
-    sdir = str(tmp_path / "svc")
+    sdir = socket_dir
     env0 = {k: v for k, v in os.environ.items() if k != "SNPGPU_SERVICE"}
     server = subprocess.Popen([sys.executable, exe, "serve", "--socketDir", sdir, "--device", "0", "--idleTimeout", "60"], env=env0,
                               stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
