@@ -50,6 +50,13 @@
 #define SCAN_LIST_CAP 192                    // line starts held in LDS per pass (a tile with more makes extra passes)
 #define SCAN_HINT_WORDS 12                   // contig names up to 44 bytes take the fast compare
 #define SCAN_HIT_CAP 128                     // matched lines a wave collects in LDS before it publishes them (what LDS is left at sixteen waves per CU)
+#ifndef SCAN_DMA_POL
+// cache policy of the tile DMA: bits 1:0 the four body instructions, bits 3:2 the fifth (the tile's last 16 bytes + the halo, which
+// the next tile's first instruction reads again); each 0 default, 1 nt, 2 sc1, 3 sc0 sc1.  Fixed at compile time: a run-time
+// choice cost the parse its last free SGPRs (spills).  nt on the body, default on the fifth: +4 % at 30x, +5-7 % on the stream
+// alone (profiles/r7/scan_fetch.md).  Tuning builds hold the other policies (k_scan_wave_pol) for tools/scan_sweep.py (POLICY=)
+#define SCAN_DMA_POL 1
+#endif
 #ifndef SCAN_HIT_FLUSH
 #define SCAN_HIT_FLUSH 48                    // ... published at the top of the next tile once there are this many
 #endif
@@ -294,8 +301,8 @@ __device__ __forceinline__ uint32_t term_flags(uint32_t w) { return (w + 0x76767
 #define SCAN_HINT_NONE 0xFFFFFFFFu           // no usable hint
 #define SCAN_HINT_ABSENT 0xFFFFFFFEu         // the name is known NOT to be a contig of the site set
 
-template <bool kExact, int kTime>
-__global__ __launch_bounds__(1024) void k_scan_wave(ScanArgs a, SiteSetDev ss) {
+template <bool kExact, int kTime, int kPol>
+__device__ __forceinline__ void scan_wave(ScanArgs a, SiteSetDev ss) {
     extern __shared__ uint4 scan_lds[];
     ScanShared &sh = *(ScanShared *)scan_lds;
     constexpr bool kDepth = kTime == 4;                      // also add up the depth column (collect_metrics by-product)
@@ -379,8 +386,15 @@ __global__ __launch_bounds__(1024) void k_scan_wave(ScanArgs a, SiteSetDev ss) {
                 const uint64_t gr = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(ga >> 32)) << 32) |
                                     (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)ga);      // (the builtin returns int)
                 const uint32_t m0v = __builtin_amdgcn_readfirstlane(lds0 + (r >= 4 ? 4096 : 0));
-                if (r * 64 + lane < SCAN_WTILE_CHUNKS)                     // the last instruction has a partial exec mask
-                    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1 offset:%3" ::"v"(voff), "s"(gr), "s"(m0v), "n"((r & 3) * 1024) : "memory");
+                const int pol = r < 4 ? kPol & 3 : (kPol >> 2) & 3;      // (r is a constant here: the branches fold)
+#define SCAN_DMA(P) asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1 offset:%3" P ::"v"(voff), "s"(gr), "s"(m0v), "n"((r & 3) * 1024) : "memory")
+                if (r * 64 + lane < SCAN_WTILE_CHUNKS) {                   // the last instruction has a partial exec mask
+                    if (pol == 0) SCAN_DMA("");
+                    else if (pol == 1) SCAN_DMA(" nt");
+                    else if (pol == 2) SCAN_DMA(" sc1");
+                    else SCAN_DMA(" sc0 sc1");
+                }
+#undef SCAN_DMA
             }
             return SCAN_DMA_PER_TILE;
         }
@@ -972,6 +986,12 @@ __global__ __launch_bounds__(1024) void k_scan_wave(ScanArgs a, SiteSetDev ss) {
         for (int o = 32; o; o >>= 1) depth_acc += __shfl_xor(depth_acc, o);
     if (lane == 0) { a.totals[3 * gwave] = lines_seen; a.totals[3 * gwave + 1] = hits; a.totals[3 * gwave + 2] = depth_acc; }
 }
+template <bool kExact, int kTime>
+__global__ __launch_bounds__(1024) void k_scan_wave(ScanArgs a, SiteSetDev ss) { scan_wave<kExact, kTime, SCAN_DMA_POL>(a, ss); }
+#ifdef SNPGPU_TUNING
+template <int kTime, int kPol>                               // tuning: the other tile-DMA policies
+__global__ __launch_bounds__(1024) void k_scan_wave_pol(ScanArgs a, SiteSetDev ss) { scan_wave<false, kTime, kPol>(a, ss); }
+#endif
 
 // The exact parser over the queued lines (one lane per line, bytes read straight from global memory).
 __global__ __launch_bounds__(256) void k_scan_queue(ScanArgs a, SiteSetDev ss) {
@@ -1188,6 +1208,7 @@ struct ScanConfig {
     int oversub_min = 1500;                                 // (tuning) tiles per resident wave from which a forced oversub applies
     int share[4] = {329, 282, 223, 169};                    // measured: 1 / (finish time with equal shares), oldest first (30x)
     int share_dense[4] = {320, 280, 225, 175};              // ... at 8x (tools/scan_sweep.py; {290, 266, 238, 206} while the atomics of the matches still stood in the waves' way: round 5)
+    int dma_pol = SCAN_DMA_POL;                             // (tuning) the tile-DMA policy of the launch
     bool ready = false;
 };
 ScanConfig &scan_config() {
@@ -1213,11 +1234,31 @@ ScanConfig &scan_config() {
         if (const char *o = getenv("SNPGPU_SCAN_OVERSUB_MIN")) if (atoi(o) >= 0) c.oversub_min = atoi(o);
         c.mode = m ? atoi(m) : 0;
         if (w && atoi(w) >= 1 && atoi(w) <= 16) c.waves = atoi(w);
+        if (const char *p = getenv("SNPGPU_SCAN_POLICY")) {    // "body,fifth": 0 default, 1 nt, 2 sc1, 3 sc0 sc1
+            int body, fifth;
+            if (sscanf(p, "%d,%d", &body, &fifth) == 2 && body >= 0 && body <= 3 && fifth >= 0 && fifth <= 3) c.dma_pol = body | fifth << 2;
+        }
 #endif
         c.ready = true;
     }
     return c;
 }
+#ifdef SNPGPU_TUNING
+// the tile-DMA policies a tuning build can choose between in one process (SNPGPU_SCAN_POLICY); any other value runs SCAN_DMA_POL
+#define SCAN_TUNE_POLS(X) X(0) X(1) X(5) X(2) X(3)
+template <int kTime> const void *scan_wave_fn(int pol) {
+#define SCAN_POL_CASE(P) if (pol == P) return (const void *)k_scan_wave_pol<kTime, P>;
+    SCAN_TUNE_POLS(SCAN_POL_CASE)
+#undef SCAN_POL_CASE
+    return (const void *)k_scan_wave<false, kTime>;
+}
+template <int kTime> void launch_scan_wave(int pol, unsigned grid, unsigned threads, size_t lds, hipStream_t st, const ScanArgs &sa, const SiteSetDev &dev) {
+#define SCAN_POL_CASE(P) if (pol == P) { k_scan_wave_pol<kTime, P><<<grid, threads, lds, st>>>(sa, dev); return; }
+    SCAN_TUNE_POLS(SCAN_POL_CASE)
+#undef SCAN_POL_CASE
+    k_scan_wave<false, kTime><<<grid, threads, lds, st>>>(sa, dev);
+}
+#endif
 // The scan kernels ask for more than 64 KiB of dynamic LDS; the permission is a per-device function attribute, so every
 // context sets it for its own device (a process may drive several GPUs: call_consensus_batch).
 void scan_allow_lds(snpgpu_ctx *ctx) {
@@ -1225,6 +1266,9 @@ void scan_allow_lds(snpgpu_ctx *ctx) {
 #ifdef SNPGPU_TUNING
     for (auto f : {(const void *)k_scan_wave<false, 1>, (const void *)k_scan_wave<false, 2>, (const void *)k_scan_wave<false, 3>})
         (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+#define SCAN_POL_ATTR(P) for (auto f : {scan_wave_fn<0>(P), scan_wave_fn<3>(P)}) (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    SCAN_TUNE_POLS(SCAN_POL_ATTR)
+#undef SCAN_POL_ATTR
 #endif
     for (auto f : {(const void *)k_scan_wave<false, 0>, (const void *)k_scan_wave<false, 4>, (const void *)k_scan_wave<true, 0>})
         (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -1335,7 +1379,7 @@ int snpgpu_scan_range(snpgpu_ctx *ctx, const snpgpu_siteset *ss, const SampleDev
         k_scan_wave<false, 4><<<grid, threads, lds, st>>>(sa, ss->dev);  // the same parse + the 4th column
 #ifdef SNPGPU_TUNING
     } else if (c.mode == 7) {                               // tuning: LDS-DMA streaming rate without any parsing
-        k_scan_wave<false, 3><<<grid, threads, lds, st>>>(sa, ss->dev);
+        launch_scan_wave<3>(c.dma_pol, grid, threads, lds, st, sa, ss->dev);
     } else if (c.mode == 8 || c.mode == 9) {                // tuning: per-wave time stamps (9) + phase cycle counts (8)
         sa.dbg = (unsigned long long *)(ss->slow_queue + SNPGPU_SLOW_QUEUE_CAP - 65536);
         if (c.mode == 8) k_scan_wave<false, 2><<<grid, threads, lds, st>>>(sa, ss->dev);
@@ -1349,6 +1393,8 @@ int snpgpu_scan_range(snpgpu_ctx *ctx, const snpgpu_siteset *ss, const SampleDev
             free(recs);
         }
         sa.dbg = nullptr;
+    } else if (c.dma_pol != SCAN_DMA_POL) {
+        launch_scan_wave<0>(c.dma_pol, grid, threads, lds, st, sa, ss->dev);
 #endif
     } else {
         k_scan_wave<false, 0><<<grid, threads, lds, st>>>(sa, ss->dev);
