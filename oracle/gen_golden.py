@@ -529,6 +529,12 @@ def gen_steps_vectors():
         s = sorted(rng.randint(1, span) for _ in range(n))       # duplicates allowed
         m, w = rng.choice([(3, 1000), (2, 125), (1, 15), (5, 50), (1, 1)])
         dense.append({"m": m, "w": w, "snps": s, "out": [list(t) for t in fr.find_dense_regions(m, w, s)]})
+    # the ends of the rule range: no SNP allowed (every position is a window of its own once the window is >= 1), a window
+    # of 0 or 1, and more allowed SNPs than there are positions (after the random cases: their draws stay what they were)
+    some = [3, 3, 4, 10, 11, 25, 40, 40, 41, 1000, 1001, 1003]
+    for m, w in [(0, 0), (0, 1), (0, 2), (0, 15), (1, 0), (1, 1), (1, 2), (2, 1), (11, 1000), (12, 1000), (13, 1000), (12, 1 << 30)]:
+        for s in ([], [7], some):
+            dense.append({"m": m, "w": w, "snps": s, "out": [list(t) for t in fr.find_dense_regions(m, w, s)]})
     vec["find_dense_regions"] = dense
 
     merges = []

@@ -1,7 +1,8 @@
 """BASELINE.json configs[3] and configs[4] at their stated sizes on one MI355X.
 
 The oracle cannot run at these sizes, so the checks are the size-independent ones: symmetry, zero diagonal, numpy on random
-pairs and on the last (partial) tile row / column, tile split over ranks == the full run (distance); line counts = newline
+pairs and on the last (partial) tile row / column, tile split over ranks == the full run — and, for the distance, the whole
+matrix against the matrix-product statement of oracle/distance_ref.py computed on the device; line counts = newline
 counts, matched lines = sites with a line, a 300-sample batch (two scan groups: 256 + 44) == a 125-sample batch (the per-GPU
 shard of configs[3], one group) == per-sample calls, and the oracle on the very lines the device picked (consensus).
 """
@@ -64,6 +65,24 @@ def test_distance_10000_x_200000(d):
         d.distance_packed_dev(pk.data_ptr(), n, s, dm3.data_ptr(), r, 3)
     torch.cuda.synchronize()
     assert bool(torch.equal(dm3, dm))
+    # all 10^8 entries against the matrix-product statement of the distance (oracle/distance_ref.py) on the device: one-hot
+    # matrices for a chunk of sites at a time, float32 products for a block of rows at a time, sized from the free memory.
+    # First one block of 256 rows of this very input against numpy on the host: if float32 matmuls are not exact here for
+    # integer sums up to the chunk length, chunks of 2 047 sites (sums below 2^11, accumulated in int32) are used instead.
+    from oracle import distance_ref as dr
+    del dm3
+    torch.cuda.empty_cache()
+    free = torch.cuda.mem_get_info()[0]
+    k_chunk = int(max(2047, min(s, 1 << 15, free // 4 // (n * 32))))       # per (row, site): 5 float32 + byte-sized temporaries
+    row_block = int(max(128, min(n, free // 4 // (n * 16))))              # per (row, column): two float32 products + an int32
+    blk = sym[4096:4352]
+    blk_host = dr.distance_numpy(blk.cpu().numpy())
+    assert np.array_equal(blk_host, dm[4096:4352, 4096:4352].cpu().numpy())
+    if not np.array_equal(dr.distance_torch(blk, k_chunk=k_chunk).cpu().numpy(), blk_host):
+        k_chunk = 2047
+        assert np.array_equal(dr.distance_torch(blk, k_chunk=k_chunk).cpu().numpy(), blk_host)
+    ref = dr.distance_torch(sym, row_block=row_block, k_chunk=k_chunk)
+    assert bool(torch.equal(dm, ref)), "%d entries differ" % int((dm != ref).sum().item())
 
 
 def test_configs3_shard_125_and_grouped_batch_300(d):
