@@ -166,8 +166,8 @@ int  snpgpu_timer_start(snpgpu_ctx *ctx);
 int  snpgpu_timer_stop_ms(snpgpu_ctx *ctx, float *out_ms);   /* synchronises on the stop event */
 
 /* Per-kernel timing for bench.py: when enabled, HIP events are recorded on the stream around every launch of
- * the scan (0), per-site caller (1) and distance (2) kernels and around everything phase-1 site calling launches for a
- * file (3); snpgpu_ctx_kernel_time_ms synchronises, returns the
+ * the scan (0), per-site caller (1) and distance (2) kernels, around everything phase-1 site calling launches for a
+ * file (3) and around the VCF count of a piece of a file (4); snpgpu_ctx_kernel_time_ms synchronises, returns the
  * summed elapsed time and the number of launches of that kernel since the last query, and clears them. */
 int  snpgpu_ctx_kernel_timing(snpgpu_ctx *ctx, int enable);
 int  snpgpu_ctx_kernel_time_ms(snpgpu_ctx *ctx, int kernel, float *total_ms, uint32_t *launches);
@@ -384,6 +384,32 @@ int  snpgpu_varscan_dev(snpgpu_ctx *ctx, const void *d_pileup, uint64_t nbytes, 
 int  snpgpu_varscan_batch_dev(snpgpu_ctx *ctx, const void *const *d_pileups, const uint64_t *nbytes, uint32_t n_files,
                               const snpgpu_varscan_params *params, uint32_t capacity, snpgpu_varscan_site *out_sites,
                               uint32_t *out_n_sites, uint64_t *out_status, int32_t *out_rc);
+
+/* ---- the SNP count of a VCF file: what collect_metrics.py:61-106 (count_vcf_file_snps, through PyVCF) returns ------------
+ * The file is streamed through the staging chunks of the pileup streams and counted on the device by a text kernel.  Per data
+ * line (not empty, not starting with '#'; a CR in front of the terminator is not part of it):
+ *   - ten TAB-separated columns; FORMAT and the sample column split on ':' into the same number of fields, one named GT; every
+ *     allele of GT (split on '/' or '|') is '.' or a decimal index into [REF] + ALT.split(','); the line is shorter than
+ *     SNPGPU_VCF_LINE_WINDOW bytes.  A data line outside this grammar is UNUSUAL: it is counted as such and not judged;
+ *   - not a SNP when an allele is '.', when every allele is 0, when none of the named alleles is one of the single letters
+ *     A C G T N, or when there is an FT field whose value is not exactly PASS; one SNP otherwise.
+ * out_counts[3]: SNPs among the usual lines, data lines, unusual lines.  out_unusual_off[capacity]: the byte offsets of the
+ * first bytes of the unusual lines in ascending order (all of them when out_counts[2] <= capacity, else `capacity` arbitrary
+ * ones); for a line of SNPGPU_VCF_LINE_WINDOW bytes or more the offset of its TERMINATOR with bit 63 set.  Such a line is
+ * reported before its first byte is seen: a '#' line or an empty line that long is counted in out_counts[1] and [2] as well, and
+ * it is the caller who reads the line (backwards from the terminator) and finds that it counts nothing.  *out_status: the
+ * SNPGPU_VCF_* bits below.  Returns SNPGPU_E_IO when the file cannot be opened or read (an error of the input), another code
+ * for everything else.  Synchronous. */
+#define SNPGPU_VCF_LINE_WINDOW 4096
+#define SNPGPU_VCF_MORE_UNUSUAL 1u  /* more unusual lines than `capacity` */
+#define SNPGPU_VCF_LONG_LINE    2u  /* one of the reported lines is longer than the window */
+int  snpgpu_vcf_count_snps_file(snpgpu_ctx *ctx, const char *path, uint32_t capacity, uint64_t *out_counts,
+                                uint64_t *out_unusual_off, uint64_t *out_status);
+/* Many files as ONE stream (the readers run ahead across file boundaries): out_counts [n_files][3], out_unusual_off
+ * [n_files][capacity], out_status [n_files], out_rc [n_files] (SNPGPU_OK or SNPGPU_E_IO per file; the call itself fails only
+ * for argument, memory or HIP errors). */
+int  snpgpu_vcf_count_snps_files(snpgpu_ctx *ctx, const char *const *paths, uint32_t n_files, uint32_t capacity,
+                                 uint64_t *out_counts, uint64_t *out_unusual_off, uint64_t *out_status, int32_t *out_rc);
 
 /* ---- resident pileups: the input side of the one-job pipeline (`cfsan_snp_pipeline hot_path_batch`) ----------------------
  * The reference runs steps 4-11 as separate process arrays over a shared file system (run.py:662-784): call_sites

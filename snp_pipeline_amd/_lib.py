@@ -12,6 +12,7 @@ SCAN_STATUS_WORDS = 4
 F_RAWDPTH, F_VARFREQ, F_DEPTH, F_STRDPTH, F_STRBIAS, F_REGION = 1, 2, 4, 8, 16, 32
 SITE_IN_SNPLIST, SITE_EXCLUDED = 1, 2
 ST_NO_LINE, ST_OK, ST_SHORT_LINE, ST_BAD_DEPTH, ST_NO_QUALS, ST_MULTI_REF = 0, 1, 2, 3, 4, 5
+VCF_LINE_WINDOW, VCF_MORE_UNUSUAL, VCF_LONG_LINE = 4096, 1, 2
 E_HIP, E_ARG, E_NOMEM, E_PILEUP, E_UNSUPPORTED, E_IO, E_TIMEOUT = -1, -2, -3, -4, -5, -6, -7
 
 
@@ -153,6 +154,8 @@ SIGNATURES = {
     "snpgpu_varscan_file": (C.c_int, [_P, C.c_char_p, _P, C.c_uint32, _P, C.POINTER(C.c_uint32), _P]),
     "snpgpu_varscan_files": (C.c_int, [_P, C.POINTER(C.c_char_p), C.c_uint32, _P, C.c_uint32, _P, _P, _P, _P]),
     "snpgpu_varscan_format_rows": (C.c_size_t, [_P, C.c_uint32, _P, C.c_uint64, _P, _P, C.c_size_t, C.POINTER(C.c_uint32)]),
+    "snpgpu_vcf_count_snps_file": (C.c_int, [_P, C.c_char_p, C.c_uint32, _P, _P, _P]),
+    "snpgpu_vcf_count_snps_files": (C.c_int, [_P, C.POINTER(C.c_char_p), C.c_uint32, C.c_uint32, _P, _P, _P, _P]),
     "snpgpu_fasta_scan": (C.c_int, [C.c_char_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "snpgpu_fasta_load": (C.c_int, [C.c_char_p, C.c_uint64, C.c_uint64, C.c_uint8, _P, _P, _P, _P]),
     "snpgpu_vcf_sites": (C.c_int, [C.c_char_p, C.c_uint64, _P, _P, C.POINTER(C.c_uint64), _P, C.c_uint64, _P, C.c_uint32, C.POINTER(C.c_uint32)]),

@@ -14,7 +14,7 @@ import argparse
 import os
 import sys
 
-from . import call_consensus, call_sites, distance, filter_regions, hot_path, merge_sites, service, snp_matrix, snp_reference, utils
+from . import call_consensus, call_sites, collect_metrics, distance, filter_regions, hot_path, merge_sites, service, snp_matrix, snp_reference, utils
 from .utils import __version__, verbose_print
 
 NOT_PROVIDED = ("run", "data", "index_ref", "map_reads", "merge_vcfs",
@@ -171,6 +171,13 @@ def parse_argument_list(argv):
     hot_path.add_arguments(sub)
     _common(sub)
     sub.set_defaults(func=hot_path.hot_path_batch, excepthook=utils.handle_global_exception)
+
+    # Extension of this build (no reference counterpart): collect_metrics for all samples and combine_metrics in one process
+    sub = subparsers.add_parser("collect_metrics_batch", help="collect_metrics for every sample directory and the merged table, one process, all visible GPUs", formatter_class=fmt,
+                                description="Collect the quality and SNP metrics of every sample directory listed in sampleDirsFile in one process: the depth sums of the stale pileups come out of one stream through the pileup scan, the SNP counts of the stale VCF files out of one stream through the count kernel, per visible GPU.  Options as collect_metrics; file options are names inside each sample directory.")
+    collect_metrics.add_arguments(sub)
+    sub.add_argument("--version", action="version", version="%(prog)s version " + __version__)
+    sub.set_defaults(func=collect_metrics.collect_metrics_batch, excepthook=utils.handle_global_exception)
 
     # Extension of this build (no reference counterpart): the per-node service behind the per-sample CLI (SNPGPU_SERVICE)
     sub = subparsers.add_parser("serve", help="keep the GPU context for the per-sample subcommands of this node", formatter_class=fmt,

@@ -43,6 +43,7 @@ struct snpgpu_ctx {
 #define SNPGPU_K_CALL 1
 #define SNPGPU_K_DISTANCE 2
 #define SNPGPU_K_VARSCAN 3          // everything phase-1 site calling launches for one file (scan, walk, long walk)
+#define SNPGPU_K_VCF_COUNT 4        // the SNP count of a piece of a VCF file (vcf_count.hip)
 // RAII-less helpers: call begin before the launch and end right after it (no-ops unless timing is enabled)
 // Start of a public call that produces per-site records: the spill is there and empty (enqueued on the context's stream).
 int snpgpu_spill_begin(snpgpu_ctx *ctx);
@@ -147,6 +148,12 @@ int snpgpu_enqueue_varscan_batch(snpgpu_ctx *ctx, const uint8_t *const *d_bufs, 
 int snpgpu_enqueue_call_lines(snpgpu_ctx *ctx, const SampleDev *d_sample, const uint64_t *d_line_off, const uint8_t *d_flags,
                               uint32_t n_lines, const snpgpu_caller_params *prm, uint8_t *d_out_base, uint8_t *d_out_filters,
                               snpgpu_site_counts *d_out_counts, uint32_t *d_todo_n = nullptr, uint64_t *d_todo = nullptr, uint64_t *d_todo2 = nullptr);
+// vcf_count.hip: the rows of the piece d_buf[0, n) of a VCF file whose terminators lie at or behind own_from (0 for the piece at the
+// start of the file, else SNPGPU_VCF_LOOK bytes of the piece before) are counted into d_res: SNPs, data lines, unusual lines, then
+// `capacity` offsets of unusual lines.  d_buf is 16-byte aligned and readable up to the next 16-byte boundary behind n.
+#define SNPGPU_VCF_TILE 16384
+#define SNPGPU_VCF_LOOK SNPGPU_VCF_LINE_WINDOW
+int snpgpu_enqueue_vcf_count(snpgpu_ctx *ctx, const uint8_t *d_buf, uint32_t n, uint32_t own_from, uint64_t file_off, uint64_t *d_res, uint32_t capacity);
 // the call kernels over a scanned batch (consensus.hip); d_todo_n: 4 words (3 zeroed), d_todo / d_todo2: n * n_sites entries each;
 // lines_out.hip: the per-line records of --vcfAllPos packed into 24 bytes where they fit, the others gathered as they are
 size_t snpgpu_compact_lines_workspace_words(uint64_t n_lines);

@@ -1826,3 +1826,182 @@ int snpgpu_pileups_get_stats(const snpgpu_pileups *store, snpgpu_pileups_stats *
 }
 
 }  // extern "C"
+
+// ---- the SNP counts of VCF files (vcf_count.hip) ----------------------------------------------------------------------------
+// The files go through the same reader threads, staging ring and copy streams as the pileups, but nothing of a file stays on the
+// device: a staging chunk holds a piece of the file behind the SNPGPU_VCF_LOOK bytes in front of it (read again: 4 KiB per 16 MiB),
+// is copied into one of a few device buffers and counted by a launch of its own, whose counts are added to the file's result
+// words.  All results come back in one copy at the end.
+namespace {
+
+int vcf_count_stream(snpgpu_ctx *ctx, const char *const *paths, uint32_t n_files, uint32_t capacity, uint64_t *out_counts, uint64_t *out_unusual_off,
+                     uint64_t *out_status, int32_t *out_rc) {
+    constexpr uint32_t N_DEV = 3;                               // device buffers a chunk is counted in
+    HIP_TRY(ctx, snpgpu_enter(ctx));
+    const size_t chunk = (size_t)16 << 20;                      // the staging chunks of the pileup streams: the pinned ring is shared with them
+    const uint64_t step = chunk - SNPGPU_VCF_LOOK - 16;         // new bytes per piece: look-back + piece + a final newline fit into a chunk
+    std::vector<Source> src;
+    std::vector<Job> jobs;
+    std::vector<uint32_t> chunks_of;
+    try {                                                       // (no exception may leave through the C ABI: no memory is an error code)
+        src.resize(n_files);
+        chunks_of.resize(n_files);
+        for (uint32_t f = 0; f < n_files; ++f) {
+            Source &s = src[f];
+            s.path = paths[f];
+            struct stat stt;
+            if (!s.path || stat(s.path, &stt) != 0 || !S_ISREG(stt.st_mode)) { s.rc = SNPGPU_E_IO; s.size = 0; }
+            else s.size = (uint64_t)stt.st_size;
+            const uint64_t n = s.size;
+            const uint32_t nc = n ? (uint32_t)((n + step - 1) / step) : 1;      // an empty file still takes one (empty) job
+            chunks_of[f] = nc;
+            for (uint32_t c = 0; c < nc; ++c) {
+                const uint64_t lo = (uint64_t)c * step, hi = n - lo < step ? n : lo + step, look = c ? SNPGPU_VCF_LOOK : 0;
+                jobs.push_back(Job{f, lo - look, hi - lo + look, c == 0, c + 1 == nc, c});
+            }
+        }
+    } catch (const std::exception &) {
+        return snpgpu_set_error(ctx, SNPGPU_E_NOMEM, "no memory for the job list of %u files", n_files);
+    }
+    const uint64_t J = jobs.size();
+    const size_t res_words = 3 + (size_t)capacity;
+
+    // everything that has to be undone lives here, and every exit after this point goes through `done`
+    Opener opener;
+    Shared sh;
+    std::vector<std::thread> readers;
+    hipEvent_t ev_counted[N_DEV] = {nullptr, nullptr, nullptr};
+    std::vector<uint64_t> h_res;
+    snpgpu_stream_pool *p = nullptr;
+    uint8_t *d_buf[N_DEV] = {nullptr, nullptr, nullptr};
+    uint64_t *d_res = nullptr;
+    hipStream_t st = ctx->stream;
+    uint64_t R = 1;
+    int rc = SNPGPU_OK;
+    bool opened = false;
+#define VC_TRY(expr)                                                                                                \
+    do {                                                                                                            \
+        hipError_t e_ = (expr);                                                                                     \
+        if (e_ != hipSuccess) { rc = snpgpu_set_error(ctx, SNPGPU_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); goto done; } \
+    } while (0)
+
+    try { h_res.assign((size_t)n_files * res_words, 0); } catch (const std::exception &) { rc = snpgpu_set_error(ctx, SNPGPU_E_NOMEM, "no memory for the results"); goto done; }
+    try { opener.start(&src, chunks_of); } catch (const std::exception &) { rc = snpgpu_set_error(ctx, SNPGPU_E_NOMEM, "no memory for the file opener"); goto done; }
+    opened = true;
+    {
+        uint32_t n_readers = snpgpu_reader_threads();
+        if (n_readers > J) n_readers = (uint32_t)J;
+        uint32_t n_staging = n_readers + 4;
+        if (n_staging > J) n_staging = (uint32_t)J;
+        rc = pool_ensure(ctx, chunk, n_staging, 0, 0, 0, 0);
+        if (rc) goto done;
+        p = ctx->pool;
+        R = p->staging.size() < n_staging ? p->staging.size() : n_staging;
+        const size_t buf_bytes = chunk + 256, res_bytes = up(8 * res_words * n_files, 256);
+        void *ws = nullptr;
+        rc = snpgpu_scratch(ctx, N_DEV * buf_bytes + res_bytes + 256, &ws);
+        if (rc) goto done;
+        for (uint32_t i = 0; i < N_DEV; ++i) d_buf[i] = (uint8_t *)ws + i * buf_bytes;
+        d_res = (uint64_t *)((uint8_t *)ws + N_DEV * buf_bytes);
+        VC_TRY(hipStreamSynchronize(st));                       // whatever used the scratch before is done
+        for (uint32_t i = 0; i < N_DEV; ++i) VC_TRY(hipEventCreateWithFlags(&ev_counted[i], hipEventDisableTiming));
+        VC_TRY(hipMemsetAsync(d_res, 0, res_bytes, st));
+        sh.R = R;
+        sh.opener = &opener;
+        try {
+            sh.filled.assign(J, 0);
+            sh.job_err.assign(J, 0);
+            for (uint32_t i = 0; i < n_readers; ++i) readers.emplace_back(reader_main, ctx, &sh, &jobs, &src);
+        } catch (const std::exception &e) {
+            rc = snpgpu_set_error(ctx, SNPGPU_E_NOMEM, "cannot start the reader threads: %s", e.what());
+            goto done;
+        }
+    }
+    {
+        int64_t copies_done = 0;
+        for (uint64_t j = 0; j < J; ++j) {
+            const Job &jb = jobs[j];
+            Source &s = src[jb.file];
+            for (;;) {                                          // wait for the piece; meanwhile hand copied-out staging buffers back to the readers
+                bool progress = false;
+                while (copies_done < (int64_t)j && hipEventQuery(p->ev_copy[copies_done % R]) != hipErrorNotReady) { ++copies_done; progress = true; }
+                std::unique_lock<std::mutex> lk(sh.mu);
+                if (progress) { sh.freed = copies_done; lk.unlock(); sh.cv.notify_all(); lk.lock(); }
+                if (sh.filled[j]) break;
+                sh.cv.wait_for(lk, std::chrono::microseconds(copies_done < (int64_t)j ? 20 : 2000), [&] { return sh.filled[j] != 0; });
+                if (sh.filled[j]) break;
+            }
+            if (sh.job_err[j] && s.rc == SNPGPU_OK) s.rc = SNPGPU_E_IO;
+            uint8_t *h = (uint8_t *)p->staging[j % R];
+            uint32_t len = (uint32_t)jb.len;
+            if (jb.last && len && h[len - 1] != '\n') h[len++] = '\n';      // a last line without a terminator is a line
+            const uint32_t b = (uint32_t)(j % N_DEV);
+            hipStream_t cs = (j & 1) ? p->copy_stream2 : p->copy_stream;
+            if (j >= N_DEV) VC_TRY(hipStreamWaitEvent(cs, ev_counted[b], 0));      // the piece that was in this buffer has been counted
+            if (len) VC_TRY(hipMemcpyAsync(d_buf[b], h, len, hipMemcpyHostToDevice, cs));
+            VC_TRY(hipEventRecord(p->ev_copy[j % R], cs));
+            VC_TRY(hipStreamWaitEvent(st, p->ev_copy[j % R], 0));
+            if (s.rc == SNPGPU_OK && s.size) {
+                rc = snpgpu_enqueue_vcf_count(ctx, d_buf[b], len, jb.first ? 0 : SNPGPU_VCF_LOOK, jb.off, d_res + (size_t)jb.file * res_words, capacity);
+                if (rc) goto done;
+            }
+            VC_TRY(hipEventRecord(ev_counted[b], st));
+        }
+        VC_TRY(hipMemcpyAsync(h_res.data(), d_res, 8 * res_words * n_files, hipMemcpyDeviceToHost, st));
+        VC_TRY(hipStreamSynchronize(st));
+    }
+done:
+#undef VC_TRY
+    if (opened) {
+        if (rc) opener.cancel();
+        {
+            std::lock_guard<std::mutex> lk(sh.mu);
+            if (rc) { sh.abort = true; sh.next.store(J); }
+        }
+        sh.cv.notify_all();
+        for (auto &t : readers) t.join();
+        if (rc && p) { (void)hipStreamSynchronize(p->copy_stream); (void)hipStreamSynchronize(p->copy_stream2); (void)hipStreamSynchronize(st); }
+        opener.finish();
+        for (auto &s2 : src) if (s2.fd >= 0) { close(s2.fd); s2.fd = -1; }
+    }
+    for (hipEvent_t e : ev_counted) if (e) (void)hipEventDestroy(e);
+    if (rc) return rc;
+    for (uint32_t f = 0; f < n_files; ++f) {
+        const uint64_t *r = h_res.data() + (size_t)f * res_words;
+        uint64_t *cnt = out_counts + 3 * (size_t)f;
+        cnt[0] = r[0]; cnt[1] = r[1]; cnt[2] = r[2];
+        uint64_t status = r[2] > capacity ? SNPGPU_VCF_MORE_UNUSUAL : 0;
+        const uint64_t n_off = r[2] < capacity ? r[2] : capacity;
+        for (uint64_t k = 0; k < n_off; ++k) {
+            out_unusual_off[(size_t)f * capacity + k] = r[3 + k];
+            if (r[3 + k] >> 63) status |= SNPGPU_VCF_LONG_LINE;
+        }
+        std::sort(out_unusual_off + (size_t)f * capacity, out_unusual_off + (size_t)f * capacity + n_off);
+        out_status[f] = status;
+        out_rc[f] = src[f].rc;                                  // SNPGPU_E_IO: the file could not be opened or read (its counts are void)
+    }
+    return SNPGPU_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int snpgpu_vcf_count_snps_files(snpgpu_ctx *ctx, const char *const *paths, uint32_t n_files, uint32_t capacity, uint64_t *out_counts,
+                                uint64_t *out_unusual_off, uint64_t *out_status, int32_t *out_rc) {
+    if (!ctx || !out_counts || !out_status || !out_rc || (n_files && !paths) || (capacity && !out_unusual_off))
+        return snpgpu_set_error(ctx, SNPGPU_E_ARG, "null argument");
+    if (capacity > (1u << 20)) return snpgpu_set_error(ctx, SNPGPU_E_ARG, "the capacity for unusual lines is at most 2^20");
+    if (!n_files) return SNPGPU_OK;
+    return vcf_count_stream(ctx, paths, n_files, capacity, out_counts, out_unusual_off, out_status, out_rc);
+}
+
+int snpgpu_vcf_count_snps_file(snpgpu_ctx *ctx, const char *path, uint32_t capacity, uint64_t *out_counts, uint64_t *out_unusual_off, uint64_t *out_status) {
+    if (!path) return snpgpu_set_error(ctx, SNPGPU_E_ARG, "null argument");
+    int32_t file_rc = SNPGPU_OK;
+    const int rc = snpgpu_vcf_count_snps_files(ctx, &path, 1, capacity, out_counts, out_unusual_off, out_status, &file_rc);
+    if (rc) return rc;
+    return file_rc ? snpgpu_set_error(ctx, file_rc, "cannot open or read the VCF file %s", path) : SNPGPU_OK;
+}
+
+}  // extern "C"

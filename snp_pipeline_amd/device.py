@@ -636,6 +636,37 @@ class Device(object):
                 out.append((sites[i, :counts[i]].copy(), int(status[i, 1])))
         return out
 
+    def vcf_count_snps_file(self, path, capacity=64):
+        """The SNP count of one VCF file: see vcf_count_snps_files."""
+        res = self.vcf_count_snps_files([path], capacity)[0]
+        if isinstance(res, Exception):
+            raise res
+        return res
+
+    def vcf_count_snps_files(self, paths, capacity=64):
+        """What the count kernel finds in VCF files, all of them in one stream: per file (snps, data_lines, unusual, offsets,
+        status) — SNPs among the lines inside the kernel's grammar, data lines, lines outside it, the byte offsets of those
+        (at most `capacity`; bit 63: the offset is the terminator of a line longer than the window), the SNPGPU_VCF_* bits —
+        or an IOError object for a file that cannot be opened or read.  collect_metrics.count_snps_files makes counts of it."""
+        n = len(paths)
+        if n == 0:
+            return []
+        cap = int(capacity)
+        arr = (C.c_char_p * n)(*[os.fsencode(p) for p in paths])
+        counts = np.zeros((n, 3), dtype=np.uint64)
+        offsets = np.zeros((n, max(cap, 1)), dtype=np.uint64)
+        status = np.zeros(n, dtype=np.uint64)
+        rcs = np.zeros(n, dtype=np.int32)
+        self._check(self.lib.snpgpu_vcf_count_snps_files(self.ctx, arr, n, cap, _ptr(counts), _ptr(offsets), _ptr(status), _ptr(rcs)))
+        out = []
+        for i, path in enumerate(paths):
+            if rcs[i] != 0:
+                out.append(IOError("cannot open or read the VCF file %s" % path))
+            else:
+                k = min(int(counts[i, 2]), cap)
+                out.append((int(counts[i, 0]), int(counts[i, 1]), int(counts[i, 2]), [int(x) for x in offsets[i, :k]], int(status[i])))
+        return out
+
     def raise_file_status(self, path, rc, res, check=True, wanted=None):
         """Raise for one file of call_consensus_files the way call_consensus does for its single pileup (wanted: see site_error)."""
         if rc == L.E_IO:

@@ -173,6 +173,10 @@ class _Job(object):
         self.vs_opts = varscan.Options(env("VarscanMpileup2snp_ExtraParams", args.varscanExtraParams))
         self.site_calling = cs.site_calling_mode(getattr(args, "siteCalling", None))
         self.want_vcf = not args.noConsensusVcf
+        # --collectMetrics: the metrics files (and the table) at the end of the job, from what the job holds (stage_collect_metrics)
+        self.collect_metrics = bool(getattr(args, "collectMetrics", False))
+        self.cm_extra = env("CollectMetrics_ExtraParams", getattr(args, "collectMetricsExtraParams", None))
+        self.metrics_known = {}                        # sample dir -> {"depth_sum", "missingPos", "missingPosPreserved"}
         # --vcfAllPos (a row for every line of the pileup, call_consensus.py:148-151) is the per-sample command's all-lines pass: the
         # job writes the FASTA files and everything downstream, and lets that command write every sample's two VCF files at the end
         self.vcf_all_pos = bool(self.cc_args.vcfAllPos and self.want_vcf)
@@ -658,6 +662,7 @@ def _prepare_flows(job):
     # column is summed by the same scan, the gaps are counted in the rows that are written anyway
     fl.metrics_ref = getattr(cc_args, "amdMetricsRefFasta", None)
     fl.metrics_ref_len = sum(utils.read_fasta_lengths(fl.metrics_ref).values()) if fl.metrics_ref else 0
+    fl.want_depth = bool(fl.metrics_ref) or job.collect_metrics     # the depth column is summed by the scan for either of them
     fl.filters_desc = vcf_writer.filter_descriptions(cc_args.minConsFreq, cc_args.minConsDpth, cc_args.minConsStrdDpth, cc_args.minConsStrdBias)
     fl.filter_names = [n for n, _ in fl.filters_desc]
     fl.d_cols1, fl.d_cols2 = torch.from_numpy(cols1.astype(np.int32)).cuda(), torch.from_numpy(cols2.astype(np.int32)).cuda()
@@ -737,6 +742,13 @@ def _write_group(job, fl, part, hs, vcf_later, spill=None):
             owners.append(s)
     res = devmod.write_consensus_files(jobs, fl.ss, fl.filter_names, cc_args.vcfPreserveRefCase, cc_args.vcfFailedSnpGt, n_threads=job.args.writerThreads,
                                        spill=spill)
+    if job.collect_metrics:                                  # kept for stage_collect_metrics: no pileup and no FASTA is read again
+        st_h = hs["status"].numpy()
+        for k, s in enumerate(part):
+            if s.ok:
+                job.metrics_known[s.dir] = {"depth_sum": int(st_h[k, 3]) & 0xFFFFFFFFFFFFFFFF,
+                                            "missingPos": int(np.count_nonzero(hs["base1"].numpy()[k, :S1] == 0x2D)),
+                                            "missingPosPreserved": int(np.count_nonzero(hs["base2"].numpy()[k, :S2] == 0x2D))}
     if fl.metrics_ref:                                       # as call_consensus._record_metrics does for the two flows, in their order
         st_h = hs["status"].numpy()
         for k, s in enumerate(part):
@@ -812,10 +824,10 @@ def _consensus_group(job, fl, g0, part, hs, vcf_again, vcf_later):
         if len(res_idx) == g:
             dev.call_consensus_many_dev(ss, ptrs, sizes, prm, d_base.data_ptr(), d_filt.data_ptr(), d_status.data_ptr(),
                                         d_counts=d_counts.data_ptr() if want_vcf else 0, d_line_off=d_line.data_ptr(),
-                                        want_depth_sum=bool(fl.metrics_ref))
+                                        want_depth_sum=fl.want_depth)
         else:
             _call_scattered(dev, ss, prm, res_idx, ptrs, sizes, d_base, d_filt, d_status, d_counts, d_line, S, want_vcf, torch,
-                            want_depth_sum=bool(fl.metrics_ref))
+                            want_depth_sum=fl.want_depth)
     elif res_idx:
         d_status[:g] = torch.tensor([-1, 0, 0, 0], dtype=torch.int64, device="cuda")
     rest = [(k, s) for k, s, ptr, _ in resident if not ptr]
@@ -831,7 +843,7 @@ def _consensus_group(job, fl, g0, part, hs, vcf_again, vcf_later):
     if rest:
         # files that did not fit the memory budget: streamed again (the only pileups that cross the link twice)
         results, rcs, st = dev.call_consensus_files(ss, [s.pileup for _, s in rest], prm, want_counts=want_vcf, want_line_offsets=True,
-                                                    want_depth_sum=bool(fl.metrics_ref))
+                                                    want_depth_sum=fl.want_depth)
         job.h2d_extra += int(st.bytes)
         for (k, s), rc, r in zip(rest, rcs, results):
             if int(rc) == L.E_IO:
@@ -854,7 +866,7 @@ def _consensus_group(job, fl, g0, part, hs, vcf_again, vcf_later):
                     pass                                      # (its scan error stands)
             if copies:
                 results, rcs, st = dev.call_consensus_files(ss, [c for _, _, c in copies], prm, want_counts=want_vcf, want_line_offsets=True,
-                                                            want_depth_sum=bool(fl.metrics_ref))
+                                                            want_depth_sum=fl.want_depth)
                 job.h2d_extra += int(st.bytes)
                 for (k, s, _), rc, r in zip(copies, rcs, results):
                     if int(rc) == L.E_IO:
@@ -1124,13 +1136,35 @@ def stage_leftover_vcfs(job):
         utils.set_logging_verbosity(job.args)
 
 
-STAGES = (stage_ingest_and_sites, stage_site_union_and_regions, stage_consensus, stage_matrices_and_distances, stage_leftover_vcfs)
+def stage_collect_metrics(job):
+    """--collectMetrics: the metrics file of every sample of this rank (collect_metrics.run_batch), with the depth sums and gap
+    counts the job holds as `known` and the VCF files it has just written counted in one stream on the job's device.  The table
+    is written by rank 0 when every rank has got here (hot_path_batch)."""
+    if not job.collect_metrics:
+        return
+    from . import collect_metrics as cm
+    t0 = time.perf_counter()
+    options = cm.Options.from_args(_step_args("collect_metrics_batch", [job.dirs_file, job.ref_path], job.cm_extra))
+    job.metrics_options = options
+    job.dev.sync()
+    job.metrics_done = cm.run_batch([s.dir for s in job.mine], job.ref_path, options, devices=[job.dev], known=job.metrics_known,
+                                    report_errors=False)
+    for s, message in ((s, job.metrics_done["errors"].get(s.dir)) for s in job.mine):
+        if message and s.ok:
+            s.fail(message)
+    job.lap("collect_metrics", t0)
+
+
+STAGES = (stage_ingest_and_sites, stage_site_union_and_regions, stage_consensus, stage_matrices_and_distances, stage_leftover_vcfs,
+          stage_collect_metrics)
 
 
 def _job_stats(job):
     st = job.store.stats()
     fl = job.flows
-    return {"h2d_bytes": int(st.h2d_bytes) + job.h2d_extra, "file_bytes": int(st.file_bytes), "resident_files": int(st.n_resident),
+    done = getattr(job, "metrics_done", None)
+    return {"collect_metrics": {k: v for k, v in done.items() if k != "errors"} if done else None,
+            "h2d_bytes": int(st.h2d_bytes) + job.h2d_extra, "file_bytes": int(st.file_bytes), "resident_files": int(st.n_resident),
             "files": int(st.n_files), "seconds": time.perf_counter() - job.t_start, "site_calling": job.site_calling,
             "ingest": {"seconds": st.seconds, "allocating": st.seconds_allocating, "waiting_for_readers": st.seconds_waiting_for_readers,
                        "waiting_for_device": st.seconds_waiting_for_device, "reader_seconds_reading": st.reader_seconds_reading,
@@ -1169,6 +1203,10 @@ def hot_path_batch(args):
     errs = [s.error for s in job.mine if not s.ok]
     all_errs = comm.gather_objects(errs)
     failed = sum(len(e) for e in all_errs)
+    if job.collect_metrics and job.rank == 0 and getattr(job, "metrics_options", None) is not None:    # (every rank's metrics files are written: the gather above)
+        from . import collect_metrics as cm
+        merged = args.mergedMetricsFile or os.path.join(job.work_dir, "metrics.tsv")
+        cm.combine(job.unsorted_dirs, job.metrics_options.metricsFile, merged, bool(getattr(args, "spaceHeadings", False)))
     comm.close()                                             # (before anything that may end the process: sample_error exits when StopOnSampleError says so)
     for msg in errs:
         utils.sample_error(msg, continue_possible=True)
@@ -1228,6 +1266,9 @@ def add_arguments(sub):
                       ("callConsensusExtraParams", "CallConsensus_ExtraParams"), ("varscanExtraParams", "VarscanMpileup2snp_ExtraParams")):
         sub.add_argument("--" + name, dest=name, type=str, default=None, metavar="STRING",
                          help="Options of that step, as the configuration file gives them (default: the environment variable %s)" % env)
+    sub.add_argument("--collectMetrics", dest="collectMetrics", action="store_true", help="At the end of the job write every sample's metrics file and the merged table (collect_metrics_batch), from the depth sums and gap counts the job holds: no pileup is read a second time")
+    sub.add_argument("--collectMetricsExtraParams", dest="collectMetricsExtraParams", type=str, default=None, metavar="STRING", help="Options of collect_metrics, as the configuration file gives them (default: the environment variable CollectMetrics_ExtraParams)")
+    sub.add_argument("--mergedMetricsFile", dest="mergedMetricsFile", type=str, default=None, metavar="PATH", help="With --collectMetrics: the merged metrics table (default: metrics.tsv in the work directory)")
     sub.add_argument("--noConsensusVcf", dest="noConsensusVcf", action="store_true", help="Do not write consensus.vcf / consensus_preserved.vcf")
     sub.add_argument("--residentBytes", dest="residentBytes", type=int, default=0, metavar="INT", help="Device memory for resident pileups (0 = what is free, less 24 GiB); files past it are streamed twice")
     sub.add_argument("--groupBytes", dest="groupBytes", type=int, default=0, metavar="INT", help="Host bytes of per-site results per group of samples (default 1 GiB)")

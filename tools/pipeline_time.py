@@ -37,6 +37,9 @@ def main():
     ap.add_argument("--resident-frac", type=float, default=0.0,
                     help="after the timed runs: one more run with --residentBytes = this fraction of the pileup bytes (the rest is streamed twice); "
                          "its time and whether every output file equals the fully resident run's")
+    ap.add_argument("--collect-metrics", type=int, default=0, metavar="RUNS",
+                    help="after the timed runs: RUNS runs each of the job alone, of collect_metrics_batch -f after it (every pileup read again "
+                         "for its depth sum) and of the job with --collectMetrics; medians, and whether both routes write the same metrics files")
     ap.add_argument("--probe-open", choices=("none", "stat", "serial", "parallel"), default="none",
                     help="before the first run: time stat / open of every pileup (what does the first open after the write cost?)")
     a = ap.parse_args()
@@ -147,6 +150,31 @@ def main():
                                       "h2d_bytes": st["h2d_bytes"], "h2d_over_file_bytes": st["h2d_bytes"] / total,
                                       "over_fully_resident": st["seconds"] / best["seconds"], "outputs_identical_to_fully_resident": part == full,
                                       "phases": st["phases"]}
+        if a.collect_metrics > 0:
+            import statistics
+            extra = (" --noConsensusVcf" if a.no_vcf else "") + (" " + a.extra if a.extra else "")
+            merged = os.path.join(tmpdir, "metrics.tsv")
+
+            def metrics_text():
+                return [open(os.path.join(sd, "metrics")).read() for sd in dirs] + [open(merged).read()]
+            alone, after, inside, phase, counted = [], [], [], [], None
+            for _ in range(a.collect_metrics):
+                alone.append(bench.run_cli(bench.hot_path_line(dirs_file, ref_path, extra), verbose=a.verbose))
+                after.append(bench.run_cli("collect_metrics_batch -f --mergedMetricsFile %s --verbose 0 %s %s" % (merged, dirs_file, ref_path), verbose=a.verbose))
+            separate_route = metrics_text()
+            for _ in range(a.collect_metrics):
+                inside.append(bench.run_cli(bench.hot_path_line(dirs_file, ref_path, extra + " --collectMetrics --mergedMetricsFile " + merged), verbose=a.verbose))
+                st = hot_path.hot_path_batch.last_stats
+                phase.append(st["phases"].get("collect_metrics", 0.0))
+                counted = st["collect_metrics"]
+            vcf_bytes = sum(os.path.getsize(os.path.join(sd, n)) for sd in dirs for n in ("var.flt.vcf", "var.flt_preserved.vcf", "consensus.vcf", "consensus_preserved.vcf")
+                            if os.path.exists(os.path.join(sd, n)))
+            out["collect_metrics"] = {"runs": a.collect_metrics, "job_alone_seconds": alone, "collect_metrics_batch_after_seconds": after,
+                                      "job_with_collectMetrics_seconds": inside, "collect_metrics_phase_seconds": phase,
+                                      "median_job_alone": statistics.median(alone), "median_after": statistics.median(after),
+                                      "median_job_with_option": statistics.median(inside), "median_phase": statistics.median(phase),
+                                      "option_cost_over_job": statistics.median(inside) / statistics.median(alone) - 1.0,
+                                      "vcf_bytes": vcf_bytes, "counted_by_the_job": counted, "same_metrics_files_and_table": metrics_text() == separate_route}
         if a.separate and not a.no_vcf:
             mine = bench.output_digests(tmpdir, dirs)
             for sdir in dirs:
