@@ -411,6 +411,29 @@ int  snpgpu_vcf_count_snps_file(snpgpu_ctx *ctx, const char *path, uint32_t capa
 int  snpgpu_vcf_count_snps_files(snpgpu_ctx *ctx, const char *const *paths, uint32_t n_files, uint32_t capacity,
                                  uint64_t *out_counts, uint64_t *out_unusual_off, uint64_t *out_status, int32_t *out_rc);
 
+/* ---- merge_vcfs: the multi-sample VCF file from the per-sample files of this pipeline's own writer (vcf_merge.hip) ----------
+ * paths[n_files]: the files in COLUMN order, each with one sample column; out_path: the merged file (created or truncated);
+ * own_lines[own_len]: header lines of the caller (each with its LF) that go in front of #CHROM, where bcftools puts its two.
+ * The files are streamed through the staging ring; a kernel turns every data line inside the grammar (see vcf_merge.hip) into
+ * a record, the site union is a sort + unique, one wave merges a site (ALT union in column order, GT and the Number=A vectors
+ * re-indexed, NS summed, FILTER united), and the text is formatted on the device and written by the library's writer threads.
+ * A line outside the kernel's grammar, or longer than SNPGPU_VCF_LINE_WINDOW, is parsed on the host, one line at a time
+ * (stats->host_lines counts them); a line outside the host's rule as well, a position that comes twice in one file, or records of
+ * different REF at one position end the call with SNPGPU_E_UNSUPPORTED and a message that names the file and the byte offset
+ * (also in stats->bad_file / bad_offset); nothing is dropped silently.  SNPGPU_E_IO: a file cannot be read or written.
+ * The text leaves the device in rounds of sites: as many whole rows as the output buffer holds are formatted, copied back in
+ * 16 MiB pieces and written, then the next (stats->rounds); the buffer is 64 MiB, or 2^options bytes for options 12 to 32, and
+ * never shorter than the longest row.  The records and the [site][column] table are held whole: 160 bytes a record and 4 bytes
+ * a sample cell, at most 2^31 - 2 records.  Synchronous. */
+typedef struct snpgpu_merge_stats {
+    uint64_t columns, sites, cells, host_lines, bytes;          /* bytes: the size of the merged file */
+    uint64_t bad_file, bad_offset;                              /* of the line that ended the call (UINT64_MAX: none) */
+    double   seconds_parse, seconds_merge, seconds_write;       /* reading + parsing; union, rows and formatting; copy back + pwrite */
+    uint32_t writer_threads, rounds;                            /* rounds: ranges of sites the text went out in */
+} snpgpu_merge_stats;
+int  snpgpu_merge_vcf_files(snpgpu_ctx *ctx, const char *const *paths, uint32_t n_files, const char *out_path,
+                            const char *own_lines, uint32_t own_len, uint32_t options, snpgpu_merge_stats *stats);
+
 /* ---- resident pileups: the input side of the one-job pipeline (`cfsan_snp_pipeline hot_path_batch`) ----------------------
  * The reference runs steps 4-11 as separate process arrays over a shared file system (run.py:662-784): call_sites
  * (call_sites.py:89-108) and call_consensus twice (run.py:704-710, :712-718) each read a sample's reads.all.pileup again.

@@ -33,6 +33,12 @@ class SiteCounts(C.Structure):
 SPILL_SYMS, SPILL_REF, SPILL_CAP = 120, 64, 1024
 
 
+class MergeStats(C.Structure):
+    _fields_ = [("columns", C.c_uint64), ("sites", C.c_uint64), ("cells", C.c_uint64), ("host_lines", C.c_uint64), ("bytes", C.c_uint64),
+                ("bad_file", C.c_uint64), ("bad_offset", C.c_uint64), ("seconds_parse", C.c_double), ("seconds_merge", C.c_double),
+                ("seconds_write", C.c_double), ("writer_threads", C.c_uint32), ("rounds", C.c_uint32)]
+
+
 class SymbolSpill(C.Structure):
     _fields_ = [("n", C.c_uint32), ("ref_len", C.c_uint32), ("depth64", C.c_int64), ("sym", C.c_uint8 * SPILL_SYMS),
                 ("total", C.c_uint32 * SPILL_SYMS), ("fwd", C.c_uint32 * SPILL_SYMS), ("rev", C.c_uint32 * SPILL_SYMS),
@@ -169,6 +175,7 @@ SIGNATURES = {
     "snpgpu_dense_windows_dev": (C.c_int, [_P, _P, _P, C.c_uint32, C.c_uint32, _P, _P, C.c_uint32, _P, _P, _P, _P]),
     "snpgpu_merge_regions_dev": (C.c_int, [_P, _P, _P, _P, C.c_uint32, _P, _P, _P, _P]),
     "snpgpu_in_regions_dev": (C.c_int, [_P, _P, _P, C.c_uint32, _P, _P, _P, C.c_uint32, _P]),
+    "snpgpu_merge_vcf_files": (C.c_int, [_P, C.POINTER(C.c_char_p), C.c_uint32, C.c_char_p, C.c_char_p, C.c_uint32, C.c_uint32, _P]),
     "snpgpu_merge_sites_dev": (C.c_int, [_P, _P, _P, C.c_uint32, _P, _P, _P, _P]),
     "snpgpu_comm_available": (C.c_int, []),
     "snpgpu_comm_version": (C.c_int, [C.POINTER(C.c_int)]),

@@ -14,10 +14,10 @@ import argparse
 import os
 import sys
 
-from . import call_consensus, call_sites, collect_metrics, distance, filter_regions, hot_path, merge_sites, service, snp_matrix, snp_reference, utils
+from . import call_consensus, call_sites, collect_metrics, distance, filter_regions, hot_path, merge_sites, merge_vcfs, service, snp_matrix, snp_reference, utils
 from .utils import __version__, verbose_print
 
-NOT_PROVIDED = ("run", "data", "index_ref", "map_reads", "merge_vcfs",
+NOT_PROVIDED = ("run", "data", "index_ref", "map_reads",
                 "collect_metrics", "combine_metrics", "purge")
 
 
@@ -185,6 +185,12 @@ def parse_argument_list(argv):
     service.add_arguments(sub)
     _common(sub)
     sub.set_defaults(func=service.serve, excepthook=utils.handle_global_exception)
+
+    sub = subparsers.add_parser("merge_vcfs", help="Merge the per-sample VCF files", formatter_class=fmt,
+                                description="Merge the consensus vcf files from all samples into a single multi-vcf file for all samples.")
+    merge_vcfs.add_arguments(sub)
+    _common(sub)
+    sub.set_defaults(func=merge_vcfs.merge_vcfs, excepthook=utils.handle_global_exception)
 
     sub = subparsers.add_parser("snp_matrix", help="Create a matrix of SNPs", formatter_class=fmt,
                                 description="Create the SNP matrix containing the consensus base for each of the samples at the positions where high-confidence SNPs were found in any of the samples.")

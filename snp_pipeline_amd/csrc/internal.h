@@ -44,6 +44,7 @@ struct snpgpu_ctx {
 #define SNPGPU_K_DISTANCE 2
 #define SNPGPU_K_VARSCAN 3          // everything phase-1 site calling launches for one file (scan, walk, long walk)
 #define SNPGPU_K_VCF_COUNT 4        // the SNP count of a piece of a VCF file (vcf_count.hip)
+#define SNPGPU_K_VCF_MERGE 5        // the parse, rows and write kernels of merge_vcfs (vcf_merge.hip)
 // RAII-less helpers: call begin before the launch and end right after it (no-ops unless timing is enabled)
 // Start of a public call that produces per-site records: the spill is there and empty (enqueued on the context's stream).
 int snpgpu_spill_begin(snpgpu_ctx *ctx);
@@ -154,6 +155,32 @@ int snpgpu_enqueue_call_lines(snpgpu_ctx *ctx, const SampleDev *d_sample, const 
 #define SNPGPU_VCF_TILE 16384
 #define SNPGPU_VCF_LOOK SNPGPU_VCF_LINE_WINDOW
 int snpgpu_enqueue_vcf_count(snpgpu_ctx *ctx, const uint8_t *d_buf, uint32_t n, uint32_t own_from, uint64_t file_off, uint64_t *d_res, uint32_t capacity);
+// vcf_merge.hip: one record of one sample at one position, as the parse kernel (or the host, for a line the kernel leaves alone) fills it
+struct snpgpu_merge_cell {
+    uint64_t key;                   // FNV-1a of CHROM, later (contig in order of first appearance << 32) | POS
+    uint64_t off;                   // file offset of the line
+    uint32_t column, pos, ns, ft_mask;      // ft_mask: bit i = the i-th ##FILTER id of the header besides PASS
+    uint32_t sdp, rd, rdf, rdr;
+    uint32_t idx;                   // which of the distinct CHROM hashes
+    uint8_t ref, n_alt, gt, pad;    // gt: 0xFF for '.'
+    uint8_t alt[8];
+    uint32_t ad[8], adf[8], adr[8]; // 0xFFFFFFFF for '.'
+};
+static_assert(sizeof(snpgpu_merge_cell) == 160, "the merge record is 160 bytes");
+__host__ __device__ bool snpgpu_merge_parse_line(const uint8_t *p, uint32_t s, uint32_t e, const uint8_t *filt, const uint32_t *filt_off, uint32_t n_filt,
+                                                 bool strict, snpgpu_merge_cell *c);
+int snpgpu_enqueue_merge_parse(snpgpu_ctx *ctx, const uint8_t *d_buf, uint32_t n, uint32_t own_from, uint64_t file_off, uint32_t column, snpgpu_merge_cell *d_cells,
+                               uint64_t cell_cap, uint64_t *d_ctl, uint64_t *d_unusual, uint32_t unusual_cap, const uint8_t *d_filt, const uint32_t *d_filt_off,
+                               uint32_t n_filt);
+int snpgpu_enqueue_merge_hash_keys(snpgpu_ctx *ctx, const snpgpu_merge_cell *d_cells, uint64_t n, uint64_t *d_keys, uint32_t *d_zeros);
+int snpgpu_enqueue_merge_contig_first(snpgpu_ctx *ctx, snpgpu_merge_cell *d_cells, uint64_t n, const uint64_t *d_uniq, const uint32_t *d_n_uniq, uint64_t *d_first);
+int snpgpu_enqueue_merge_site_keys(snpgpu_ctx *ctx, snpgpu_merge_cell *d_cells, uint64_t n, const uint32_t *d_rank, uint64_t *d_keys, uint32_t *d_cols);
+int snpgpu_enqueue_merge_scatter(snpgpu_ctx *ctx, const snpgpu_merge_cell *d_cells, uint64_t n, const uint64_t *d_sites, const uint32_t *d_n_sites, uint32_t n_col,
+                                 uint32_t *d_table, uint64_t *d_ctl);
+size_t snpgpu_merge_rows_scan_words(uint32_t n_sites);
+int snpgpu_enqueue_merge_rows(snpgpu_ctx *ctx, int write, const snpgpu_merge_cell *d_cells, const uint32_t *d_table, uint32_t n_col, const uint64_t *d_site_keys,
+                              uint32_t n_sites, uint32_t site_lo, uint32_t site_hi, uint64_t out_base, const uint8_t *d_names, const uint32_t *d_name_off, const uint8_t *d_filt, const uint32_t *d_filt_off,
+                              uint64_t *d_row_len, uint64_t *d_row_end, uint64_t *d_scan_ws, uint8_t *d_out, uint64_t *d_ctl);
 // the call kernels over a scanned batch (consensus.hip); d_todo_n: 4 words (3 zeroed), d_todo / d_todo2: n * n_sites entries each;
 // lines_out.hip: the per-line records of --vcfAllPos packed into 24 bytes where they fit, the others gathered as they are
 size_t snpgpu_compact_lines_workspace_words(uint64_t n_lines);

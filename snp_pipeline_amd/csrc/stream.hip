@@ -1834,8 +1834,10 @@ int snpgpu_pileups_get_stats(const snpgpu_pileups *store, snpgpu_pileups_stats *
 // words.  All results come back in one copy at the end.
 namespace {
 
-int vcf_count_stream(snpgpu_ctx *ctx, const char *const *paths, uint32_t n_files, uint32_t capacity, uint64_t *out_counts, uint64_t *out_unusual_off,
-                     uint64_t *out_status, int32_t *out_rc) {
+// begin(d_extra): enqueue what has to happen before the first piece; piece(d_buf, len, own_from, job): enqueue the work on one piece;
+// end(d_extra): enqueue what follows the last piece and wait for it.  extra_bytes of scratch behind the piece buffers are the caller's.
+template <class Begin, class Piece, class End>
+int vcf_stream(snpgpu_ctx *ctx, const char *const *paths, uint32_t n_files, size_t extra_bytes, int32_t *out_rc, Begin begin, Piece piece, End end) {
     constexpr uint32_t N_DEV = 3;                               // device buffers a chunk is counted in
     HIP_TRY(ctx, snpgpu_enter(ctx));
     const size_t chunk = (size_t)16 << 20;                      // the staging chunks of the pileup streams: the pinned ring is shared with them
@@ -1864,17 +1866,14 @@ int vcf_count_stream(snpgpu_ctx *ctx, const char *const *paths, uint32_t n_files
         return snpgpu_set_error(ctx, SNPGPU_E_NOMEM, "no memory for the job list of %u files", n_files);
     }
     const uint64_t J = jobs.size();
-    const size_t res_words = 3 + (size_t)capacity;
-
     // everything that has to be undone lives here, and every exit after this point goes through `done`
     Opener opener;
     Shared sh;
     std::vector<std::thread> readers;
     hipEvent_t ev_counted[N_DEV] = {nullptr, nullptr, nullptr};
-    std::vector<uint64_t> h_res;
     snpgpu_stream_pool *p = nullptr;
     uint8_t *d_buf[N_DEV] = {nullptr, nullptr, nullptr};
-    uint64_t *d_res = nullptr;
+    void *d_extra = nullptr;
     hipStream_t st = ctx->stream;
     uint64_t R = 1;
     int rc = SNPGPU_OK;
@@ -1885,7 +1884,6 @@ int vcf_count_stream(snpgpu_ctx *ctx, const char *const *paths, uint32_t n_files
         if (e_ != hipSuccess) { rc = snpgpu_set_error(ctx, SNPGPU_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); goto done; } \
     } while (0)
 
-    try { h_res.assign((size_t)n_files * res_words, 0); } catch (const std::exception &) { rc = snpgpu_set_error(ctx, SNPGPU_E_NOMEM, "no memory for the results"); goto done; }
     try { opener.start(&src, chunks_of); } catch (const std::exception &) { rc = snpgpu_set_error(ctx, SNPGPU_E_NOMEM, "no memory for the file opener"); goto done; }
     opened = true;
     {
@@ -1897,15 +1895,16 @@ int vcf_count_stream(snpgpu_ctx *ctx, const char *const *paths, uint32_t n_files
         if (rc) goto done;
         p = ctx->pool;
         R = p->staging.size() < n_staging ? p->staging.size() : n_staging;
-        const size_t buf_bytes = chunk + 256, res_bytes = up(8 * res_words * n_files, 256);
+        const size_t buf_bytes = chunk + 256, res_bytes = up(extra_bytes, 256);
         void *ws = nullptr;
         rc = snpgpu_scratch(ctx, N_DEV * buf_bytes + res_bytes + 256, &ws);
         if (rc) goto done;
         for (uint32_t i = 0; i < N_DEV; ++i) d_buf[i] = (uint8_t *)ws + i * buf_bytes;
-        d_res = (uint64_t *)((uint8_t *)ws + N_DEV * buf_bytes);
+        d_extra = (uint8_t *)ws + N_DEV * buf_bytes;
         VC_TRY(hipStreamSynchronize(st));                       // whatever used the scratch before is done
         for (uint32_t i = 0; i < N_DEV; ++i) VC_TRY(hipEventCreateWithFlags(&ev_counted[i], hipEventDisableTiming));
-        VC_TRY(hipMemsetAsync(d_res, 0, res_bytes, st));
+        rc = begin(d_extra);
+        if (rc) goto done;
         sh.R = R;
         sh.opener = &opener;
         try {
@@ -1942,13 +1941,13 @@ int vcf_count_stream(snpgpu_ctx *ctx, const char *const *paths, uint32_t n_files
             VC_TRY(hipEventRecord(p->ev_copy[j % R], cs));
             VC_TRY(hipStreamWaitEvent(st, p->ev_copy[j % R], 0));
             if (s.rc == SNPGPU_OK && s.size) {
-                rc = snpgpu_enqueue_vcf_count(ctx, d_buf[b], len, jb.first ? 0 : SNPGPU_VCF_LOOK, jb.off, d_res + (size_t)jb.file * res_words, capacity);
+                rc = piece(d_buf[b], len, jb.first ? 0u : (uint32_t)SNPGPU_VCF_LOOK, jb);
                 if (rc) goto done;
             }
             VC_TRY(hipEventRecord(ev_counted[b], st));
         }
-        VC_TRY(hipMemcpyAsync(h_res.data(), d_res, 8 * res_words * n_files, hipMemcpyDeviceToHost, st));
-        VC_TRY(hipStreamSynchronize(st));
+        rc = end(d_extra);
+        if (rc) goto done;
     }
 done:
 #undef VC_TRY
@@ -1966,6 +1965,28 @@ done:
     }
     for (hipEvent_t e : ev_counted) if (e) (void)hipEventDestroy(e);
     if (rc) return rc;
+    for (uint32_t f = 0; f < n_files; ++f) out_rc[f] = src[f].rc;   // SNPGPU_E_IO: the file could not be opened or read (its results are void)
+    return SNPGPU_OK;
+}
+
+int vcf_count_stream(snpgpu_ctx *ctx, const char *const *paths, uint32_t n_files, uint32_t capacity, uint64_t *out_counts, uint64_t *out_unusual_off,
+                     uint64_t *out_status, int32_t *out_rc) {
+    const size_t res_words = 3 + (size_t)capacity;
+    std::vector<uint64_t> h_res;
+    try { h_res.assign((size_t)n_files * res_words, 0); } catch (const std::exception &) { return snpgpu_set_error(ctx, SNPGPU_E_NOMEM, "no memory for the results"); }
+    hipStream_t st = ctx->stream;
+    uint64_t *d_res = nullptr;
+    const int rc = vcf_stream(ctx, paths, n_files, 8 * res_words * n_files, out_rc,
+        [&](void *d_extra) { d_res = (uint64_t *)d_extra; HIP_TRY(ctx, hipMemsetAsync(d_res, 0, 8 * res_words * n_files, st)); return (int)SNPGPU_OK; },
+        [&](const uint8_t *d_buf, uint32_t len, uint32_t own_from, const Job &jb) {
+            return snpgpu_enqueue_vcf_count(ctx, d_buf, len, own_from, jb.off, d_res + (size_t)jb.file * res_words, capacity);
+        },
+        [&](void *) {
+            HIP_TRY(ctx, hipMemcpyAsync(h_res.data(), d_res, 8 * res_words * n_files, hipMemcpyDeviceToHost, st));
+            HIP_TRY(ctx, hipStreamSynchronize(st));
+            return (int)SNPGPU_OK;
+        });
+    if (rc) return rc;
     for (uint32_t f = 0; f < n_files; ++f) {
         const uint64_t *r = h_res.data() + (size_t)f * res_words;
         uint64_t *cnt = out_counts + 3 * (size_t)f;
@@ -1978,8 +1999,418 @@ done:
         }
         std::sort(out_unusual_off + (size_t)f * capacity, out_unusual_off + (size_t)f * capacity + n_off);
         out_status[f] = status;
-        out_rc[f] = src[f].rc;                                  // SNPGPU_E_IO: the file could not be opened or read (its counts are void)
     }
+    return SNPGPU_OK;
+}
+
+
+// ---- merge_vcfs (vcf_merge.hip) -----------------------------------------------------------------------------------------------
+// The header lines and the #CHROM line of a VCF file: read from its start until the first data line.
+bool merge_read_head(const char *path, std::vector<std::string> &header, std::string &chrom_line) {
+    const int fd = open(path, O_RDONLY | O_CLOEXEC);
+    if (fd < 0) return false;
+    std::string text;
+    char block[65536];
+    size_t at = 0;
+    bool done = false, ok = true;
+    while (!done) {
+        const ssize_t got = pread(fd, block, sizeof block, (off_t)text.size());
+        if (got < 0) { ok = false; break; }
+        text.append(block, (size_t)got);
+        const bool eof = got == 0;
+        for (;;) {
+            size_t end = text.find('\n', at);
+            if (end == std::string::npos) { if (!eof) break; end = text.size(); if (end == at) { done = true; break; } }
+            std::string line = text.substr(at, end - at);
+            if (!line.empty() && line.back() == '\r') line.pop_back();
+            at = end + 1;
+            if (line.empty()) continue;
+            if (line[0] != '#') { done = true; break; }
+            if (chrom_line.empty()) { if (line.compare(0, 6, "#CHROM") == 0) chrom_line = line; else header.push_back(line); }
+            if (at >= text.size() && eof) { done = true; break; }
+        }
+        if (eof) done = true;
+    }
+    close(fd);
+    return ok;
+}
+
+// The line of the file whose first byte is at `off`, or (bit 63) whose terminator is there; *start: its first byte.
+bool merge_read_line(int fd, uint64_t off, std::string &line, uint64_t *start) {
+    char block[65536];
+    line.clear();
+    if (off >> 63) {
+        uint64_t at = off & ~(1ull << 63);
+        std::string rev;
+        bool found = false;
+        while (at > 0 && !found) {
+            const uint64_t lo = at > sizeof block ? at - sizeof block : 0;
+            if (pread(fd, block, at - lo, (off_t)lo) != (ssize_t)(at - lo)) return false;
+            uint64_t k = at - lo;
+            while (k > 0 && block[k - 1] != '\n') --k;
+            found = k > 0;
+            line.insert(0, block + k, at - lo - k);
+            at = lo + k;
+        }
+        *start = at;
+    } else {
+        *start = off;
+        for (uint64_t at = off;;) {
+            const ssize_t got = pread(fd, block, sizeof block, (off_t)at);
+            if (got < 0) return false;
+            if (got == 0) break;
+            const void *nl = memchr(block, '\n', (size_t)got);
+            if (nl) { line.append(block, (const char *)nl - block); break; }
+            line.append(block, (size_t)got);
+            at += (uint64_t)got;
+        }
+    }
+    if (!line.empty() && line.back() == '\r') line.pop_back();
+    return true;
+}
+
+struct MergeBuffers {                // everything merge_vcf_files allocates on the device, freed on every way out
+    std::vector<void *> d;
+    ~MergeBuffers() { for (void *p : d) if (p) (void)hipFree(p); }
+    template <class T> hipError_t get(T **out, size_t bytes) {
+        void *p = nullptr;
+        const hipError_t e = hipMalloc(&p, bytes ? bytes : 256);
+        if (e == hipSuccess) d.push_back(p);
+        *out = (T *)p;
+        return e;
+    }
+};
+
+double seconds_since(const std::chrono::steady_clock::time_point &t0) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); }
+
+int merge_vcf_files(snpgpu_ctx *ctx, const char *const *paths, uint32_t n_files, const char *out_path, const char *own_lines, uint32_t own_len,
+                    uint64_t out_cap, snpgpu_merge_stats *stats) {
+    constexpr uint32_t UNUSUAL_CAP = 1u << 16;
+    HIP_TRY(ctx, snpgpu_enter(ctx));
+    hipStream_t st = ctx->stream;
+    auto t0 = std::chrono::steady_clock::now();
+    // the headers: the first file's lines, every file's column name, the filter ids the records are held against
+    std::vector<std::string> header, names(n_files);
+    std::string filt;
+    std::vector<uint32_t> filt_off(1, 0);
+    uint64_t total_bytes = 0;
+    for (uint32_t f = 0; f < n_files; ++f) {
+        std::vector<std::string> h;
+        std::string chrom;
+        struct stat stt;
+        if (!paths[f] || stat(paths[f], &stt) != 0 || !merge_read_head(paths[f], f ? h : header, chrom)) {
+            stats->bad_file = f;
+            return snpgpu_set_error(ctx, SNPGPU_E_IO, "cannot open or read the VCF file %s", paths[f] ? paths[f] : "(null)");
+        }
+        total_bytes += (uint64_t)stt.st_size;
+        size_t tabs = 0, last = 0;
+        for (size_t i = 0; i < chrom.size(); ++i) if (chrom[i] == '\t') { ++tabs; last = i; }
+        if (tabs != 9) {
+            stats->bad_file = f;
+            return snpgpu_set_error(ctx, SNPGPU_E_UNSUPPORTED, "%s: no #CHROM line with one sample column", paths[f]);
+        }
+        names[f] = chrom.substr(last + 1);
+    }
+    for (const std::string &h : header) {
+        const char key[] = "##FILTER=<ID=";
+        if (h.compare(0, sizeof key - 1, key) != 0) continue;
+        const size_t a = sizeof key - 1, b = h.find_first_of(",>", a);
+        const std::string id = h.substr(a, b == std::string::npos ? std::string::npos : b - a);
+        if (id == "PASS") continue;
+        filt += id;
+        filt_off.push_back((uint32_t)filt.size());
+    }
+    const uint32_t n_filt = (uint32_t)filt_off.size() - 1;
+    if (n_filt > 31) return snpgpu_set_error(ctx, SNPGPU_E_UNSUPPORTED, "%s: more than 31 filters", paths[0]);
+
+    MergeBuffers mem;
+    const uint64_t cell_cap = total_bytes / 56 + UNUSUAL_CAP + 64;      // (no line of the grammar is shorter than 56 bytes)
+    if (cell_cap > 0x7FFFFFFEull) return snpgpu_set_error(ctx, SNPGPU_E_UNSUPPORTED, "too many VCF records for one merge");
+    snpgpu_merge_cell *d_cells = nullptr;
+    uint64_t *d_ctl = nullptr, *d_unusual = nullptr;
+    uint8_t *d_filt = nullptr;
+    uint32_t *d_filt_off = nullptr;
+    HIP_TRY(ctx, mem.get(&d_cells, cell_cap * sizeof(snpgpu_merge_cell)));
+    HIP_TRY(ctx, mem.get(&d_ctl, 64));
+    HIP_TRY(ctx, mem.get(&d_unusual, 16ull * UNUSUAL_CAP));
+    HIP_TRY(ctx, mem.get(&d_filt, filt.size() + 16));
+    HIP_TRY(ctx, mem.get(&d_filt_off, 4 * filt_off.size()));
+    HIP_TRY(ctx, hipMemsetAsync(d_ctl, 0, 64, st));
+    if (!filt.empty()) HIP_TRY(ctx, hipMemcpyAsync(d_filt, filt.data(), filt.size(), hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(d_filt_off, filt_off.data(), 4 * filt_off.size(), hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+
+    // parse: the files as one stream
+    std::vector<int32_t> file_rc(n_files, 0);
+    uint64_t ctl[8] = {0};
+    int rc = vcf_stream(ctx, paths, n_files, 0, file_rc.data(),
+        [&](void *) { return (int)SNPGPU_OK; },
+        [&](const uint8_t *d_buf, uint32_t len, uint32_t own_from, const Job &jb) {
+            return snpgpu_enqueue_merge_parse(ctx, d_buf, len, own_from, jb.off, jb.file, d_cells, cell_cap, d_ctl, d_unusual, UNUSUAL_CAP, d_filt, d_filt_off, n_filt);
+        },
+        [&](void *) {
+            HIP_TRY(ctx, hipMemcpyAsync(ctl, d_ctl, 64, hipMemcpyDeviceToHost, st));
+            HIP_TRY(ctx, hipStreamSynchronize(st));
+            return (int)SNPGPU_OK;
+        });
+    if (rc) return rc;
+    for (uint32_t f = 0; f < n_files; ++f)
+        if (file_rc[f]) { stats->bad_file = f; return snpgpu_set_error(ctx, SNPGPU_E_IO, "cannot open or read the VCF file %s", paths[f]); }
+    if (ctl[2] & 1) return snpgpu_set_error(ctx, SNPGPU_E_UNSUPPORTED, "more VCF records than the merge made room for");
+    if (ctl[1] > UNUSUAL_CAP) return snpgpu_set_error(ctx, SNPGPU_E_UNSUPPORTED, "%llu lines outside the kernel's grammar: more than the %u the host takes", (unsigned long long)ctl[1], UNUSUAL_CAP);
+    uint64_t n_cells = ctl[0];
+    // the lines the kernel left alone: one at a time on the host, by the same routine in its wider setting
+    if (ctl[1]) {
+        std::vector<uint64_t> unusual(2 * ctl[1]);
+        HIP_TRY(ctx, hipMemcpy(unusual.data(), d_unusual, 16 * ctl[1], hipMemcpyDeviceToHost));
+        std::vector<snpgpu_merge_cell> extra;
+        std::string line;
+        for (uint64_t k = 0; k < ctl[1]; ++k) {
+            const uint32_t f = (uint32_t)unusual[2 * k];
+            const int fd = open(paths[f], O_RDONLY | O_CLOEXEC);
+            uint64_t start = 0;
+            const bool got = fd >= 0 && merge_read_line(fd, unusual[2 * k + 1], line, &start);
+            if (fd >= 0) close(fd);
+            if (!got) { stats->bad_file = f; return snpgpu_set_error(ctx, SNPGPU_E_IO, "cannot open or read the VCF file %s", paths[f]); }
+            if (line.empty() || line[0] == '#') continue;
+            snpgpu_merge_cell c;
+            if (line.size() > 0x7FFFFFFFu ||
+                !snpgpu_merge_parse_line((const uint8_t *)line.data(), 0, (uint32_t)line.size(), (const uint8_t *)filt.data(), filt_off.data(), n_filt, false, &c)) {
+                stats->bad_file = f;
+                stats->bad_offset = start;
+                return snpgpu_set_error(ctx, SNPGPU_E_UNSUPPORTED, "%s: the line at byte %llu is outside the pipeline's own VCF grammar, on which alone the merge is pinned",
+                                        paths[f], (unsigned long long)start);
+            }
+            c.off = start;
+            c.column = f;
+            extra.push_back(c);
+            ++stats->host_lines;
+        }
+        if (n_cells + extra.size() > cell_cap) return snpgpu_set_error(ctx, SNPGPU_E_UNSUPPORTED, "more VCF records than the merge made room for");
+        if (!extra.empty()) HIP_TRY(ctx, hipMemcpy(d_cells + n_cells, extra.data(), extra.size() * sizeof(snpgpu_merge_cell), hipMemcpyHostToDevice));
+        n_cells += extra.size();
+    }
+    stats->cells = n_cells;
+    stats->seconds_parse = seconds_since(t0);
+    t0 = std::chrono::steady_clock::now();
+
+    // contigs in order of first appearance over the columns, then the site union
+    std::vector<std::string> contigs;
+    uint32_t n_sites = 0;
+    uint64_t *d_keys = nullptr, *d_uniq = nullptr, *d_first = nullptr;
+    uint32_t *d_cols = nullptr, *d_off = nullptr, *d_carrier = nullptr, *d_n = nullptr, *d_rank = nullptr, *d_table = nullptr, *d_name_off = nullptr;
+    uint8_t *d_names = nullptr;
+    if (n_cells) {
+        HIP_TRY(ctx, mem.get(&d_keys, 8 * n_cells));
+        HIP_TRY(ctx, mem.get(&d_uniq, 8 * n_cells));
+        HIP_TRY(ctx, mem.get(&d_cols, 4 * n_cells));
+        HIP_TRY(ctx, mem.get(&d_off, 4 * (n_cells + 1)));
+        HIP_TRY(ctx, mem.get(&d_carrier, 4 * n_cells));
+        HIP_TRY(ctx, mem.get(&d_n, 16));
+        rc = snpgpu_enqueue_merge_hash_keys(ctx, d_cells, n_cells, d_keys, d_cols);
+        if (rc) return rc;
+        rc = snpgpu_merge_sites_dev(ctx, d_keys, d_cols, (uint32_t)n_cells, d_uniq, d_off, d_carrier, d_n);
+        if (rc) return rc;
+        uint32_t n_u[2] = {0, 0};
+        HIP_TRY(ctx, hipMemcpyAsync(n_u, d_n, 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, hipStreamSynchronize(st));
+        HIP_TRY(ctx, mem.get(&d_first, 8ull * n_u[0]));
+        HIP_TRY(ctx, mem.get(&d_rank, 4ull * n_u[0]));
+        HIP_TRY(ctx, hipMemsetAsync(d_first, 0xFF, 8ull * n_u[0], st));
+        rc = snpgpu_enqueue_merge_contig_first(ctx, d_cells, n_cells, d_uniq, d_n, d_first);
+        if (rc) return rc;
+        std::vector<uint64_t> first(n_u[0]);
+        HIP_TRY(ctx, hipMemcpyAsync(first.data(), d_first, 8ull * n_u[0], hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, hipStreamSynchronize(st));
+        std::vector<uint32_t> order(n_u[0]), rank(n_u[0]), name_off(1, 0);
+        for (uint32_t i = 0; i < n_u[0]; ++i) order[i] = i;
+        std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return first[a] < first[b]; });
+        std::string all_names, line;
+        for (uint32_t r = 0; r < n_u[0]; ++r) {
+            rank[order[r]] = r;
+            const uint32_t f = (uint32_t)(first[order[r]] >> 40);
+            const int fd = open(paths[f], O_RDONLY | O_CLOEXEC);
+            uint64_t start = 0;
+            const bool got = fd >= 0 && merge_read_line(fd, first[order[r]] & ((1ull << 40) - 1), line, &start);
+            if (fd >= 0) close(fd);
+            if (!got) { stats->bad_file = f; return snpgpu_set_error(ctx, SNPGPU_E_IO, "cannot open or read the VCF file %s", paths[f]); }
+            contigs.push_back(line.substr(0, line.find('\t')));
+            all_names += contigs.back();
+            name_off.push_back((uint32_t)all_names.size());
+        }
+        HIP_TRY(ctx, mem.get(&d_names, all_names.size() + 16));
+        HIP_TRY(ctx, mem.get(&d_name_off, 4 * name_off.size()));
+        HIP_TRY(ctx, hipMemcpyAsync(d_names, all_names.data(), all_names.size(), hipMemcpyHostToDevice, st));
+        HIP_TRY(ctx, hipMemcpyAsync(d_name_off, name_off.data(), 4 * name_off.size(), hipMemcpyHostToDevice, st));
+        HIP_TRY(ctx, hipMemcpyAsync(d_rank, rank.data(), 4ull * n_u[0], hipMemcpyHostToDevice, st));
+        rc = snpgpu_enqueue_merge_site_keys(ctx, d_cells, n_cells, d_rank, d_keys, d_cols);
+        if (rc) return rc;
+        rc = snpgpu_merge_sites_dev(ctx, d_keys, d_cols, (uint32_t)n_cells, d_uniq, d_off, d_carrier, d_n);
+        if (rc) return rc;
+        HIP_TRY(ctx, hipMemcpyAsync(n_u, d_n, 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, hipStreamSynchronize(st));              // (the host vectors above were copied from)
+        n_sites = n_u[0];
+        if ((uint64_t)n_sites * n_files > 0xFFFFFFFFFFull) return snpgpu_set_error(ctx, SNPGPU_E_UNSUPPORTED, "too many sample cells for one merge");
+        HIP_TRY(ctx, mem.get(&d_table, 4ull * n_sites * n_files));
+        HIP_TRY(ctx, hipMemsetAsync(d_table, 0, 4ull * n_sites * n_files, st));
+        rc = snpgpu_enqueue_merge_scatter(ctx, d_cells, n_cells, d_uniq, d_n, n_files, d_table, d_ctl);
+        if (rc) return rc;
+    }
+    stats->sites = n_sites;
+
+    // the header
+    std::string head;
+    {
+        const std::string pass_line = "##FILTER=<ID=PASS,Description=\"All filters passed\">";
+        std::vector<std::string> lines;
+        for (const std::string &h : header) if (h != pass_line) lines.push_back(h);
+        lines.insert(lines.begin() + ((!lines.empty() && lines[0].compare(0, 12, "##fileformat") == 0) ? 1 : 0), pass_line);
+        for (const std::string &l : lines) { head += l; head += '\n'; }
+        for (const std::string &c : contigs) { head += "##contig=<ID=" + c + ">\n"; }
+        if (own_lines && own_len) head.append(own_lines, own_len);
+        head += "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT";
+        for (const std::string &n : names) { head += '\t'; head += n; }
+        head += '\n';
+    }
+
+    // rows: the lengths and offsets of all sites (16 bytes a site) ...
+    uint64_t out_bytes = 0;
+    uint64_t *d_row_len = nullptr, *d_row_end = nullptr, *d_scan = nullptr;
+    std::vector<uint64_t> row_end;
+    if (n_sites) {
+        HIP_TRY(ctx, mem.get(&d_row_len, 8ull * n_sites));
+        HIP_TRY(ctx, mem.get(&d_row_end, 8ull * n_sites));
+        HIP_TRY(ctx, mem.get(&d_scan, 8 * (snpgpu_merge_rows_scan_words(n_sites) + 1)));
+        rc = snpgpu_enqueue_merge_rows(ctx, 0, d_cells, d_table, n_files, d_uniq, n_sites, 0, n_sites, 0, d_names, d_name_off, d_filt, d_filt_off, d_row_len, d_row_end, d_scan,
+                                       nullptr, d_ctl);
+        if (rc) return rc;
+        row_end.resize(n_sites);
+        HIP_TRY(ctx, hipMemcpyAsync(row_end.data(), d_row_end, 8ull * n_sites, hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, hipMemcpyAsync(ctl, d_ctl, 64, hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, hipStreamSynchronize(st));
+        out_bytes = row_end[n_sites - 1];
+        if (ctl[2] & 2) {
+            snpgpu_merge_cell c;
+            HIP_TRY(ctx, hipMemcpy(&c, d_cells + ctl[3], sizeof c, hipMemcpyDeviceToHost));
+            stats->bad_file = c.column;
+            stats->bad_offset = c.off;
+            return snpgpu_set_error(ctx, SNPGPU_E_UNSUPPORTED, "%s: the position of the line at byte %llu comes twice in the file", paths[c.column], (unsigned long long)c.off);
+        }
+        if (ctl[2] & 4) return snpgpu_set_error(ctx, SNPGPU_E_UNSUPPORTED, "records of different REF at one position: outside the grammar the merge is pinned on");
+    }
+    // ... and the rounds: as many whole rows as the output buffer holds (a row longer than the buffer is a round of its own,
+    // and the buffer is as long as the longest round)
+    struct Round { uint32_t lo, hi; uint64_t base, len; };
+    std::vector<Round> rounds;
+    uint64_t buf_bytes = 0;
+    for (uint32_t lo = 0; lo < n_sites;) {
+        const uint64_t base = lo ? row_end[lo - 1] : 0;
+        uint32_t hi = (uint32_t)(std::upper_bound(row_end.begin() + lo, row_end.end(), base + out_cap) - row_end.begin());
+        if (hi == lo) hi = lo + 1;
+        rounds.push_back(Round{lo, hi, base, row_end[hi - 1] - base});
+        if (rounds.back().len > buf_bytes) buf_bytes = rounds.back().len;
+        lo = hi;
+    }
+    std::vector<uint64_t>().swap(row_end);
+    stats->rounds = (uint32_t)(rounds.size() < 0xFFFFFFFFu ? rounds.size() : 0xFFFFFFFFu);
+    uint8_t *d_out = nullptr;
+    if (n_sites) HIP_TRY(ctx, mem.get(&d_out, buf_bytes + 16));
+    stats->seconds_merge = seconds_since(t0);
+    t0 = std::chrono::steady_clock::now();
+
+    // the file: each round's text comes back in pieces through the staging ring, writer threads pwrite each piece at its place
+    // (the time of the rounds' text kernels is in seconds_write: they run between the copies)
+    const int fd = open(out_path, O_WRONLY | O_CREAT | O_TRUNC | O_CLOEXEC, 0666);
+    if (fd < 0) return snpgpu_set_error(ctx, SNPGPU_E_IO, "cannot create %s", out_path);
+    bool io_ok = true;
+    for (size_t at = 0; at < head.size() && io_ok;) {
+        const ssize_t w = pwrite(fd, head.data() + at, head.size() - at, (off_t)at);
+        if (w <= 0) io_ok = false; else at += (size_t)w;
+    }
+    const size_t chunk = (size_t)16 << 20;
+    uint64_t n_pieces = 0;
+    for (const Round &r : rounds) n_pieces += (r.len + chunk - 1) / chunk;
+    uint32_t n_writers = snpgpu_writer_threads(16);
+    if (n_writers > n_pieces) n_writers = (uint32_t)n_pieces;
+    if (n_writers < 1) n_writers = 1;
+    stats->writer_threads = n_writers;
+    rc = SNPGPU_OK;
+    if (n_pieces) {
+        const uint32_t n_ring = (uint32_t)(n_pieces < n_writers + 2 ? n_pieces : n_writers + 2);
+        rc = pool_ensure(ctx, chunk, n_ring, 0, 0, 0, 0);
+        if (rc) { close(fd); return rc; }
+        snpgpu_stream_pool *p = ctx->pool;
+        const uint64_t R = p->staging.size() < n_ring ? p->staging.size() : n_ring;
+        struct Piece { uint64_t slot, off, len; };              // staging buffer, offset in the rows' text, bytes
+        std::mutex mu;
+        std::condition_variable cv;
+        std::vector<Piece> ready;                               // pieces copied back, waiting for a writer
+        std::vector<char> busy(R, 0);                           // staging buffer in use (being filled or written)
+        bool closing = false, failed = false;
+        std::vector<std::thread> writers;
+        auto writer_main = [&] {
+            for (;;) {
+                Piece pc;
+                {
+                    std::unique_lock<std::mutex> lk(mu);
+                    cv.wait(lk, [&] { return closing || !ready.empty(); });
+                    if (ready.empty()) return;
+                    pc = ready.back();
+                    ready.pop_back();
+                }
+                const char *h = (const char *)p->staging[pc.slot];
+                bool ok = true;
+                for (uint64_t at = 0; at < pc.len && ok;) {
+                    const ssize_t w = pwrite(fd, h + at, pc.len - at, (off_t)(head.size() + pc.off + at));
+                    if (w <= 0) ok = false; else at += (uint64_t)w;
+                }
+                {
+                    std::lock_guard<std::mutex> lk(mu);
+                    busy[pc.slot] = 0;
+                    if (!ok) failed = true;
+                }
+                cv.notify_all();
+            }
+        };
+        try {
+            for (uint32_t i = 0; i < n_writers; ++i) writers.emplace_back(writer_main);
+        } catch (const std::exception &) {
+            if (writers.empty()) { close(fd); return snpgpu_set_error(ctx, SNPGPU_E_NOMEM, "cannot start a writer thread"); }
+        }
+        hipError_t herr = hipSuccess;
+        int krc = SNPGPU_OK;
+        uint64_t j = 0;
+        for (size_t r = 0; r < rounds.size() && herr == hipSuccess && krc == SNPGPU_OK; ++r) {
+            const Round &rd = rounds[r];                        // (the copies of the round before are complete: the buffer is free)
+            krc = snpgpu_enqueue_merge_rows(ctx, 1, d_cells, d_table, n_files, d_uniq, n_sites, rd.lo, rd.hi, rd.base, d_names, d_name_off, d_filt, d_filt_off, d_row_len,
+                                            d_row_end, d_scan, d_out, d_ctl);
+            for (uint64_t lo = 0; lo < rd.len && herr == hipSuccess && krc == SNPGPU_OK; lo += chunk, ++j) {
+                const uint64_t slot = j % R;
+                {
+                    std::unique_lock<std::mutex> lk(mu);
+                    cv.wait(lk, [&] { return !busy[slot]; });
+                    busy[slot] = 1;
+                }
+                const uint64_t len = rd.len - lo < chunk ? rd.len - lo : chunk;
+                herr = hipMemcpyAsync(p->staging[slot], d_out + lo, len, hipMemcpyDeviceToHost, st);
+                if (herr == hipSuccess) herr = hipStreamSynchronize(st);
+                if (herr != hipSuccess) break;
+                { std::lock_guard<std::mutex> lk(mu); ready.push_back(Piece{slot, rd.base + lo, len}); }
+                cv.notify_all();
+            }
+        }
+        { std::lock_guard<std::mutex> lk(mu); closing = true; }
+        cv.notify_all();
+        for (auto &t : writers) t.join();
+        if (krc) rc = krc;
+        else if (herr != hipSuccess) rc = snpgpu_set_error(ctx, SNPGPU_E_HIP, "copying the merged text back failed: %s", hipGetErrorString(herr));
+        if (failed) io_ok = false;
+    }
+    if (close(fd) != 0) io_ok = false;
+    if (rc) return rc;
+    if (!io_ok) return snpgpu_set_error(ctx, SNPGPU_E_IO, "cannot write %s", out_path);
+    stats->bytes = head.size() + out_bytes;
+    stats->seconds_write = seconds_since(t0);
     return SNPGPU_OK;
 }
 
@@ -2002,6 +2433,21 @@ int snpgpu_vcf_count_snps_file(snpgpu_ctx *ctx, const char *path, uint32_t capac
     const int rc = snpgpu_vcf_count_snps_files(ctx, &path, 1, capacity, out_counts, out_unusual_off, out_status, &file_rc);
     if (rc) return rc;
     return file_rc ? snpgpu_set_error(ctx, file_rc, "cannot open or read the VCF file %s", path) : SNPGPU_OK;
+}
+
+int snpgpu_merge_vcf_files(snpgpu_ctx *ctx, const char *const *paths, uint32_t n_files, const char *out_path, const char *own_lines, uint32_t own_len,
+                           uint32_t options, snpgpu_merge_stats *stats) {
+    if (!ctx || !paths || !out_path || !stats || (own_len && !own_lines)) return snpgpu_set_error(ctx, SNPGPU_E_ARG, "null argument");
+    if (options && (options < 12 || options > 32)) return snpgpu_set_error(ctx, SNPGPU_E_ARG, "options: 0, or 12 to 32, the log2 of the output buffer's bytes");
+    if (n_files == 0 || n_files >= (1u << 24)) return snpgpu_set_error(ctx, SNPGPU_E_ARG, "the merge takes 1 to 2^24 - 1 files");
+    *stats = snpgpu_merge_stats{};
+    stats->columns = n_files;
+    stats->bad_file = stats->bad_offset = UINT64_MAX;
+    try {
+        return merge_vcf_files(ctx, paths, n_files, out_path, own_lines, own_len, 1ull << (options ? options : 26), stats);
+    } catch (const std::exception &e) {                         // (no exception may leave through the C ABI)
+        return snpgpu_set_error(ctx, SNPGPU_E_NOMEM, "merge_vcf_files: %s", e.what());
+    }
 }
 
 }  // extern "C"

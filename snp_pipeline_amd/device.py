@@ -667,6 +667,21 @@ class Device(object):
                 out.append((int(counts[i, 0]), int(counts[i, 1]), int(counts[i, 2]), [int(x) for x in offsets[i, :k]], int(status[i])))
         return out
 
+    def merge_vcf_files(self, paths, out_path, own_lines=b"", out_buffer_log2=0):
+        """The multi-sample VCF file of `paths` (column order) written to out_path by the library (snpgpu_merge_vcf_files);
+        own_lines: header lines (bytes, each with its LF) that go in front of #CHROM; out_buffer_log2: 0 for the library's 64 MiB
+        output buffer, or 12 to 32 (the text leaves the device in rounds of sites that fit it).  Returns the statistics as a dict.  Raises
+        IOError for a file that cannot be read or written, SnpGpuError (E_UNSUPPORTED) for a line or a site outside the grammar the merge
+        is pinned on (the message names the file and the byte offset)."""
+        n = len(paths)
+        arr = (C.c_char_p * n)(*[os.fsencode(p) for p in paths])
+        stats = L.MergeStats()
+        rc = self.lib.snpgpu_merge_vcf_files(self.ctx, arr, n, os.fsencode(out_path), own_lines, len(own_lines), int(out_buffer_log2), C.byref(stats))
+        if rc == L.E_IO:
+            raise IOError(self.lib.snpgpu_last_error(self.ctx).decode("utf-8", "replace"))
+        self._check(rc)
+        return {name: getattr(stats, name) for name, _ in L.MergeStats._fields_}
+
     def raise_file_status(self, path, rc, res, check=True, wanted=None):
         """Raise for one file of call_consensus_files the way call_consensus does for its single pileup (wanted: see site_error)."""
         if rc == L.E_IO:

@@ -1177,6 +1177,8 @@ def hot_path_batch(args):
     """Entry point of ``cfsan_snp_pipeline hot_path_batch`` (an extension of this build; see the module docstring)."""
     utils.print_log_header(classpath=True)
     utils.print_arguments(args)
+    if getattr(args, "mergeVcfs", False) and args.noConsensusVcf:
+        utils.global_error("Error: --mergeVcfs merges the consensus.vcf files of the job: it cannot be combined with --noConsensusVcf.")
     comm = _Comm()
     job = _Job(args, comm)
     if not args.forceFlag and job.is_fresh():
@@ -1214,9 +1216,29 @@ def hot_path_batch(args):
         verbose_print("%d of %d samples failed." % (failed, job.n_total))
         if not errs and utils._stop_on_sample_error():       # a peer's sample failed: leave with the code it leaves with
             sys.exit(100)
+    # merge_vcfs may end the process (a sample without its VCF, a line outside the rule, a missing tool): it runs after the group
+    # is closed and this rank's sample errors are reported; every rank's consensus*.vcf files are written (the gather above)
+    if getattr(args, "mergeVcfs", False) and job.rank == 0:
+        _merge_vcfs_stage(job)
 
 
 hot_path_batch.last_stats = None
+
+
+def _merge_vcfs_stage(job):
+    """--mergeVcfs: snpma.vcf and snpma_preserved.vcf in the work directory, as run.py:755-766 asks merge_vcfs for them: from the
+    files the job has just written, for the samples of each flow's filtered list, through the subcommand's own library call."""
+    from . import merge_vcfs as mv
+    t0 = time.perf_counter()
+    routes = {}
+    for listing, name, out in ((job.filtered1, "consensus.vcf", "snpma.vcf"), (job.filtered2, "consensus_preserved.vcf", "snpma_preserved.vcf")):
+        with open(listing, "r") as f:
+            dirs = [d for d in (line.rstrip() for line in f) if d]
+        routes[out] = mv.merge_sample_dirs(dirs, name, os.path.join(job.work_dir, out), force=True, merger=getattr(job.args, "vcfMerger", None))
+    job.timings["merge_vcfs"] = time.perf_counter() - t0
+    if hot_path_batch.last_stats is not None:
+        hot_path_batch.last_stats["merge_vcfs"] = routes
+    verbose_print("#   %-34s %.3f s" % ("merge_vcfs", job.timings["merge_vcfs"]))
 
 
 def _fasta_bytes(name, seq):
@@ -1269,6 +1291,8 @@ def add_arguments(sub):
     sub.add_argument("--collectMetrics", dest="collectMetrics", action="store_true", help="At the end of the job write every sample's metrics file and the merged table (collect_metrics_batch), from the depth sums and gap counts the job holds: no pileup is read a second time")
     sub.add_argument("--collectMetricsExtraParams", dest="collectMetricsExtraParams", type=str, default=None, metavar="STRING", help="Options of collect_metrics, as the configuration file gives them (default: the environment variable CollectMetrics_ExtraParams)")
     sub.add_argument("--mergedMetricsFile", dest="mergedMetricsFile", type=str, default=None, metavar="PATH", help="With --collectMetrics: the merged metrics table (default: metrics.tsv in the work directory)")
+    sub.add_argument("--mergeVcfs", dest="mergeVcfs", action="store_true", help="At the end of the job write snpma.vcf and snpma_preserved.vcf (merge_vcfs) into the work directory, from the consensus.vcf / consensus_preserved.vcf files the job has just written; not with --noConsensusVcf")
+    sub.add_argument("--vcfMerger", dest="vcfMerger", type=str, default=None, choices=("bcftools", "device", "auto"), metavar="MODE", help="With --mergeVcfs: who merges, as merge_vcfs --vcfMerger (default: $SNPGPU_VCF_MERGER, else auto)")
     sub.add_argument("--noConsensusVcf", dest="noConsensusVcf", action="store_true", help="Do not write consensus.vcf / consensus_preserved.vcf")
     sub.add_argument("--residentBytes", dest="residentBytes", type=int, default=0, metavar="INT", help="Device memory for resident pileups (0 = what is free, less 24 GiB); files past it are streamed twice")
     sub.add_argument("--groupBytes", dest="groupBytes", type=int, default=0, metavar="INT", help="Host bytes of per-site results per group of samples (default 1 GiB)")

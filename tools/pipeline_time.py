@@ -40,6 +40,9 @@ def main():
     ap.add_argument("--collect-metrics", type=int, default=0, metavar="RUNS",
                     help="after the timed runs: RUNS runs each of the job alone, of collect_metrics_batch -f after it (every pileup read again "
                          "for its depth sum) and of the job with --collectMetrics; medians, and whether both routes write the same metrics files")
+    ap.add_argument("--merge-vcfs", type=int, default=0, metavar="RUNS",
+                    help="after the timed runs: RUNS runs each of the job alone, of merge_vcfs -f (both flows, device route) after it and of the job "
+                         "with --mergeVcfs; medians, and whether both routes write the same snpma.vcf / snpma_preserved.vcf")
     ap.add_argument("--probe-open", choices=("none", "stat", "serial", "parallel"), default="none",
                     help="before the first run: time stat / open of every pileup (what does the first open after the write cost?)")
     a = ap.parse_args()
@@ -175,6 +178,34 @@ def main():
                                       "median_job_with_option": statistics.median(inside), "median_phase": statistics.median(phase),
                                       "option_cost_over_job": statistics.median(inside) / statistics.median(alone) - 1.0,
                                       "vcf_bytes": vcf_bytes, "counted_by_the_job": counted, "same_metrics_files_and_table": metrics_text() == separate_route}
+        if a.merge_vcfs > 0 and not a.no_vcf:
+            import statistics
+            os.environ["SNPGPU_VCF_MERGER"] = "device"
+            extra = " " + a.extra if a.extra else ""
+            flows = (("consensus.vcf", "snpma.vcf", dirs_file + ".OrigVCF.filtered"), ("consensus_preserved.vcf", "snpma_preserved.vcf", dirs_file + ".PresVCF.filtered"))
+
+            def merged_text():
+                return [[l for l in open(os.path.join(tmpdir, out), "rb").read().split(b"\n") if not l.startswith(b"##snpgpu_merge")] for _, out, _ in flows]
+            from snp_pipeline_amd import merge_vcfs as mv
+            alone, after, inside, phase, library = [], [], [], [], []
+            for _ in range(a.merge_vcfs):
+                alone.append(bench.run_cli(bench.hot_path_line(dirs_file, ref_path, extra), verbose=a.verbose))
+                wall = 0.0
+                for vcf, out, listing in flows:
+                    wall += bench.run_cli("merge_vcfs -f -n %s -o %s --verbose 0 %s" % (vcf, os.path.join(tmpdir, out), listing), verbose=a.verbose)
+                    library.append({k: mv.merge_sample_dirs.last_stats[k] for k in ("sites", "cells", "bytes", "rounds", "seconds_parse", "seconds_merge", "seconds_write")})
+                after.append(wall)
+            separate_route = merged_text()
+            for _ in range(a.merge_vcfs):
+                inside.append(bench.run_cli(bench.hot_path_line(dirs_file, ref_path, extra + " --mergeVcfs"), verbose=a.verbose))
+                phase.append(inside[-1] - hot_path.hot_path_batch.last_stats["seconds"])
+            out["merge_vcfs"] = {"runs": a.merge_vcfs, "job_alone_seconds": alone, "merge_vcfs_after_seconds": after, "job_with_mergeVcfs_seconds": inside,
+                                 "median_job_alone": statistics.median(alone), "median_after": statistics.median(after),
+                                 "median_job_with_option": statistics.median(inside), "median_seconds_after_the_stages": statistics.median(phase),
+                                 "option_cost_over_job": statistics.median(inside) / statistics.median(alone) - 1.0,
+                                 "merged_bytes": [os.path.getsize(os.path.join(tmpdir, o)) for _, o, _ in flows],
+                                 "input_bytes": sum(os.path.getsize(os.path.join(sd, v)) for sd in dirs for v, _, _ in flows),
+                                 "library_clocks_of_the_separate_merges": library, "same_files_by_both_routes": merged_text() == separate_route}
         if a.separate and not a.no_vcf:
             mine = bench.output_digests(tmpdir, dirs)
             for sdir in dirs:
