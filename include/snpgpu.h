@@ -559,6 +559,19 @@ int  snpgpu_rows_copy_dev(snpgpu_ctx *ctx, const void *d_src, uint64_t src_strid
  * out_line_off[n_sites] is a HOST pointer; synchronous. */
 int  snpgpu_siteset_line_offsets(snpgpu_ctx *ctx, const snpgpu_siteset *ss, uint64_t *out_line_off);
 
+/* Which call kernel took how many sites of the most recent call launch on the context (the all-lines entry points: lines).
+ * The call step runs one lane per site over windows of 128, 256 and 512 bytes, each pass over what the one before handed on (a
+ * line whose terminator does not lie inside the window, counted from the 16-byte boundary at or below its first byte; a bases
+ * field over 64 / 128 / 255 bytes; a malformed line; a symbol besides *ACGTN), and one wave per site for the rest — every line
+ * of a sample sequenced deeper than about 240x.  out[0..2]: the three lane passes in that order; out[3]: the wave-per-site
+ * kernel.  Only sites that have a line count: the sum is the number of pileup lines the scan matched to a listed site (a position
+ * that several lines of one file carry counts once per line in the first pass's figure).  For a batch whose lines average more
+ * than 100 bytes the 128-byte pass does not run and out[0] is 0.  A public call over more samples than one launch takes (256, or
+ * 1 GiB of line-offset rows) makes several launches: the figures are those of the last.  The kernels keep the counts in device
+ * memory; they are read back here, so this call waits for the stream and a call launch never does.  Before any launch: all zero. */
+#define SNPGPU_CALL_PASSES 4
+int  snpgpu_call_pass_counts(snpgpu_ctx *ctx, uint64_t out[SNPGPU_CALL_PASSES]);
+
 /* ---- snp_matrix / distance: utils.calculate_sequence_distance (utils.py:1135-1165) over all pairs
  *      (distance.py:93-98) ----------------------------------------------------------------------
  * The samples x sites matrix is packed 4 bits per site, planar per 32-site word:

@@ -8,6 +8,7 @@ LIB_PATH = os.path.join(_HERE, "lib", "libsnpgpu.so")
 
 MAX_SYMS = 8
 SCAN_STATUS_WORDS = 4
+CALL_PASSES = 4                     # SNPGPU_CALL_PASSES: the three lane passes (128, 256, 512 bytes) and the wave-per-site kernel
 
 F_RAWDPTH, F_VARFREQ, F_DEPTH, F_STRDPTH, F_STRBIAS, F_REGION = 1, 2, 4, 8, 16, 32
 SITE_IN_SNPLIST, SITE_EXCLUDED = 1, 2
@@ -153,6 +154,7 @@ SIGNATURES = {
     "snpgpu_symbol_spill_read": (C.c_int, [_P, _P, C.c_uint32, C.POINTER(C.c_uint32)]),
     "snpgpu_symbol_spill_capacity": (C.c_uint32, [_P]),
     "snpgpu_siteset_line_offsets": (C.c_int, [_P, _P, _P]),
+    "snpgpu_call_pass_counts": (C.c_int, [_P, _P]),
     "snpgpu_packed_row_bytes": (C.c_size_t, [C.c_uint32]),
     "snpgpu_pack_matrix_dev": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, C.c_size_t, _P]),
     "snpgpu_distance_packed_dev": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _P]),

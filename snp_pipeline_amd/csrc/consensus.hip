@@ -957,17 +957,22 @@ __global__ __launch_bounds__(kWaves * 64, kWin == 128 ? 3 : 1) void k_call_lanes
 // One workgroup, before the call kernels: is this a batch of deep pileups?  The scan has just counted the lines of every
 // sample; mean line length = bytes / lines.  (Every lane kernel pushes what it cannot do on a list with one atomic per
 // 64 sites — same-address atomics cost ~12 ns each — so a pass that would push nearly everything on is skipped as a whole.)
-__global__ __launch_bounds__(256) void k_call_mode(const SampleDev *samples, uint32_t n, uint32_t *deep) {
-    __shared__ unsigned long long part[2][4];
-    unsigned long long bytes = 0, lines = 0;
-    for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) { bytes += samples[i].nbytes; lines += samples[i].status[1]; }
-    for (int o = 32; o; o >>= 1) { bytes += __shfl_xor(bytes, o); lines += __shfl_xor(lines, o); }
-    if ((threadIdx.x & 63) == 0) { part[0][threadIdx.x >> 6] = bytes; part[1][threadIdx.x >> 6] = lines; }
+// It also leaves, for snpgpu_call_pass_counts, how many of the launch's sites have a line at all: the scan's count of matching
+// lines (status[2]), or every "site" when the sites ARE the lines of a file (all_lines != 0).  deep[1], deep[2]: that count, 64 bits.
+__global__ __launch_bounds__(256) void k_call_mode(const SampleDev *samples, uint32_t n, uint32_t *deep, uint64_t all_lines) {
+    __shared__ unsigned long long part[3][4];
+    unsigned long long bytes = 0, lines = 0, hits = 0;
+    for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) { bytes += samples[i].nbytes; lines += samples[i].status[1]; hits += samples[i].status[2]; }
+    for (int o = 32; o; o >>= 1) { bytes += __shfl_xor(bytes, o); lines += __shfl_xor(lines, o); hits += __shfl_xor(hits, o); }
+    if ((threadIdx.x & 63) == 0) { part[0][threadIdx.x >> 6] = bytes; part[1][threadIdx.x >> 6] = lines; part[2][threadIdx.x >> 6] = hits; }
     __syncthreads();
     if (threadIdx.x == 0) {
         bytes = part[0][0] + part[0][1] + part[0][2] + part[0][3];
         lines = part[1][0] + part[1][1] + part[1][2] + part[1][3];
+        hits = all_lines ? all_lines : part[2][0] + part[2][1] + part[2][2] + part[2][3];
         *deep = bytes > 100ull * lines ? 1u : 0u;
+        deep[1] = (uint32_t)hits;
+        deep[2] = (uint32_t)(hits >> 32);
     }
 }
 
@@ -981,9 +986,10 @@ struct SampleIO { const uint8_t *d_pileup; size_t nbytes; uint64_t *d_status; };
 static int enqueue_call_n(snpgpu_ctx *ctx, uint32_t n_sites, const uint8_t *default_flags, const SampleDev *d_table, uint32_t n,
                           const snpgpu_caller_params *prm, const uint64_t *d_site_line, uint8_t *d_out_base,
                           uint8_t *d_out_filters, snpgpu_site_counts *d_out_counts, uint32_t *d_todo_n, uint64_t *d_todo,
-                          uint64_t *d_todo2, const uint8_t *d_site_flags, uint32_t flags_stride) {
+                          uint64_t *d_todo2, const uint8_t *d_site_flags, uint32_t flags_stride, bool all_lines = false) {
     hipStream_t st = ctx->stream;
     if (!n_sites || !n) return SNPGPU_OK;
+    ctx->call_passes_from = d_todo_n == ctx->d_call_ctl ? 1 : 0;      // (a caller's own counters may be gone when the counts are asked for)
     CallArgs ca;
     ca.samples = d_table;
     ca.n_samples = n;
@@ -1012,10 +1018,11 @@ static int enqueue_call_n(snpgpu_ctx *ctx, uint32_t n_sites, const uint8_t *defa
         // One lane per site, in three window sizes: 128 bytes (64-bit masks: half the registers and a quarter of the LDS of
         // the next one, so twice the waves per SIMD — a 30x line is ~90 bytes) for every site, 256 bytes (bases field <= 128)
         // for what that left, 512 bytes (bases field <= 255) for what THAT left, then one wave per site for the rest.
-        // With per-site records (consensus.vcf) the same chain writes them too.  d_todo_n: three leftover counts.
+        // With per-site records (consensus.vcf) the same chain writes them too.  d_todo_n: three leftover counts, then the
+        // words of k_call_mode (SNPGPU_CALL_CTL_MODE).
         const uint64_t groups = (n_work + 63) / 64;
-        k_call_mode<<<1, 256, 0, st>>>(d_table, n, d_todo_n + 3);
-        ca.deep = d_todo_n + 3;
+        k_call_mode<<<1, 256, 0, st>>>(d_table, n, d_todo_n + SNPGPU_CALL_CTL_MODE, all_lines ? (uint64_t)n_sites : 0ull);
+        ca.deep = d_todo_n + SNPGPU_CALL_CTL_MODE;
         ca.todo = d_todo;
         ca.todo_n = d_todo_n;
         const uint64_t b0 = (groups + 3) / 4, m0 = (uint64_t)ctx->n_cu * 16;
@@ -1053,15 +1060,18 @@ int snpgpu_enqueue_call(snpgpu_ctx *ctx, const snpgpu_siteset *ss, const SampleD
 
 // Every line of one pileup as a "site" (--vcfAllPos, call_consensus.py:148 / pileup.py:418-421): the caller over a list of line
 // offsets — the same chain as over a site list (one lane per line in three window sizes, one wave per line for what is left; up to
-// round 4 every line took a wave of its own: 9.9 ms for 5 M lines).  d_todo / d_todo2: 8 * n_lines bytes each; d_todo_n: four words.
+// round 4 every line took a wave of its own: 9.9 ms for 5 M lines).  d_todo / d_todo2: 8 * n_lines bytes each; d_todo_n:
+// SNPGPU_CALL_CTL_WORDS words.
 int snpgpu_enqueue_call_lines(snpgpu_ctx *ctx, const SampleDev *d_sample, const uint64_t *d_line_off, const uint8_t *d_flags,
                               uint32_t n_lines, const snpgpu_caller_params *prm, uint8_t *d_out_base, uint8_t *d_out_filters,
                               snpgpu_site_counts *d_out_counts, uint32_t *d_todo_n, uint64_t *d_todo, uint64_t *d_todo2) {
     if (!n_lines) return SNPGPU_OK;
     if (d_todo_n && d_todo && d_todo2) {
-        HIP_TRY(ctx, hipMemsetAsync(d_todo_n, 0, 16, ctx->stream));
-        return enqueue_call_n(ctx, n_lines, d_flags, d_sample, 1, prm, d_line_off, d_out_base, d_out_filters, d_out_counts, d_todo_n, d_todo, d_todo2, nullptr, 0);
+        HIP_TRY(ctx, hipMemsetAsync(d_todo_n, 0, 4 * SNPGPU_CALL_CTL_WORDS, ctx->stream));
+        return enqueue_call_n(ctx, n_lines, d_flags, d_sample, 1, prm, d_line_off, d_out_base, d_out_filters, d_out_counts, d_todo_n, d_todo, d_todo2, nullptr, 0, true);
     }
+    ctx->call_passes_from = 2;                                // one wave per line for all of them
+    ctx->call_passes_all = n_lines;
     CallArgs ca;
     ca.samples = d_sample;
     ca.n_samples = 1;
@@ -1095,16 +1105,17 @@ static int enqueue_group(snpgpu_ctx *ctx, const snpgpu_siteset *ss, const Sample
     const size_t ws_bytes = (snpgpu_scan_workspace_bytes(ctx, n) + 255) / 256 * 256;
     const size_t rows_bytes = d_site_line ? 0 : 8ull * n_sites * n;
     const size_t list_bytes = (8ull * n_sites * n + 255) / 256 * 256;
-    const size_t todo_bytes = 2 * list_bytes + 256;                             // leftovers of the two lane kernels + their counts
+    const size_t todo_bytes = 2 * list_bytes;                                   // leftovers of the lane kernels (their counts: snpgpu_call_ctl)
     void *ws = nullptr;
     {
         int rc = snpgpu_scratch(ctx, ws_bytes + rows_bytes + todo_bytes + 256, &ws);
         if (rc) return rc;
     }
     if (!d_site_line) d_site_line = (uint64_t *)((char *)ws + ws_bytes);
-    uint32_t *d_todo_n = (uint32_t *)((char *)ws + ws_bytes + rows_bytes);      // leftovers after the 128-, 256- and 512-byte passes
-    uint64_t *d_todo = (uint64_t *)((char *)ws + ws_bytes + rows_bytes + 256);
-    uint64_t *d_todo2 = (uint64_t *)((char *)ws + ws_bytes + rows_bytes + 256 + list_bytes);
+    uint32_t *d_todo_n = snpgpu_call_ctl(ctx);                                  // leftovers after the 128-, 256- and 512-byte passes: the context's
+    if (!d_todo_n) return SNPGPU_E_HIP;                                         // own words, so that snpgpu_call_pass_counts finds them later
+    uint64_t *d_todo = (uint64_t *)((char *)ws + ws_bytes + rows_bytes);
+    uint64_t *d_todo2 = (uint64_t *)((char *)ws + ws_bytes + rows_bytes + list_bytes);
     std::vector<SampleDev> samples(n);
     for (uint32_t i = 0; i < n; ++i) {
         samples[i] = SampleDev{};
@@ -1112,8 +1123,8 @@ static int enqueue_group(snpgpu_ctx *ctx, const snpgpu_siteset *ss, const Sample
         samples[i].nbytes = io[i].nbytes;
         samples[i].status = io[i].d_status;
     }
-    // the scan's prepare kernel also zeroes the line-offset rows and the two leftover counters of the lane kernels
-    int rc = snpgpu_enqueue_scan(ctx, ss, samples, ws, d_site_line, want_depth, d_todo_n, 3);
+    // the scan's prepare kernel also zeroes the line-offset rows and the leftover counters of the lane kernels
+    int rc = snpgpu_enqueue_scan(ctx, ss, samples, ws, d_site_line, want_depth, d_todo_n, SNPGPU_CALL_PASSES - 1);
     if (rc) return rc;
     return snpgpu_enqueue_call(ctx, ss, (const SampleDev *)ws, n, prm, d_site_line, d_out_base, d_out_filters, d_out_counts,
                                d_todo_n, d_todo, d_todo2, d_site_flags, flags_stride);
@@ -1127,7 +1138,42 @@ static int enqueue_sample(snpgpu_ctx *ctx, const snpgpu_siteset *ss, const uint8
     return enqueue_group(ctx, ss, &io, 1, prm, d_out_base, d_out_filters, d_out_counts, ss->site_line, want_depth);
 }
 
+// The context's own control words of the call chain (allocated once): see SNPGPU_CALL_CTL_WORDS.
+uint32_t *snpgpu_call_ctl(snpgpu_ctx *ctx) {
+    if (!ctx->d_call_ctl) {
+        void *d = nullptr;
+        if (hipMalloc(&d, 256) != hipSuccess) { snpgpu_set_error(ctx, SNPGPU_E_HIP, "hipMalloc of the call chain's counters failed"); return nullptr; }
+        if (hipMemsetAsync(d, 0, 256, ctx->stream) != hipSuccess) { (void)hipFree(d); snpgpu_set_error(ctx, SNPGPU_E_HIP, "hipMemsetAsync failed"); return nullptr; }
+        ctx->d_call_ctl = (uint32_t *)d;
+    }
+    return ctx->d_call_ctl;
+}
+
 extern "C" {
+
+// Which pass took how many of the last call launch's sites: the leftover counts of the chain, read back now (the one
+// synchronisation of this feature is here, not in the launch).
+int snpgpu_call_pass_counts(snpgpu_ctx *ctx, uint64_t out[SNPGPU_CALL_PASSES]) {
+    if (!ctx || !out) return snpgpu_set_error(ctx, SNPGPU_E_ARG, "null argument");
+    for (int k = 0; k < SNPGPU_CALL_PASSES; ++k) out[k] = 0;
+    if (ctx->call_passes_from == 2) { out[SNPGPU_CALL_PASSES - 1] = ctx->call_passes_all; return SNPGPU_OK; }
+    if (ctx->call_passes_from != 1 || !ctx->d_call_ctl) return SNPGPU_OK;      // no call launch yet
+    HIP_TRY(ctx, snpgpu_enter(ctx));
+    uint32_t h[SNPGPU_CALL_CTL_WORDS];
+    HIP_TRY(ctx, hipMemcpyAsync(h, ctx->d_call_ctl, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    // a pass took what the pass before left minus what it left itself; the first pass that ran (the 256-byte one for a batch
+    // of deep pileups, see k_call_mode) started from every site that has a line
+    const uint64_t with_line = (uint64_t)h[SNPGPU_CALL_CTL_MODE + 1] | ((uint64_t)h[SNPGPU_CALL_CTL_MODE + 2] << 32);
+    const int first = h[SNPGPU_CALL_CTL_MODE] ? 1 : 0;
+    uint64_t before = with_line;
+    for (int k = first; k < SNPGPU_CALL_PASSES - 1; ++k) {
+        out[k] = before > h[k] ? before - h[k] : 0;
+        before = h[k];
+    }
+    out[SNPGPU_CALL_PASSES - 1] = before;
+    return SNPGPU_OK;
+}
 
 int snpgpu_call_consensus_dev(snpgpu_ctx *ctx, const snpgpu_siteset *ss, const void *d_pileup, size_t nbytes,
                               const snpgpu_caller_params *params, uint8_t *d_out_base, uint8_t *d_out_filters,

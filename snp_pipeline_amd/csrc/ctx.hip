@@ -106,6 +106,7 @@ int snpgpu_ctx_create(int device, snpgpu_ctx **out) {
     hipEventCreate(&ctx->ev_stop);
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) == hipSuccess) ctx->n_cu = prop.multiProcessorCount;
+    (void)snpgpu_call_ctl(ctx);                                 // (here, so that no call launch ever allocates; a failure shows at the first launch)
     *out = ctx;
     return SNPGPU_OK;
 }
@@ -118,6 +119,7 @@ void snpgpu_ctx_destroy(snpgpu_ctx *ctx) {
     snpgpu_stream_pool_destroy(ctx);
     if (ctx->scratch) hipFree(ctx->scratch);
     if (ctx->d_spill) hipFree(ctx->d_spill);
+    if (ctx->d_call_ctl) hipFree(ctx->d_call_ctl);
     for (auto &t : ctx->timed) { hipEventDestroy(t.a); hipEventDestroy(t.b); }
     for (auto e : ctx->event_pool) hipEventDestroy(e);
     if (ctx->ev_start) hipEventDestroy(ctx->ev_start);

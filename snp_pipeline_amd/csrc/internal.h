@@ -30,6 +30,11 @@ struct snpgpu_ctx {
     // positions with more than SNPGPU_MAX_SYMS symbols: [SNPGPU_SPILL_CAP] records + one counter word (allocated on first use)
     snpgpu_symbol_spill *d_spill = nullptr;
     uint32_t *d_spill_n = nullptr;
+    // the call chain's control words (consensus.hip, snpgpu_call_ctl) and where snpgpu_call_pass_counts finds the last launch's counts:
+    // 0 nowhere (no launch yet, or a caller's own words), 1 in d_call_ctl, 2 every one of call_passes_all lines took a wave
+    uint32_t *d_call_ctl = nullptr;
+    int call_passes_from = 0;
+    uint64_t call_passes_all = 0;
     uint32_t spill_cap = 0, spill_want = SNPGPU_SPILL_CAP;     // records the arena holds / should hold at the next call (it grows when a call ran out)
     // optional per-kernel timing (bench): event pairs recorded around selected launches
     bool time_kernels = false;
@@ -181,7 +186,12 @@ size_t snpgpu_merge_rows_scan_words(uint32_t n_sites);
 int snpgpu_enqueue_merge_rows(snpgpu_ctx *ctx, int write, const snpgpu_merge_cell *d_cells, const uint32_t *d_table, uint32_t n_col, const uint64_t *d_site_keys,
                               uint32_t n_sites, uint32_t site_lo, uint32_t site_hi, uint64_t out_base, const uint8_t *d_names, const uint32_t *d_name_off, const uint8_t *d_filt, const uint32_t *d_filt_off,
                               uint64_t *d_row_len, uint64_t *d_row_end, uint64_t *d_scan_ws, uint8_t *d_out, uint64_t *d_ctl);
-// the call kernels over a scanned batch (consensus.hip); d_todo_n: 4 words (3 zeroed), d_todo / d_todo2: n * n_sites entries each;
+// the call kernels over a scanned batch (consensus.hip); d_todo_n: SNPGPU_CALL_CTL_WORDS words — what each of the three lane passes
+// left (zeroed by the scan's prepare kernel), then what k_call_mode writes: the deep flag and the 64-bit count of sites that have a
+// line; snpgpu_call_ctl(): the context's own such words; d_todo / d_todo2: n * n_sites entries each;
+#define SNPGPU_CALL_CTL_MODE (SNPGPU_CALL_PASSES - 1)
+#define SNPGPU_CALL_CTL_WORDS (SNPGPU_CALL_CTL_MODE + 3)
+uint32_t *snpgpu_call_ctl(snpgpu_ctx *ctx);
 // lines_out.hip: the per-line records of --vcfAllPos packed into 24 bytes where they fit, the others gathered as they are
 size_t snpgpu_compact_lines_workspace_words(uint64_t n_lines);
 int snpgpu_enqueue_compact_lines(snpgpu_ctx *ctx, const snpgpu_site_counts *d_counts, const uint8_t *d_flags, uint64_t n_lines, snpgpu_line_record *d_recs,

@@ -425,7 +425,6 @@ int run_stream(snpgpu_ctx *ctx, const snpgpu_siteset *ss, std::vector<Source> &s
         const size_t o_tab = o; o += table_bytes * p->slot.size();
         const size_t o_tot = o; o += up(snpgpu_scan_totals_bytes(ctx), 256);
         const size_t o_line = o; o += list_bytes;
-        const size_t o_todon = o; o += 256;
         const size_t o_todo = o; o += list_bytes;
         const size_t o_todo2 = o; o += list_bytes;
         const size_t o_base = o; o += up(n_sites, 256);
@@ -438,7 +437,8 @@ int run_stream(snpgpu_ctx *ctx, const snpgpu_siteset *ss, std::vector<Source> &s
         if (rc) { close_all(); return rc; }
         char *b = (char *)ws;
         ds.tables = (SampleDev *)(b + o_tab); ds.table_stride = table_bytes;
-        ds.totals = (uint64_t *)(b + o_tot); ds.site_line = (uint64_t *)(b + o_line); ds.todo_n = (uint32_t *)(b + o_todon);
+        ds.totals = (uint64_t *)(b + o_tot); ds.site_line = (uint64_t *)(b + o_line); ds.todo_n = snpgpu_call_ctl(ctx);
+        if (!ds.todo_n) { close_all(); return SNPGPU_E_HIP; }
         ds.todo = (uint64_t *)(b + o_todo); ds.todo2 = (uint64_t *)(b + o_todo2); ds.base = (uint8_t *)(b + o_base);
         ds.filters = (uint8_t *)(b + o_filt); ds.status = (uint64_t *)(b + o_stat);
         ds.counts = out.counts ? (snpgpu_site_counts *)(b + o_cnt) : nullptr;
@@ -538,7 +538,7 @@ int run_stream(snpgpu_ctx *ctx, const snpgpu_siteset *ss, std::vector<Source> &s
                 cur_waves = h_tab[2 * nc + 1].wave0;
                 tiles_done = 0;
                 ST_TRY(hipMemcpyAsync(d_tab, h_tab, (size_t)(nc + 1) * 2 * sizeof(SampleDev), hipMemcpyHostToDevice, st));
-                rc = snpgpu_scan_begin(ctx, ss, d_tab + 2 * nc, 1, ds.site_line, ds.todo_n, 3);
+                rc = snpgpu_scan_begin(ctx, ss, d_tab + 2 * nc, 1, ds.site_line, ds.todo_n, SNPGPU_CALL_PASSES - 1);
                 if (rc) goto done;
             }
             {
@@ -836,7 +836,7 @@ int all_lines_pass(snpgpu_ctx *ctx, const snpgpu_siteset *ss, const char *path, 
     if (rc == SNPGPU_OK)
         rc = snpgpu_enqueue_call_lines(ctx, (const SampleDev *)(b + o_samp), (const uint64_t *)(b + o_off), (const uint8_t *)(b + o_flag),
                                        n_lines, params, (uint8_t *)(b + o_base), (uint8_t *)(b + o_filt), (snpgpu_site_counts *)(b + o_cnt),
-                                       (uint32_t *)(b + o_todo), (uint64_t *)(b + o_todo + 256), (uint64_t *)(b + o_todo + 256 + up(8ull * n_lines, 256)));
+                                       snpgpu_call_ctl(ctx), (uint64_t *)(b + o_todo + 256), (uint64_t *)(b + o_todo + 256 + up(8ull * n_lines, 256)));
     if (rc) return rc;
     al.d_off = (uint64_t *)(b + o_off);
     al.d_flags = (uint8_t *)(b + o_flag);

@@ -729,6 +729,18 @@ class Device(object):
         self._check(self.lib.snpgpu_siteset_line_offsets(self.ctx, siteset.handle, _ptr(out)))
         return out
 
+    CALL_PASS_NAMES = ("lanes128", "lanes256", "lanes512", "wave")
+
+    def call_pass_counts(self):
+        """How many sites (lines, for the all-lines calls) each call kernel took in the most recent call launch on this
+        device: a dict over CALL_PASS_NAMES — the one-lane-per-site passes by window size, then the wave-per-site kernel,
+        which gets what no window holds (lines over 512 bytes — every line of a sample deeper than about 240x —, malformed
+        lines, unusual symbols).  Only sites that have a line
+        count.  Waits for the stream; the call launches themselves never do."""
+        out = np.zeros(L.CALL_PASSES, dtype=np.uint64)
+        self._check(self.lib.snpgpu_call_pass_counts(self.ctx, _ptr(out)))
+        return dict(zip(self.CALL_PASS_NAMES, (int(v) for v in out)))
+
     def call_consensus_dev(self, siteset, d_pileup_ptr, nbytes, params, d_bases, d_filters, d_status, d_counts=None,
                            want_depth_sum=False):
         """All arguments are device pointers (ints); asynchronous on the context's stream."""

@@ -148,6 +148,7 @@ class _Job(object):
         self.rank, self.world = comm.rank, comm.world
         self.t_start = time.perf_counter()
         self.timings = {}
+        self.call_passes = {}                          # lines each call kernel took, summed over the groups (Device.call_pass_counts)
         self.deferred = None                           # first exception of a guarded block (see guard)
         self.dev = self.store = None
 
@@ -814,6 +815,7 @@ def _consensus_group(job, fl, g0, part, hs, vcf_again, vcf_later):
     d_base, d_filt, d_filt2, d_line, d_status, d_counts = fl.d_base, fl.d_filt, fl.d_filt2, fl.d_line, fl.d_status, fl.d_counts
     t_g = time.perf_counter()
     g = len(part)
+    one_launch = False                                        # the whole group in ONE call launch: then the launch's pass counts are the group's
     resident = [(k, s) + store.get(s.store_index) for k, s in enumerate(part)]
     res_idx = [k for k, s, ptr, _ in resident if ptr]
     if res_idx and S:
@@ -822,6 +824,7 @@ def _consensus_group(job, fl, g0, part, hs, vcf_again, vcf_later):
         ptrs = [ptr for _, _, ptr, _ in resident if ptr]
         sizes = [n for _, _, ptr, n in resident if ptr]
         if len(res_idx) == g:
+            one_launch = g <= 256 and 8 * S * g <= (1 << 30)  # (what snpgpu_call_consensus_many_dev puts into one launch)
             dev.call_consensus_many_dev(ss, ptrs, sizes, prm, d_base.data_ptr(), d_filt.data_ptr(), d_status.data_ptr(),
                                         d_counts=d_counts.data_ptr() if want_vcf else 0, d_line_off=d_line.data_ptr(),
                                         want_depth_sum=fl.want_depth)
@@ -865,6 +868,7 @@ def _consensus_group(job, fl, g0, part, hs, vcf_again, vcf_later):
                 except (utf8_names.Refused, UnicodeDecodeError, OSError):
                     pass                                      # (its scan error stands)
             if copies:
+                one_launch = False
                 results, rcs, st = dev.call_consensus_files(ss, [c for _, _, c in copies], prm, want_counts=want_vcf, want_line_offsets=True,
                                                             want_depth_sum=fl.want_depth)
                 job.h2d_extra += int(st.bytes)
@@ -935,6 +939,18 @@ def _consensus_group(job, fl, g0, part, hs, vcf_again, vcf_later):
                     vcf_again.append(s)
                     vcf_later.add(s.index)
     torch.cuda.current_stream().synchronize()
+    if S and one_launch and not rest:
+        # which call kernel took how many of the group's lines (the device is idle here: the read-back costs one small copy).  The
+        # library keeps the figures of its last launch only, so a group that took several launches (samples streamed again, escaped
+        # copies, scattered calls) is counted under "groups_not_counted" instead.  Lines under "wave" are off the fast path: over
+        # 512 bytes, or malformed.
+        passes = dev.call_pass_counts()
+        for k, v in passes.items():
+            job.call_passes[k] = job.call_passes.get(k, 0) + v
+        if args.verbose >= 2:
+            verbose_print("#   call passes, samples %d-%d: %s" % (g0, g0 + g - 1, "  ".join("%s %d" % (k, passes[k]) for k in devmod.Device.CALL_PASS_NAMES)))
+    elif S:
+        job.call_passes["groups_not_counted"] = job.call_passes.get("groups_not_counted", 0) + 1
     job.lap("3b   of which: results to the host" if args.verbose >= 2 else "3ab  of which: device work + results to the host", t_g)
     return chk, group_spill
 
@@ -1169,12 +1185,18 @@ def _job_stats(job):
             "ingest": {"seconds": st.seconds, "allocating": st.seconds_allocating, "waiting_for_readers": st.seconds_waiting_for_readers,
                        "waiting_for_device": st.seconds_waiting_for_device, "reader_seconds_reading": st.reader_seconds_reading,
                        "reader_seconds_waiting": st.reader_seconds_waiting, "preparing": st.seconds_preparing},
-            "phases": job.timings, "sites": fl.S1, "sites_preserved": fl.S2, "samples": job.hi - job.lo,
+            "phases": job.timings, "call_passes": dict(job.call_passes), "sites": fl.S1, "sites_preserved": fl.S2, "samples": job.hi - job.lo,
             "readers": int(st.n_readers), "usable_cores": job.cpu["usable_cpus"], "local_world": job.cpu["local_ranks"], "cpu_budget": job.cpu}
 
 
 def hot_path_batch(args):
-    """Entry point of ``cfsan_snp_pipeline hot_path_batch`` (an extension of this build; see the module docstring)."""
+    """Entry point of ``cfsan_snp_pipeline hot_path_batch`` (an extension of this build; see the module docstring).
+
+    ``hot_path_batch.last_stats`` holds this rank's figures of the last run (``_job_stats``).  Its key ``call_passes`` is a dict
+    over ``Device.CALL_PASS_NAMES`` (lanes128, lanes256, lanes512, wave): how many pileup lines of the job's consensus step each
+    call kernel took, summed over the groups of samples whose call was one launch; ``groups_not_counted``, when present, is the
+    number of groups that took several launches and are left out.  Lines under ``wave`` left the one-lane-per-site path: they
+    are longer than 512 bytes (a sample deeper than about 240x) or malformed.  ``-v 2`` logs the same figures per group."""
     utils.print_log_header(classpath=True)
     utils.print_arguments(args)
     if getattr(args, "mergeVcfs", False) and args.noConsensusVcf:
