@@ -476,6 +476,27 @@ template <int N> __device__ __forceinline__ BM<N> m_clear_lowest(BM<N> a) {
     return a;
 }
 
+// Thirty-two bytes as seven plane words (p[b]: bit b of every byte, one mask bit per byte; bit 7 is clear on ASCII input) and the
+// byte classes as boolean functions of them (v_bitop3).  tests/test_call_counts_cpu.py states the same functions over every byte.
+struct Planes {
+    uint32_t p0, p1, p2, p3, p4, p5, p6;
+    __device__ __forceinline__ uint32_t punct() const { return ~p6 & p5 & ~p4; }                         // 0x20-0x2F
+    __device__ __forceinline__ uint32_t caret() const { return p6 & ~p5 & p4 & p3 & p2 & p1 & ~p0; }     // '^' 0x5E
+    __device__ __forceinline__ uint32_t sign() const { return punct() & p3 & p0 & (p2 ^ p1); }           // '+' 0x2B, '-' 0x2D
+    __device__ __forceinline__ uint32_t dollar() const { return punct() & ~p3 & p2 & ~p1 & ~p0; }        // '$' 0x24
+    __device__ __forceinline__ uint32_t digit() const { return ~p6 & p5 & p4 & ~(p3 & (p2 | p1)); }      // 0x30-0x39
+    // The read symbols under a mask `keep`: A C G N T = 0x41 0x43 0x47 0x4E 0x54 by their low five bits (00001 00011 00111 01110 10100;
+    // upper() / lower() tell the strand), '*' 0x2A, ',' 0x2C, '.' 0x2E.  Shared terms are factored by hand: the compiler does not find them.
+    struct Symbols { uint32_t a5, c5, g5, n5, t5, star, dot, comma; };
+    __device__ __forceinline__ Symbols symbols(uint32_t keep) const {
+        const uint32_t lo3 = ~p4 & ~p3, ac = lo3 & ~p2 & p0;
+        const uint32_t kp = keep & ~p6 & p5 & ~p4 & p3 & ~p0;                                          // 0x28-0x2E, even
+        return Symbols{ac & ~p1, ac & p1, lo3 & p2 & p1 & p0, ~p4 & p3 & p2 & p1 & ~p0, p4 & ~p3 & p2 & ~p1 & ~p0, kp & ~p2 & p1, kp & p2 & p1, kp & p2 & ~p1};
+    }
+    __device__ __forceinline__ uint32_t upper() const { return p6 & ~p5; }                               // 0x40-0x5F
+    __device__ __forceinline__ uint32_t lower() const { return p6 & p5; }                                // 0x60-0x7F
+};
+
 // ------------------------------------------------------------------------------------------------
 //                         K2 fast path: one LANE per site, 64 sites per wave
 // ------------------------------------------------------------------------------------------------
@@ -705,10 +726,10 @@ __global__ __launch_bounds__(kWaves * 64, kWin == 128 ? 3 : 1) void k_call_lanes
             }
         }
         // ---- bases + qualities (pileup.py:237-274) -------------------------------------------------------------------
-        // The bases field (<= kMaxField bytes here) is handled as per-lane 64*kWords-bit masks in field coordinates: byte classes by
-        // SWAR compares + dot4, caret pairs by the carry chains of two 128-bit adds (as k_call_sites does on ballots),
-        // indel markers by a short serial walk over the '+'/'-' bytes (none on most lines), and only the surviving bytes
-        // are then looked at one by one for the counts.
+        // The bases field (<= kMaxField bytes here) is handled as per-lane 64*kWords-bit masks in field coordinates: seven bit planes
+        // of its bytes (and + dot4), byte classes by boolean algebra on the planes, caret pairs by the carry chains of two 128-bit adds (as k_call_sites does on ballots),
+        // indel markers by a short serial walk over the '+'/'-' bytes (none on most lines); the counts are popcounts of the symbols'
+        // masks from the same planes, and only when some quality fails or is missing are the surviving bytes looked at one by one.
         uint64_t cnt_f = 0, cnt_r = 0;                         // byte lanes: '*' A C G N T, lane 6: '.' (fwd) / ',' (rev)
         uint32_t good = 0;
         bool parse = has && !punt && raw_depth != 0 && nf >= 6;
@@ -720,31 +741,50 @@ __global__ __launch_bounds__(kWaves * 64, kWin == 128 ? 3 : 1) void k_call_lanes
             maxL = __builtin_amdgcn_readfirstlane(maxL);
             const uint32_t nd = (maxL + 3) >> 2;                 // dwords of the longest field in the wave
             const M V = m_below<kWords>(L0);
-            // -- byte classes: NOT '^', NOT sign, NOT '$' (a cleared bit = match), digits
-            uint32_t nC[2 * kWords], nP[2 * kWords], nS[2 * kWords], dG[2 * kWords];
+            // -- bit planes of the field: pl[b] holds bit b of every byte, one mask bit per byte, in field coordinates (the layout
+            //    of BM<kWords>).  Two dwords give one mask byte per plane: the plane's bit of each byte, two dot4 that gather the
+            //    eight of them, one shift into place.  Bit 7 is clear (the scan rejects bytes >= 0x80): seven planes are the field.
+            uint32_t pl[7][2 * kWords];
 #pragma unroll
-            for (int q = 0; q < 2 * kWords; ++q) { nC[q] = 0; nP[q] = 0; nS[q] = 0; dG[q] = 0; }
+            for (int b = 0; b < 7; ++b)
+#pragma unroll
+                for (int q = 0; q < 2 * kWords; ++q) pl[b][q] = 0;
             {
                 const uint32_t sh = bs & 3u;
                 uint32_t lo = slot[bs >> 2];
 #pragma unroll
-                for (uint32_t j = 0; j < 16u * kWords; ++j) {
-                    if (j >= nd) break;
-                    const uint32_t hi = slot[(bs >> 2) + j + 1];
-                    const uint32_t w = __builtin_amdgcn_alignbyte(hi, lo, sh);
-                    lo = hi;
-                    const uint32_t ne_c = ((w ^ 0x5E5E5E5Eu) + 0x7F7F7F7Fu) & 0x80808080u;
-                    const uint32_t ne_p = ((w ^ 0x2B2B2B2Bu) + 0x7F7F7F7Fu) & ((w ^ 0x2D2D2D2Du) + 0x7F7F7F7Fu) & 0x80808080u;
-                    const uint32_t ne_s = ((w ^ 0x24242424u) + 0x7F7F7F7Fu) & 0x80808080u;
-                    const uint32_t dg = ((w + 0x50505050u) ^ (w + 0x46464646u)) & 0x80808080u;     // '0'..'9'
-                    const uint32_t pos = (4 * j) & 31u;
-                    nC[j >> 3] |= (__builtin_amdgcn_udot4(ne_c, 0x08040201u, 0u, false) >> 7) << pos;
-                    nP[j >> 3] |= (__builtin_amdgcn_udot4(ne_p, 0x08040201u, 0u, false) >> 7) << pos;
-                    nS[j >> 3] |= (__builtin_amdgcn_udot4(ne_s, 0x08040201u, 0u, false) >> 7) << pos;
-                    dG[j >> 3] |= (__builtin_amdgcn_udot4(dg, 0x08040201u, 0u, false) >> 7) << pos;
+                for (uint32_t jp = 0; jp < 8u * kWords; ++jp) {
+                    if (2 * jp >= nd) break;
+                    const uint32_t h0 = slot[(bs >> 2) + 2 * jp + 1];
+                    const uint32_t w0 = __builtin_amdgcn_alignbyte(h0, lo, sh);
+                    uint32_t w1 = 0;
+                    lo = h0;
+                    if (2 * jp + 1 < nd) {                        // (wave-uniform: nothing is read past the longest field's last dword + 1)
+                        const uint32_t h1 = slot[(bs >> 2) + 2 * jp + 2];
+                        w1 = __builtin_amdgcn_alignbyte(h1, h0, sh);
+                        lo = h1;
+                    }
+                    const uint32_t pos = (8 * jp) & 31u;
+#pragma unroll
+                    for (uint32_t b = 0; b < 7; ++b) {
+                        const uint32_t mb = 0x01010101u << b;
+                        const uint32_t v = __builtin_amdgcn_udot4(w1 & mb, 0x80402010u, __builtin_amdgcn_udot4(w0 & mb, 0x08040201u, 0u, false), false);   // eight plane bits << b
+                        pl[b][jp >> 2] |= pos >= b ? v << (pos - b) : v >> (b - pos);
+                    }
                 }
             }
-            const M C = m_andn(V, m_make<kWords>(nC)), PM = m_andn(V, m_make<kWords>(nP)), DL = m_andn(V, m_make<kWords>(nS)), D = m_and(V, m_make<kWords>(dG));
+            // -- byte classes from the planes, 32 bytes per step of plain boolean algebra (struct Planes): '^', sign, '$', digits
+            auto planes_of = [&](int q) -> Planes { return Planes{pl[0][q], pl[1][q], pl[2][q], pl[3][q], pl[4][q], pl[5][q], pl[6][q]}; };
+            uint32_t mC[2 * kWords], mP[2 * kWords], mS[2 * kWords], dG[2 * kWords];
+#pragma unroll
+            for (int q = 0; q < 2 * kWords; ++q) {
+                const Planes p = planes_of(q);
+                mC[q] = p.caret();
+                mP[q] = p.sign();
+                mS[q] = p.dollar();
+                dG[q] = p.digit();
+            }
+            const M C = m_and(V, m_make<kWords>(mC)), PM = m_and(V, m_make<kWords>(mP)), DL = m_and(V, m_make<kWords>(mS)), D = m_and(V, m_make<kWords>(dG));
             // -- '^' + next byte (pileup.py:312): openers are the carets at even distance from the start of their run
             const M EVEN = m_fill<kWords>(0x5555555555555555ull), ZERO = m_fill<kWords>(0ull);
             const M S0 = m_andn(C, m_shl1(C));
@@ -819,15 +859,45 @@ __global__ __launch_bounds__(kWaves * 64, kWin == 128 ? 3 : 1) void k_call_lanes
                 }
             }
             const bool pair_any = __ballot(parse && !allq) != 0;
-            {
+            if (!pair_any) {
+                // Every kept byte of every lane is a good base: the counts are popcounts of the classes' equality masks under K.
+                // '*' 0x2A, ',' 0x2C, '.' 0x2E; A C G N T = 0x41 0x43 0x47 0x4E 0x54, lower case (the reverse strand) = | 0x20.
+                // A kept byte of no class sends the site on, as byte 15 of the histogram does on the paired path.
+#if !(defined(SNPGPU_TUNING) && defined(CALL_EXP) && CALL_EXP >= 1)      // (experiment builds: what the phases of the lane kernel cost; the results are wrong)
+                uint32_t nf_[7] = {0, 0, 0, 0, 0, 0, 0}, nr_[7] = {0, 0, 0, 0, 0, 0, 0}, other = 0;     // '*' A C G N T, [6]: '.' / ','
+#pragma unroll
+                for (int q = 0; q < 2 * kWords; ++q) {
+                    const Planes p = planes_of(q);
+                    const uint32_t kq = (uint32_t)(K.w[q >> 1] >> (32 * (q & 1)));
+                    const Planes::Symbols e = p.symbols(kq);
+                    const uint32_t eA = e.a5, eC = e.c5, eG = e.g5, eN = e.n5, eT = e.t5, eS = e.star, eD = e.dot, eM = e.comma;
+                    const uint32_t ku = kq & p.upper(), kl = kq & p.lower();
+                    nf_[0] += __popc(eS); nf_[6] += __popc(eD); nr_[6] += __popc(eM);
+                    nf_[1] += __popc(ku & eA); nf_[2] += __popc(ku & eC); nf_[3] += __popc(ku & eG); nf_[4] += __popc(ku & eN); nf_[5] += __popc(ku & eT);
+                    nr_[1] += __popc(kl & eA); nr_[2] += __popc(kl & eC); nr_[3] += __popc(kl & eG); nr_[4] += __popc(kl & eN); nr_[5] += __popc(kl & eT);
+                    other |= kq & ~((p.p6 & (eA | eC | eG | eN | eT)) | eS | eD | eM);
+                }
+                punt = punt || other != 0u;
+                // (a lane's counts sum to at most its field's length, <= 255: a byte lane cannot overflow)
+                const uint32_t f_lo = nf_[0] | (nf_[1] << 8) | (nf_[2] << 16) | (nf_[3] << 24), f_hi = nf_[4] | (nf_[5] << 8) | (nf_[6] << 16);
+                const uint32_t r_lo = nr_[0] | (nr_[1] << 8) | (nr_[2] << 16) | (nr_[3] << 24), r_hi = nr_[4] | (nr_[5] << 8) | (nr_[6] << 16);
+                cnt_f = (uint64_t)f_lo | ((uint64_t)f_hi << 32);
+                cnt_r = (uint64_t)r_lo | ((uint64_t)r_hi << 32);
+                // good bases = all that were counted (pileup.py:252)
+                good = __builtin_amdgcn_udot4(f_lo, 0x01010101u, __builtin_amdgcn_udot4(f_hi, 0x01010101u, 0u, false), false) +
+                       __builtin_amdgcn_udot4(r_lo, 0x01010101u, __builtin_amdgcn_udot4(r_hi, 0x01010101u, 0u, false), false);
+#endif
+            } else {
+                // Some lane of the wave has a failing or a missing quality: the kept bytes are walked one by one, each paired with
+                // its quality (zip truncation, pileup.py:248-250).
                 const uint32_t sh = bs & 3u;
                 uint32_t lo = slot[bs >> 2];
                 uint32_t kept = 0;
-                uint32_t qd = qs >> 2, qw = 0, qw_next = 0;
-                if (pair_any) { qw = slot[qd & (LANES_WIN / 4 - 1u)]; qw_next = slot[(qd + 1) & (LANES_WIN / 4 - 1u)]; }
-                // The counts live in LDS while the bases are walked: byte `cl` of the lane's sixteen takes one ds_add per read base
-                // (a lane only ever touches its own sixteen bytes; <= 255 bases per field: no carry between them) instead of two
-                // 64-bit shift-and-add pairs in registers — the loop is the kernel's largest block of vector instructions.
+                uint32_t qd = qs >> 2;
+                uint32_t qw = slot[qd & (LANES_WIN / 4 - 1u)], qw_next = slot[(qd + 1) & (LANES_WIN / 4 - 1u)];
+                // This is the rare path (never taken at -q 0 on well-formed lines), kept simple rather than fast.  The counts live
+                // in LDS while the bases are walked: byte `cl` of the lane's sixteen takes one ds_add per read base (a lane only
+                // ever touches its own sixteen bytes; <= 255 bases per field: no carry between them).
                 uint32_t *my_hist = (uint32_t *)&S.hist[wave][lane];
                 S.hist[wave][lane] = make_uint4(0u, 0u, 0u, 0u);
 #if defined(SNPGPU_TUNING) && defined(CALL_EXP) && CALL_EXP >= 1      // (experiment builds: what the phases of the lane kernel cost; the results are wrong)
@@ -845,19 +915,16 @@ __global__ __launch_bounds__(kWaves * 64, kWin == 128 ? 3 : 1) void k_call_lanes
 #pragma unroll
                     for (uint32_t k = 0; k < 4; ++k) {
                         const bool emit = (k4 >> k) & 1u;
-                        bool goodb = emit;
-                        if (pair_any) {
-                            const uint32_t qi = qs + kept;
-                            if (__ballot((qi >> 2) != qd)) {
-                                const bool adv = (qi >> 2) != qd;
-                                qw = adv ? qw_next : qw;
-                                qd += adv ? 1u : 0u;
-                                qw_next = slot[(qd + 1) & (LANES_WIN / 4 - 1u)];
-                            }
-                            const uint32_t qv = (qw >> (8 * (qi & 3u))) & 0xFFu;
-                            goodb = emit && kept < qlen && (int)qv >= thr;
-                            kept += emit ? 1u : 0u;
+                        const uint32_t qi = qs + kept;
+                        if (__ballot((qi >> 2) != qd)) {
+                            const bool adv = (qi >> 2) != qd;
+                            qw = adv ? qw_next : qw;
+                            qd += adv ? 1u : 0u;
+                            qw_next = slot[(qd + 1) & (LANES_WIN / 4 - 1u)];
                         }
+                        const uint32_t qv = (qw >> (8 * (qi & 3u))) & 0xFFu;
+                        const bool goodb = emit && kept < qlen && (int)qv >= thr;
+                        kept += emit ? 1u : 0u;
                         const uint32_t cl = cl4[k];
                         // (cl 0xFF — any other symbol — lands in byte 15, which no class uses: such a site is handed on below)
                         (void)__hip_atomic_fetch_add(my_hist + ((cl >> 2) & 3u), (goodb ? 1u : 0u) << (8u * (cl & 3u)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
