@@ -260,6 +260,18 @@ int  snpgpu_call_consensus_files(snpgpu_ctx *ctx, const snpgpu_siteset *ss, cons
                                  uint8_t *out_base, uint8_t *out_filters,
                                  snpgpu_site_counts *out_counts, uint64_t *out_line_off, uint64_t *out_status,
                                  int32_t *out_rc, const snpgpu_stream_opts *opts, snpgpu_stream_stats *stats);
+/* The same stream with its rows left ON THE DEVICE: d_out_base / d_out_filters / d_out_counts (nullable) / d_out_line_off (nullable)
+ * are [n_files][n_sites] row-major DEVICE arrays, the layout snpgpu_call_consensus_many_dev writes — the kernels of file f write
+ * row f, so a group of pileups that was never resident is ready for snpgpu_region_flow_dev / snpgpu_group_check_dev when the
+ * call returns (synchronous, like the host form).  out_status [n_files][4] and out_rc [n_files] (nullable) stay HOST arrays: the
+ * caller decides per file without reading device memory.  The rows of a file with out_rc == SNPGPU_E_IO are written as '-' / 0 /
+ * no line / zeroed records.  The spill records of all files of the call form one arena (snpgpu_symbol_spill_read serves every
+ * row).  Every other argument as snpgpu_call_consensus_files.  (Additive in ABI 7.) */
+int  snpgpu_call_consensus_files_dev(snpgpu_ctx *ctx, const snpgpu_siteset *ss, const char *const *paths, uint32_t n_files,
+                                     const snpgpu_caller_params *params, const uint32_t *excl_off, const uint32_t *excl_slots,
+                                     uint8_t *d_out_base, uint8_t *d_out_filters,
+                                     snpgpu_site_counts *d_out_counts, uint64_t *d_out_line_off, uint64_t *out_status,
+                                     int32_t *out_rc, const snpgpu_stream_opts *opts, snpgpu_stream_stats *stats);
 
 /* call_consensus --vcfAllPos (call_consensus.py:148-151, pileup.py:418-421): a Record for EVERY line of the pileup,
  * whether its position is listed or not.  Synchronous; host outputs in file order: out_line_off[i] = 1 + byte offset of

@@ -128,6 +128,8 @@ SIGNATURES = {
     "snpgpu_call_consensus": (C.c_int, [_P, _P, _P, C.c_size_t, C.POINTER(CallerParams), _P, _P, _P, _P, C.c_int]),
     "snpgpu_call_consensus_files": (C.c_int, [_P, _P, C.POINTER(C.c_char_p), C.c_uint32, C.POINTER(CallerParams), _P, _P, _P, _P,
                                               _P, _P, _P, _P, C.POINTER(StreamOpts), C.POINTER(StreamStats)]),
+    "snpgpu_call_consensus_files_dev": (C.c_int, [_P, _P, C.POINTER(C.c_char_p), C.c_uint32, C.POINTER(CallerParams), _P, _P, _P, _P,
+                                                  _P, _P, _P, _P, C.POINTER(StreamOpts), C.POINTER(StreamStats)]),
     "snpgpu_call_consensus_many_dev": (C.c_int, [_P, _P, _P, _P, C.c_uint32, C.POINTER(CallerParams), _P, _P, _P, _P, _P, _P, C.c_int]),
     "snpgpu_region_flow_dev": (C.c_int, [_P, _P, _P, _P, C.c_uint32, C.c_uint32, _P, _P, C.c_uint32, _P, _P, _P, _P, _P]),
     "snpgpu_rows_copy_dev": (C.c_int, [_P, _P, C.c_uint64, _P, _P, C.c_uint64, _P, C.c_uint32, C.c_uint64]),

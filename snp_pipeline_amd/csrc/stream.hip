@@ -262,6 +262,8 @@ struct Outputs {
     uint64_t *line_off;             // nullable
     uint64_t *status;
     int32_t *rc;                    // nullable
+    bool on_device = false;         // base / filters / counts / line_off are DEVICE arrays: the kernels of file f write row f
+                                    // themselves, only the status words pass through the pinned result block
 };
 
 // What the readers and the orchestrator share.
@@ -408,8 +410,9 @@ int run_stream(snpgpu_ctx *ctx, const snpgpu_siteset *ss, std::vector<Source> &s
     if (n_slots > n_files) n_slots = n_files;
     const size_t slot_bytes = up(max_size + SNPGPU_SCAN_TILE + 256, 4096);
     const size_t r_base = 0, r_filt = up(r_base + n_sites, 256), r_stat = up(r_filt + n_sites, 256), r_line = r_stat + 256;
-    const size_t r_cnt = up(r_line + (out.line_off ? 8ull * n_sites : 0), 256);
-    const size_t r_flags = up(r_cnt + (out.counts ? sizeof(snpgpu_site_counts) * (size_t)n_sites : 0), 256);
+    const bool to_dev = out.on_device;                          // (the rows of the block are then unused: it holds status words and flags)
+    const size_t r_cnt = up(r_line + (out.line_off && !to_dev ? 8ull * n_sites : 0), 256);
+    const size_t r_flags = up(r_cnt + (out.counts && !to_dev ? sizeof(snpgpu_site_counts) * (size_t)n_sites : 0), 256);
     const size_t result_bytes = r_flags + (excl_off ? up(n_sites, 256) : 0) + 256;
     const size_t table_bytes = up((size_t)(max_chunks + 1) * 2 * sizeof(SampleDev), 256);
     {
@@ -430,7 +433,7 @@ int run_stream(snpgpu_ctx *ctx, const snpgpu_siteset *ss, std::vector<Source> &s
         const size_t o_base = o; o += up(n_sites, 256);
         const size_t o_filt = o; o += up(n_sites, 256);
         const size_t o_stat = o; o += 256;
-        const size_t o_cnt = o; o += out.counts ? up(sizeof(snpgpu_site_counts) * (size_t)n_sites, 256) : 0;
+        const size_t o_cnt = o; o += out.counts && !to_dev ? up(sizeof(snpgpu_site_counts) * (size_t)n_sites, 256) : 0;
         const size_t o_frow = o; o += excl_off ? up(n_sites, 256) * p->slot.size() : 0;
         void *ws = nullptr;
         int rc = snpgpu_scratch(ctx, o + 256, &ws);
@@ -441,7 +444,7 @@ int run_stream(snpgpu_ctx *ctx, const snpgpu_siteset *ss, std::vector<Source> &s
         if (!ds.todo_n) { close_all(); return SNPGPU_E_HIP; }
         ds.todo = (uint64_t *)(b + o_todo); ds.todo2 = (uint64_t *)(b + o_todo2); ds.base = (uint8_t *)(b + o_base);
         ds.filters = (uint8_t *)(b + o_filt); ds.status = (uint64_t *)(b + o_stat);
-        ds.counts = out.counts ? (snpgpu_site_counts *)(b + o_cnt) : nullptr;
+        ds.counts = out.counts && !to_dev ? (snpgpu_site_counts *)(b + o_cnt) : nullptr;
         ds.flag_rows = excl_off ? (uint8_t *)(b + o_frow) : nullptr;
         ds.flag_row_stride = up(n_sites, 256);
         if (d_site_line) ds.site_line = d_site_line;
@@ -482,7 +485,7 @@ int run_stream(snpgpu_ctx *ctx, const snpgpu_siteset *ss, std::vector<Source> &s
         t_wait_gpu += now_s() - t0;
         if (e != hipSuccess) return snpgpu_set_error(ctx, SNPGPU_E_HIP, "waiting for the results of pileup %u failed: %s", f, hipGetErrorString(e));
         const char *r = (const char *)p->result[slot];
-        if (n_sites) {
+        if (n_sites && !to_dev) {
             memcpy(out.base + (size_t)f * n_sites, r + r_base, n_sites);
             memcpy(out.filters + (size_t)f * n_sites, r + r_filt, n_sites);
             if (out.line_off) memcpy(out.line_off + (size_t)f * n_sites, r + r_line, 8ull * n_sites);
@@ -513,6 +516,12 @@ int run_stream(snpgpu_ctx *ctx, const snpgpu_siteset *ss, std::vector<Source> &s
             SampleDev *h_tab = (SampleDev *)p->table_host[slot];
             SampleDev *d_tab = (SampleDev *)((char *)ds.tables + ds.table_stride * slot);
             const uint32_t nc = chunks_of[f];
+            // where the kernels of this file leave their rows: the shared scratch rows (copied to the pinned block below), or row f
+            // of the caller's device arrays (any byte alignment: the scan and the call kernels store per element)
+            const size_t row = (size_t)f * n_sites;
+            uint64_t *f_line = to_dev && out.line_off ? out.line_off + row : ds.site_line;
+            uint8_t *f_base = to_dev ? out.base + row : ds.base, *f_filt = to_dev ? out.filters + row : ds.filters;
+            snpgpu_site_counts *f_counts = to_dev && out.counts ? out.counts + row : ds.counts;
             if (jb.first) {
                 // the slot, its table mirror and its result block are free once the file that used them has been harvested
                 while (harvested + (uint32_t)p->slot.size() <= f) { rc = harvest(harvested); if (rc) goto done; ++harvested; }
@@ -538,7 +547,7 @@ int run_stream(snpgpu_ctx *ctx, const snpgpu_siteset *ss, std::vector<Source> &s
                 cur_waves = h_tab[2 * nc + 1].wave0;
                 tiles_done = 0;
                 ST_TRY(hipMemcpyAsync(d_tab, h_tab, (size_t)(nc + 1) * 2 * sizeof(SampleDev), hipMemcpyHostToDevice, st));
-                rc = snpgpu_scan_begin(ctx, ss, d_tab + 2 * nc, 1, ds.site_line, ds.todo_n, SNPGPU_CALL_PASSES - 1);
+                rc = snpgpu_scan_begin(ctx, ss, d_tab + 2 * nc, 1, f_line, ds.todo_n, SNPGPU_CALL_PASSES - 1);
                 if (rc) goto done;
             }
             {
@@ -563,13 +572,13 @@ int run_stream(snpgpu_ctx *ctx, const snpgpu_siteset *ss, std::vector<Source> &s
             ST_TRY(hipStreamWaitEvent(st, p->ev_copy[j % R], 0));
             const SampleDev &e = h_tab[2 * jb.chunk];
             if (e.tile_hi > tiles_done) {
-                rc = snpgpu_scan_range(ctx, ss, d_tab + 2 * jb.chunk, 1, h_tab[2 * jb.chunk + 1].wave0, ds.totals, ds.site_line, want_depth);
+                rc = snpgpu_scan_range(ctx, ss, d_tab + 2 * jb.chunk, 1, h_tab[2 * jb.chunk + 1].wave0, ds.totals, f_line, want_depth);
                 if (rc) goto done;
                 tiles_done = e.tile_hi;
             }
             if (jb.last) {
                 const SampleDev *d_whole = d_tab + 2 * nc;
-                rc = snpgpu_scan_end(ctx, ss, d_whole, 1, cur_waves, ds.totals, ds.site_line, want_depth);
+                rc = snpgpu_scan_end(ctx, ss, d_whole, 1, cur_waves, ds.totals, f_line, want_depth);
                 char *r = (char *)p->result[slot];
                 const uint8_t *d_flags = nullptr;
                 if (rc == SNPGPU_OK && excl_off && n_sites) {
@@ -583,10 +592,18 @@ int run_stream(snpgpu_ctx *ctx, const snpgpu_siteset *ss, std::vector<Source> &s
                     d_flags = d_row;
                 }
                 if (rc == SNPGPU_OK)
-                    rc = snpgpu_enqueue_call(ctx, ss, d_whole, 1, prm, ds.site_line, ds.base, ds.filters, ds.counts, ds.todo_n, ds.todo, ds.todo2,
+                    rc = snpgpu_enqueue_call(ctx, ss, d_whole, 1, prm, f_line, f_base, f_filt, f_counts, ds.todo_n, ds.todo, ds.todo2,
                                              d_flags, 0);
                 if (rc) goto done;
-                if (n_sites) {
+                if (to_dev && n_sites && s.rc == SNPGPU_E_IO) {
+                    // could not be opened or read (known by now: the last piece has been waited for): its rows are void, and in the
+                    // caller's arrays that is '-' / 0 / no line / zeroed records rather than whatever the pieces that did arrive gave
+                    ST_TRY(hipMemsetAsync(f_base, '-', n_sites, st));
+                    ST_TRY(hipMemsetAsync(f_filt, 0, n_sites, st));
+                    if (out.line_off) ST_TRY(hipMemsetAsync(f_line, 0, 8ull * n_sites, st));
+                    if (out.counts) ST_TRY(hipMemsetAsync(f_counts, 0, sizeof(snpgpu_site_counts) * (size_t)n_sites, st));
+                }
+                if (n_sites && !to_dev) {
                     ST_TRY(hipMemcpyAsync(r + r_base, ds.base, n_sites, hipMemcpyDeviceToHost, st));
                     ST_TRY(hipMemcpyAsync(r + r_filt, ds.filters, n_sites, hipMemcpyDeviceToHost, st));
                     if (out.line_off) ST_TRY(hipMemcpyAsync(r + r_line, ds.site_line, 8ull * n_sites, hipMemcpyDeviceToHost, st));
@@ -738,6 +755,26 @@ int snpgpu_call_consensus_files(snpgpu_ctx *ctx, const snpgpu_siteset *ss, const
         src[f].path = paths[f];
     }
     Outputs out{out_base, out_filters, out_counts, out_line_off, out_status, out_rc};
+    return run_stream(ctx, ss, src, params, out, opts, stats, nullptr, excl_off, excl_slots);
+}
+
+// The same stream with the rows left on the device: the kernels of file f write row f of the caller's [n_files][n_sites] arrays
+// (the layout of snpgpu_call_consensus_many_dev), so a group of samples that was never resident is ready for the flow kernels
+// when the call returns.  Status words and return codes come back on the host, per file, as above.
+int snpgpu_call_consensus_files_dev(snpgpu_ctx *ctx, const snpgpu_siteset *ss, const char *const *paths, uint32_t n_files,
+                                    const snpgpu_caller_params *params, const uint32_t *excl_off, const uint32_t *excl_slots,
+                                    uint8_t *d_out_base, uint8_t *d_out_filters,
+                                    snpgpu_site_counts *d_out_counts, uint64_t *d_out_line_off, uint64_t *out_status,
+                                    int32_t *out_rc, const snpgpu_stream_opts *opts, snpgpu_stream_stats *stats) {
+    if (!ctx || !ss || !params || !out_status || (n_files && !paths)) return snpgpu_set_error(ctx, SNPGPU_E_ARG, "null argument");
+    if (ss->n_sites && n_files && (!d_out_base || !d_out_filters)) return snpgpu_set_error(ctx, SNPGPU_E_ARG, "null output");
+    std::vector<Source> src(n_files);
+    for (uint32_t f = 0; f < n_files; ++f) {
+        if (!paths[f]) return snpgpu_set_error(ctx, SNPGPU_E_ARG, "null path %u", f);
+        src[f].path = paths[f];
+    }
+    Outputs out{d_out_base, d_out_filters, d_out_counts, d_out_line_off, out_status, out_rc};
+    out.on_device = true;
     return run_stream(ctx, ss, src, params, out, opts, stats, nullptr, excl_off, excl_slots);
 }
 

@@ -267,6 +267,21 @@ def _again_on_spill_overflow(method):
     return wrapped
 
 
+def _exclude_csr(exclude, n_files):
+    """Per-file exclude lists (arrays of site-set slots; slots < 0 are ignored) as the CSR pair the streamed calls take."""
+    if exclude is None:
+        return None, None
+    lists = [np.asarray(e, dtype=np.int64) for e in exclude]
+    lists = [e[e >= 0].astype(np.uint32) for e in lists]
+    excl_off = np.zeros(n_files + 1, dtype=np.uint32)
+    if lists:
+        np.cumsum([len(e) for e in lists], out=excl_off[1:])
+    excl_slots = np.ascontiguousarray(np.concatenate(lists) if lists else np.zeros(0, np.uint32), dtype=np.uint32)
+    if len(excl_slots) == 0:
+        excl_slots = np.zeros(1, dtype=np.uint32)
+    return excl_off, excl_slots
+
+
 class ConsensusResult(object):
     __slots__ = ("bases", "filters", "counts", "status", "n_lines", "n_matched", "depth_sum", "line_offsets", "spill")
 
@@ -454,16 +469,7 @@ class Device(object):
         use ``raise_file_status``.  exclude: per path, the site-set slots of that file's own exclude list (arrays; slots < 0
         are ignored) — the file is called with SITE_EXCLUDED on them on top of the set's flags."""
         n_files, n = len(paths), len(siteset)
-        excl_off = excl_slots = None
-        if exclude is not None:
-            lists = [np.asarray(e, dtype=np.int64) for e in exclude]
-            lists = [e[e >= 0].astype(np.uint32) for e in lists]
-            excl_off = np.zeros(n_files + 1, dtype=np.uint32)
-            if lists:
-                np.cumsum([len(e) for e in lists], out=excl_off[1:])
-            excl_slots = np.ascontiguousarray(np.concatenate(lists) if lists else np.zeros(0, np.uint32), dtype=np.uint32)
-            if len(excl_slots) == 0:
-                excl_slots = np.zeros(1, dtype=np.uint32)
+        excl_off, excl_slots = _exclude_csr(exclude, n_files)
         enc = [os.fsencode(p) for p in paths]
         arr = (C.c_char_p * max(n_files, 1))(*enc)
         bases = np.empty((n_files, n), dtype=np.uint8)
@@ -484,6 +490,26 @@ class Device(object):
             r.line_offsets = line_off[f] if want_line_offsets else None
             results.append(r)
         return results, rcs[:n_files], stats
+
+    def call_consensus_files_dev(self, siteset, paths, params, d_bases, d_filters, d_counts=0, d_line_off=0, want_depth_sum=False,
+                                 chunk_bytes=0, n_readers=0, n_staging=0, n_slots=0, exclude=None):
+        """The streamed form with its rows left on the device (snpgpu_call_consensus_files_dev): the d_* arguments are device
+        pointers (ints) of [len(paths)][len(siteset)] arrays, the layout of ``call_consensus_many_dev``; file f's kernels write
+        row f.  Returns (status [n][4] uint64, rcs, stats) on the host.  Synchronous.  The spill records of all files are one
+        arena: ``read_symbol_spill`` after the call serves every row (and raises SpillOverflow when the caller has to repeat the
+        call).  exclude: as ``call_consensus_files``."""
+        n_files = len(paths)
+        excl_off, excl_slots = _exclude_csr(exclude, n_files)
+        arr = (C.c_char_p * max(n_files, 1))(*[os.fsencode(p) for p in paths])
+        status = np.zeros((max(n_files, 1), L.SCAN_STATUS_WORDS), dtype=np.uint64)
+        rcs = np.zeros(max(n_files, 1), dtype=np.int32)
+        opts = L.StreamOpts(int(chunk_bytes), int(n_staging), int(n_readers), int(n_slots), 1 if want_depth_sum else 0)
+        stats = L.StreamStats()
+        opt = lambda v: C.c_void_p(v) if v else None     # noqa: E731
+        self._check(self.lib.snpgpu_call_consensus_files_dev(
+            self.ctx, siteset.handle, arr, n_files, C.byref(params), _ptr(excl_off), _ptr(excl_slots), opt(d_bases), opt(d_filters),
+            opt(d_counts), opt(d_line_off), _ptr(status), _ptr(rcs), C.byref(opts), C.byref(stats)))
+        return status[:n_files], rcs[:n_files], stats
 
     @_again_on_spill_overflow
     def call_all_lines(self, siteset, path, params, capacity=0, check=True, listed_only=False):

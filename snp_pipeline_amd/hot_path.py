@@ -1,5 +1,11 @@
 """hot_path_batch: steps 4 (site calling) to 11 of the pipeline as ONE job — every pileup crosses the host link once.
 
+Once while the rank's pileups fit the resident budget (route ``resident``: they are kept in HBM between site calling and the
+consensus scan), and once at ANY size where the device does not write var.flt.vcf (``--siteCalling existing`` / ``varscan``, route
+``stream``: both site lists are known before the first pileup byte moves, so the consensus stage scans and calls each file as it
+lands and nothing is kept).  ``--pileupRoute auto`` (the default) takes ``stream`` exactly where ``resident`` would have to read
+files a second time; mode ``device`` past the budget still reads those files twice (its site calling needs the file first).
+
 The reference runs these steps as separate process arrays over a shared file system (run.py:662-784): call_sites
 (call_sites.py:89-108), filter_regions, merge_sites twice, call_consensus twice per sample (run.py:704-710 and :712-718),
 snp_matrix twice, snp_reference twice, distance twice — and every one of call_sites and the two call_consensus passes reads the
@@ -9,7 +15,9 @@ one explicit state object (``_Job``); a stage is a plain function of the job and
 
   stage_ingest_and_sites      every rank (= one GPU; torchrun-able) streams the pileups of ITS samples (a contiguous block of
                               the sorted sample directories) into HBM and KEEPS them (``Device.pileups``; files past the memory
-                              budget are re-streamed by the consensus stage).  Where var.flt.vcf comes from is the site calling
+                              budget are re-streamed by the consensus stage; on route ``stream`` nothing is copied here: the
+                              pileups are only opened, so that an unreadable one fails its sample before the site union, as the
+                              ingest would have).  Where var.flt.vcf comes from is the site calling
                               mode (``--siteCalling``, call_sites.py): ``device`` — site calling (csrc/varscan.hip) runs on each
                               file while the next one arrives and host threads finish each sample as its records come back;
                               ``varscan`` — the VarScan jar, as the reference runs it, on host threads beside the ingest;
@@ -18,7 +26,9 @@ one explicit state object (``_Job``); a stage is a plain function of the job and
                               (K4) on every rank — identical results everywhere; rank 0 writes snplist.txt / snplist_preserved.txt
                               and the two filtered directory lists, every rank the var.flt_preserved.vcf / var.flt_removed.vcf of
                               its samples
-  stage_consensus             ONE scan + call over the resident pileups at the positions of snplist.txt, with per-site records;
+  stage_consensus             ONE scan + call over the resident pileups at the positions of snplist.txt, with per-site records
+                              (route ``stream``: one streamed call per group of samples that leaves the same rows on the device,
+                              ``Device.call_consensus_files_dev``);
                               the preserved flow (snplist_preserved.txt columns, ``Region`` for the sample's removed positions) is
                               derived from it on the device (csrc/flows.hip); consensus.fasta / consensus.vcf /
                               consensus_preserved.fasta / consensus_preserved.vcf of a group of samples are written by host threads
@@ -63,6 +73,27 @@ from .utils import verbose_print
 
 INGEST_BATCH = 128          # files per streamed ingest call (the record arrays of a call are files x capacity x 48 bytes)
 VARSCAN_CAPACITY = 16384    # records per file in those arrays; a file with more is repeated alone
+
+
+PILEUP_ROUTES = ("resident", "stream", "auto")
+STREAM_MODES = ("existing", "varscan")      # site calling modes in which the device never looks at a pileup before the site lists exist
+
+
+def pileup_route_setting(given=None):
+    """`given` (a --pileupRoute option) or $SNPGPU_PILEUP_ROUTE or auto."""
+    route = (given or os.environ.get("SNPGPU_PILEUP_ROUTE") or "auto").lower()
+    if route not in PILEUP_ROUTES:
+        utils.global_error("Error: pileup route must be one of %s, not %r." % (", ".join(PILEUP_ROUTES), route))
+    return route
+
+
+def resolve_pileup_route(setting, site_calling, rank_bytes, budget_bytes):
+    """resident or stream for one rank.  ``auto`` is ``stream`` where the site lists do not need the device (STREAM_MODES) AND the
+    rank's pileup bytes exceed the resident budget — where the resident route would stream files a second time; every job that
+    fits keeps the resident route.  (An explicit ``stream`` in mode ``device`` is refused by the job, not here.)"""
+    if setting == "auto":
+        return "stream" if site_calling in STREAM_MODES and int(rank_bytes) > int(budget_bytes) else "resident"
+    return setting
 
 
 class _Sample(object):
@@ -173,6 +204,11 @@ class _Job(object):
         self.cc_args = _step_args("call_consensus", ["--vcfRefName", os.path.basename(ref_path), "--vcfFileName", "consensus.vcf", "x.pileup"], self.cc_extra)
         self.vs_opts = varscan.Options(env("VarscanMpileup2snp_ExtraParams", args.varscanExtraParams))
         self.site_calling = cs.site_calling_mode(getattr(args, "siteCalling", None))
+        self.route_setting = pileup_route_setting(getattr(args, "pileupRoute", None))
+        if self.route_setting == "stream" and self.site_calling not in STREAM_MODES:
+            utils.global_error("Error: --pileupRoute stream needs the site lists before the first pileup is read, so it goes with --siteCalling existing "
+                               "or varscan only: in mode %s the device calls the sites of each pileup, and that needs the file first." % self.site_calling)
+        self.pileup_route = None                       # resident / stream: resolved when the device is open (open_device)
         self.want_vcf = not args.noConsensusVcf
         # --collectMetrics: the metrics files (and the table) at the end of the job, from what the job holds (stage_collect_metrics)
         self.collect_metrics = bool(getattr(args, "collectMetrics", False))
@@ -197,6 +233,7 @@ class _Job(object):
         self.arenas = [None, None]
         self.arena_thread = None
         self.h2d_extra = 0
+        self.stream_stats = {"file_bytes": 0, "files": 0, "seconds": 0.0, "readers": 0}      # route stream: summed over the group calls
 
     # ---- small services of the state object ----------------------------------------------------------------------------------
     def lap(self, name, t0):
@@ -228,7 +265,22 @@ class _Job(object):
         # the one-GPU tests, and a host whose librccl.so cannot be loaded, keep torch.distributed
         if self.comm.dist and not self.comm.one_gpu and os.environ.get("SNPGPU_COMM") != "torch":
             self.abi_comm = self.sharding.use_abi_comm(self.dev)
-        self.store = self.dev.pileups(int(self.args.residentBytes or 0))
+        # the route: ``auto`` asks the store what its budget is (creating it allocates nothing); route stream keeps no store
+        if self.route_setting == "stream":
+            self.pileup_route = "stream"
+        else:
+            self.store = self.dev.pileups(int(self.args.residentBytes or 0))
+            rank_bytes = 0
+            if self.route_setting == "auto" and self.site_calling in STREAM_MODES:
+                for s in self.mine:
+                    try:
+                        rank_bytes += os.stat(s.pileup).st_size
+                    except OSError:
+                        pass
+            self.pileup_route = resolve_pileup_route(self.route_setting, self.site_calling, rank_bytes, int(self.store.stats().budget_bytes))
+            if self.pileup_route == "stream":
+                self.store.close()
+                self.store = None
 
     def close_device(self):
         if self.store is not None:
@@ -390,10 +442,57 @@ def _ingest_with_device_site_calling(job, todo):
     pool.shutdown()
 
 
+def _host_site_lists(job, todo):
+    """Modes ``varscan`` and ``existing``, the host's part: the VarScan jar where a var.flt.vcf is stale (``varscan``) or the check
+    that the files can serve as inputs (``existing`` — nothing under samples/*/var.flt.vcf is written), then the records."""
+    t_sites = time.perf_counter()
+    if job.site_calling == "existing":
+        for s in todo:
+            message = cs.check_existing_vcf(s.pileup, os.path.join(s.dir, "var.flt.vcf"))
+            if message:
+                s.fail(message)
+    else:
+        stale = [s for s in todo if job.args.forceFlag or utils.target_needs_rebuild([s.pileup], os.path.join(s.dir, "var.flt.vcf"))]
+        if stale:
+            jar = cs.find_path_in_path_list("VarScan", "CLASSPATH")
+            verbose_print("# %s %s  (and so on: %d samples)" % (utils.timestamp(), cs.varscan_command_line(jar or "VarScan.jar", stale[0].pileup), len(stale)))
+        for s, message in zip(stale, cs.run_varscan_jar_many([(s.pileup, os.path.join(s.dir, "var.flt.vcf")) for s in stale])):
+            if message:
+                s.fail(message)
+    with concurrent.futures.ThreadPoolExecutor(max_workers=max(2, devmod.host_threads(16, share=4))) as pool:
+        list(pool.map(_read_sample_vcf, [s for s in todo if s.ok]))
+    job.lap("1c   of which: var.flt.vcf files (%s) beside the ingest" % job.site_calling, t_sites)
+
+
+def _pileup_unreadable(path):
+    """What the ingest finds out when it opens a pileup (Opener::open_one): can it be opened for reading, is it a regular file?"""
+    import stat
+    try:
+        fd = os.open(path, os.O_RDONLY)
+    except OSError:
+        return True
+    try:
+        return not stat.S_ISREG(os.fstat(fd).st_mode)
+    finally:
+        os.close(fd)
+
+
+def _sites_without_ingest(job, todo):
+    """Route ``stream``: no pileup byte moves in this stage.  Every pileup is opened, so that one that cannot be read fails its
+    sample HERE with the ingest's message — the resident route drops such a sample before the site union, and both routes must
+    write the same snplist*.txt and filtered directory lists — then the host's part of the site lists, as beside an ingest."""
+    t_open = time.perf_counter()
+    with concurrent.futures.ThreadPoolExecutor(max_workers=max(2, devmod.host_threads(16, share=4))) as pool:
+        for s, bad in zip(todo, pool.map(_pileup_unreadable, [s.pileup for s in todo])):
+            if bad:
+                s.fail(_ingest_failed(s, L.E_IO, 0))
+    job.lap("1a   of which: pileups opened (route stream: nothing is copied yet)", t_open)
+    _host_site_lists(job, todo)
+
+
 def _ingest_only(job, todo):
     """Modes ``varscan`` and ``existing``: the files are only made resident (snpgpu_pileups_ingest without parameters), in a
-    helper thread; meanwhile this thread's pool runs the VarScan jar where a var.flt.vcf is stale (``varscan``) or checks that
-    the files can serve as inputs (``existing`` — nothing under samples/*/var.flt.vcf is written), and reads the records."""
+    helper thread; meanwhile this thread does the host's part of the site lists (_host_site_lists)."""
     store = job.store
     failure = []
 
@@ -415,24 +514,8 @@ def _ingest_only(job, todo):
     t_call = time.perf_counter()
     th = threading.Thread(target=run_ingest)
     th.start()
-    t_sites = time.perf_counter()
     try:
-        if job.site_calling == "existing":
-            for s in todo:
-                message = cs.check_existing_vcf(s.pileup, os.path.join(s.dir, "var.flt.vcf"))
-                if message:
-                    s.fail(message)
-        else:
-            stale = [s for s in todo if job.args.forceFlag or utils.target_needs_rebuild([s.pileup], os.path.join(s.dir, "var.flt.vcf"))]
-            if stale:
-                jar = cs.find_path_in_path_list("VarScan", "CLASSPATH")
-                verbose_print("# %s %s  (and so on: %d samples)" % (utils.timestamp(), cs.varscan_command_line(jar or "VarScan.jar", stale[0].pileup), len(stale)))
-            for s, message in zip(stale, cs.run_varscan_jar_many([(s.pileup, os.path.join(s.dir, "var.flt.vcf")) for s in stale])):
-                if message:
-                    s.fail(message)
-        with concurrent.futures.ThreadPoolExecutor(max_workers=max(2, devmod.host_threads(16, share=4))) as pool:
-            list(pool.map(_read_sample_vcf, [s for s in todo if s.ok]))
-        job.lap("1c   of which: var.flt.vcf files (%s) beside the ingest" % job.site_calling, t_sites)
+        _host_site_lists(job, todo)
     finally:
         th.join()
     job.lap("1a   of which: streamed ingest calls", t_call)
@@ -467,7 +550,10 @@ def stage_ingest_and_sites(job):
     job.arena_thread.start()
     todo = [s for s in job.mine if s.ok]
     cs.log_site_calling_mode(job.site_calling)
-    if job.site_calling == "device":
+    verbose_print("# pileup route: %s%s" % (job.pileup_route, " (auto)" if job.route_setting == "auto" else ""))
+    if job.pileup_route == "stream":
+        _sites_without_ingest(job, todo)
+    elif job.site_calling == "device":
         _ingest_with_device_site_calling(job, todo)
     else:
         _ingest_only(job, todo)
@@ -816,7 +902,27 @@ def _consensus_group(job, fl, g0, part, hs, vcf_again, vcf_later):
     t_g = time.perf_counter()
     g = len(part)
     one_launch = False                                        # the whole group in ONE call launch: then the launch's pass counts are the group's
-    resident = [(k, s) + store.get(s.store_index) for k, s in enumerate(part)]
+    streamed = job.pileup_route == "stream"
+    if streamed:
+        # nothing is resident: the group is ONE streamed call whose kernels write the group's rows where the flow kernels read them
+        # (snpgpu_call_consensus_files_dev) — the only time these pileups cross the link.  With an empty site set nothing is
+        # scanned, as on the resident route.
+        if S:
+            status, rcs, st = dev.call_consensus_files_dev(ss, [s.pileup for s in part], prm, d_base.data_ptr(), d_filt.data_ptr(),
+                                                           d_counts=d_counts.data_ptr() if want_vcf else 0, d_line_off=d_line.data_ptr(),
+                                                           want_depth_sum=fl.want_depth)
+            d_status[:g] = torch.from_numpy(status.view(np.int64)).cuda()
+            job.h2d_extra += int(st.bytes)
+            job.stream_stats["file_bytes"] += int(st.bytes)
+            job.stream_stats["files"] += g
+            job.stream_stats["seconds"] += float(st.seconds)
+            job.stream_stats["readers"] = max(job.stream_stats["readers"], int(st.n_readers))
+            for s, rc in zip(part, rcs):
+                if int(rc) == L.E_IO:                         # (readable in stage 1, not any more)
+                    s.fail(_ingest_failed(s, L.E_IO, 0))
+        else:
+            d_status[:g] = torch.tensor([-1, 0, 0, 0], dtype=torch.int64, device="cuda")
+    resident = [] if streamed else [(k, s) + store.get(s.store_index) for k, s in enumerate(part)]
     res_idx = [k for k, s, ptr, _ in resident if ptr]
     if res_idx and S:
         # resident samples first in the group's arrays would need a permutation: call them in place, sample by sample
@@ -930,7 +1036,8 @@ def _consensus_group(job, fl, g0, part, hs, vcf_again, vcf_later):
     group_spill = None
     if S and chk[:, 2].any():
         # positions with more than 8 distinct symbols: their spill records belong to ONE library call — there is one
-        # when the whole group was resident; a sample of a mixed group goes back to the per-sample command
+        # when the whole group was resident or the whole group was one streamed call (route stream); a sample of a mixed
+        # group goes back to the per-sample command
         if not rest:
             group_spill = dev.read_symbol_spill()
         else:
@@ -1176,12 +1283,15 @@ STAGES = (stage_ingest_and_sites, stage_site_union_and_regions, stage_consensus,
 
 
 def _job_stats(job):
-    st = job.store.stats()
+    st = job.store.stats() if job.store is not None else L.PileupsStats()
     fl = job.flows
+    if job.pileup_route == "stream":                         # nothing was ingested: the figures are those of the consensus stage's streamed calls
+        st.file_bytes, st.n_files, st.n_readers = job.stream_stats["file_bytes"], job.stream_stats["files"], job.stream_stats["readers"]
     done = getattr(job, "metrics_done", None)
     return {"collect_metrics": {k: v for k, v in done.items() if k != "errors"} if done else None,
             "h2d_bytes": int(st.h2d_bytes) + job.h2d_extra, "file_bytes": int(st.file_bytes), "resident_files": int(st.n_resident),
             "files": int(st.n_files), "seconds": time.perf_counter() - job.t_start, "site_calling": job.site_calling,
+            "pileup_route": job.pileup_route, "vcf_again": len(getattr(job, "vcf_again", ())),
             "ingest": {"seconds": st.seconds, "allocating": st.seconds_allocating, "waiting_for_readers": st.seconds_waiting_for_readers,
                        "waiting_for_device": st.seconds_waiting_for_device, "reader_seconds_reading": st.reader_seconds_reading,
                        "reader_seconds_waiting": st.reader_seconds_waiting, "preparing": st.seconds_preparing},
@@ -1196,7 +1306,10 @@ def hot_path_batch(args):
     over ``Device.CALL_PASS_NAMES`` (lanes128, lanes256, lanes512, wave): how many pileup lines of the job's consensus step each
     call kernel took, summed over the groups of samples whose call was one launch; ``groups_not_counted``, when present, is the
     number of groups that took several launches and are left out.  Lines under ``wave`` left the one-lane-per-site path: they
-    are longer than 512 bytes (a sample deeper than about 240x) or malformed.  ``-v 2`` logs the same figures per group."""
+    are longer than 512 bytes (a sample deeper than about 240x) or malformed.  ``-v 2`` logs the same figures per group.
+    ``pileup_route`` is the route this rank took (resident / stream, ``auto`` resolved); on route stream ``resident_files`` is 0
+    and ``h2d_bytes`` / ``file_bytes`` / ``files`` count what the consensus stage streamed.  ``vcf_again`` is the number of
+    samples whose VCF files the per-sample command wrote at the end (repeated positions, spill records of a mixed group)."""
     utils.print_log_header(classpath=True)
     utils.print_arguments(args)
     if getattr(args, "mergeVcfs", False) and args.noConsensusVcf:
@@ -1316,6 +1429,10 @@ def add_arguments(sub):
     sub.add_argument("--mergeVcfs", dest="mergeVcfs", action="store_true", help="At the end of the job write snpma.vcf and snpma_preserved.vcf (merge_vcfs) into the work directory, from the consensus.vcf / consensus_preserved.vcf files the job has just written; not with --noConsensusVcf")
     sub.add_argument("--vcfMerger", dest="vcfMerger", type=str, default=None, choices=("bcftools", "device", "auto"), metavar="MODE", help="With --mergeVcfs: who merges, as merge_vcfs --vcfMerger (default: $SNPGPU_VCF_MERGER, else auto)")
     sub.add_argument("--noConsensusVcf", dest="noConsensusVcf", action="store_true", help="Do not write consensus.vcf / consensus_preserved.vcf")
-    sub.add_argument("--residentBytes", dest="residentBytes", type=int, default=0, metavar="INT", help="Device memory for resident pileups (0 = what is free, less 24 GiB); files past it are streamed twice")
+    sub.add_argument("--residentBytes", dest="residentBytes", type=int, default=0, metavar="INT", help="Device memory for resident pileups (0 = what is free, less 24 GiB); files past it are streamed twice in site calling mode device only: in modes existing and varscan --pileupRoute auto streams every pileup once instead")
+    sub.add_argument("--pileupRoute", dest="pileupRoute", type=str, default=None, choices=PILEUP_ROUTES, metavar="ROUTE",
+                     help="How the pileups reach the consensus scan: resident (kept in device memory between site calling and the scan; files past --residentBytes are read a second time), "
+                          "stream (nothing is kept: the site lists are made first and each pileup is scanned and called as it lands, once, at any size; site calling modes existing and varscan only), "
+                          "auto (stream where the mode allows it and this rank's pileup bytes exceed the resident budget, else resident).  Default: $SNPGPU_PILEUP_ROUTE, else auto")
     sub.add_argument("--groupBytes", dest="groupBytes", type=int, default=0, metavar="INT", help="Host bytes of per-site results per group of samples (default 1 GiB)")
     sub.add_argument("--writerThreads", dest="writerThreads", type=int, default=0, metavar="INT", help="Host threads that write the consensus files (0 = up to 64)")

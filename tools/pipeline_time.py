@@ -33,9 +33,9 @@ def main():
     ap.add_argument("--dir", type=str, default=None)
     ap.add_argument("--recycle", type=int, default=0, help="GiB of device memory allocated, touched and freed before the tree is written")
     ap.add_argument("--sync", action="store_true", help="os.sync() after writing the tree: the run does not compete with the write-back of 54 GB")
-    ap.add_argument("--extra", type=str, default="", help="more options for hot_path_batch, e.g. '--siteCalling existing'")
+    ap.add_argument("--extra", type=str, default="", help="more options for hot_path_batch, e.g. '--siteCalling existing --pileupRoute stream' (with mode existing an untimed job writes the var.flt.vcf files first)")
     ap.add_argument("--resident-frac", type=float, default=0.0,
-                    help="after the timed runs: one more run with --residentBytes = this fraction of the pileup bytes (the rest is streamed twice); "
+                    help="after the timed runs: one more run with --residentBytes = this fraction of the pileup bytes (the rest is streamed twice, or with --pileupRoute auto in modes existing / varscan everything once: see pileup_route); "
                          "its time and whether every output file equals the fully resident run's")
     ap.add_argument("--collect-metrics", type=int, default=0, metavar="RUNS",
                     help="after the timed runs: RUNS runs each of the job alone, of collect_metrics_batch -f after it (every pileup read again "
@@ -129,6 +129,10 @@ def main():
                 out["probe_open_seconds"] = time.perf_counter() - t0
                 for fd in fds:
                     os.close(fd)
+        if "existing" in a.extra.split():
+            # --siteCalling existing takes the var.flt.vcf files as inputs: one untimed job in the default mode writes them first
+            bench.run_cli(bench.hot_path_line(dirs_file, ref_path, " --noConsensusVcf"), verbose=a.verbose)
+            out["site_files_written_by"] = hot_path.hot_path_batch.last_stats["site_calling"]
         runs = []
         for _ in range(a.runs):
             wall = bench.run_cli(bench.hot_path_line(dirs_file, ref_path, (" --noConsensusVcf" if a.no_vcf else "") + (" " + a.extra if a.extra else "")), verbose=a.verbose)
@@ -150,6 +154,7 @@ def main():
             st = dict(hot_path.hot_path_batch.last_stats)
             part = bench.output_digests(tmpdir, dirs)
             out["partly_resident"] = {"resident_bytes_budget": budget, "resident_files": st["resident_files"], "files": st["files"], "seconds": st["seconds"],
+                                      "pileup_route": st["pileup_route"],
                                       "h2d_bytes": st["h2d_bytes"], "h2d_over_file_bytes": st["h2d_bytes"] / total,
                                       "over_fully_resident": st["seconds"] / best["seconds"], "outputs_identical_to_fully_resident": part == full,
                                       "phases": st["phases"]}
