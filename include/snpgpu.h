@@ -435,8 +435,8 @@ int  snpgpu_vcf_count_snps_files(snpgpu_ctx *ctx, const char *const *paths, uint
  * (also in stats->bad_file / bad_offset); nothing is dropped silently.  SNPGPU_E_IO: a file cannot be read or written.
  * The text leaves the device in rounds of sites: as many whole rows as the output buffer holds are formatted, copied back in
  * 16 MiB pieces and written, then the next (stats->rounds); the buffer is 64 MiB, or 2^options bytes for options 12 to 32, and
- * never shorter than the longest row.  The records and the [site][column] table are held whole: 160 bytes a record and 4 bytes
- * a sample cell, at most 2^31 - 2 records.  Synchronous. */
+ * never shorter than the longest row.  snpgpu_merge_vcf_files is the single pass: the records and the [site][column] table
+ * are held whole, 160 bytes a record and 4 bytes a sample cell, at most 2^31 - 2 records.  Synchronous. */
 typedef struct snpgpu_merge_stats {
     uint64_t columns, sites, cells, host_lines, bytes;          /* bytes: the size of the merged file */
     uint64_t bad_file, bad_offset;                              /* of the line that ended the call (UINT64_MAX: none) */
@@ -445,6 +445,49 @@ typedef struct snpgpu_merge_stats {
 } snpgpu_merge_stats;
 int  snpgpu_merge_vcf_files(snpgpu_ctx *ctx, const char *const *paths, uint32_t n_files, const char *out_path,
                             const char *own_lines, uint32_t own_len, uint32_t options, snpgpu_merge_stats *stats);
+
+/* The merge at any size, in bounded device memory.  snpgpu_merge_plan (host only: no device, no context) says how a merge of
+ * n_files files with n_sites sites and total_input_bytes bytes of input runs under a budget of device bytes:
+ *   - the single pass above (input_passes 1, site_rounds 0) when its footprint fits: the record bound (one record per 56 bytes
+ *     of input plus room for 65 600), the key, sort and table arrays by the dense bound (every column a record at every site), the
+ *     row arrays, the output buffer and the stream's three piece buffers — figures of the input's size alone, so the route is
+ *     chosen before a byte is read;
+ *   - else a key pass and site_rounds passes, 1 + site_rounds readings of the input.  The key pass streams the files through a
+ *     kernel that keeps 24 bytes of a line (CHROM hash, POS, column, offset), in batches of as many keys as an eighth of the budget
+ *     past the stream's buffers holds (at least 4096), each sorted, uniqued and folded into the running site union: O(batch +
+ *     sites) bytes.  Then, for every
+ *     range of sites_per_round sites of the union, the files are streamed again, a record whose (contig, POS) ranks inside the
+ *     range goes to its slot [site - lo][column] (164 bytes a slot), and rows and text follow as in the single pass, appended to
+ *     the file.  sites_per_round is the most whole sites whose slots, row arrays and output buffer (planned at 256 + 48 bytes a
+ *     column per row, never more than 2^out_buffer_log2; a longer row gets its length) fit beside the union and the key
+ *     pass's arrays (freed by then, and counted all the same: every number of sites a round has a budget), and at most
+ *     (2^31 - 2) / n_files, and n_sites - 1 where the single pass could run but does not fit (the round of all sites is the
+ *     single pass).  passes->device_bytes: the bytes the plan holds.
+ * device_bytes 0: for snpgpu_merge_plan no budget at all, for the merge the device's free memory at the call less the larger of
+ * 1 GiB and a sixteenth of it.  SNPGPU_E_NOMEM: the budget is below the key pass and one site's round (passes->device_bytes: the
+ * bytes needed); the merge names them in its message and writes nothing.
+ * snpgpu_merge_vcf_files_opts follows that plan (passes, when given, reports it).  Results, errors, messages and stats are those of
+ * the single pass on the same input; stats->host_lines counts a host-parsed line once, cells and sites are totals, rounds sums
+ * the ranges of sites the text went out in.  The bounded form writes to a sibling of out_path and renames it at the end: after an
+ * error out_path is as it was before the call.  (Where two errors sit in different site rounds the one of the earlier round is
+ * reported.) */
+typedef struct snpgpu_merge_opts {
+    uint32_t out_buffer_log2;   /* 0, or 12..32: as `options` of snpgpu_merge_vcf_files */
+    uint32_t reserved;
+    uint64_t device_bytes;      /* budget for everything the merge allocates on the device; 0: see above */
+    uint64_t reserved2[2];
+} snpgpu_merge_opts;
+typedef struct snpgpu_merge_passes {
+    uint32_t input_passes;      /* 1 = the single pass; else 1 + site_rounds */
+    uint32_t site_rounds;
+    uint64_t sites_per_round;
+    uint64_t device_bytes;      /* what the plan holds (after SNPGPU_E_NOMEM: what it would need) */
+} snpgpu_merge_passes;
+int  snpgpu_merge_plan(uint32_t n_files, uint64_t n_sites, uint64_t total_input_bytes, const snpgpu_merge_opts *opts,
+                       snpgpu_merge_passes *out);
+int  snpgpu_merge_vcf_files_opts(snpgpu_ctx *ctx, const char *const *paths, uint32_t n_files, const char *out_path,
+                                 const char *own_lines, uint32_t own_len, const snpgpu_merge_opts *opts,
+                                 snpgpu_merge_stats *stats, snpgpu_merge_passes *passes /* may be NULL */);
 
 /* ---- resident pileups: the input side of the one-job pipeline (`cfsan_snp_pipeline hot_path_batch`) ----------------------
  * The reference runs steps 4-11 as separate process arrays over a shared file system (run.py:662-784): call_sites

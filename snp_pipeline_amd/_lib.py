@@ -40,6 +40,14 @@ class MergeStats(C.Structure):
                 ("seconds_write", C.c_double), ("writer_threads", C.c_uint32), ("rounds", C.c_uint32)]
 
 
+class MergeOpts(C.Structure):
+    _fields_ = [("out_buffer_log2", C.c_uint32), ("reserved", C.c_uint32), ("device_bytes", C.c_uint64), ("reserved2", C.c_uint64 * 2)]
+
+
+class MergePasses(C.Structure):
+    _fields_ = [("input_passes", C.c_uint32), ("site_rounds", C.c_uint32), ("sites_per_round", C.c_uint64), ("device_bytes", C.c_uint64)]
+
+
 class SymbolSpill(C.Structure):
     _fields_ = [("n", C.c_uint32), ("ref_len", C.c_uint32), ("depth64", C.c_int64), ("sym", C.c_uint8 * SPILL_SYMS),
                 ("total", C.c_uint32 * SPILL_SYMS), ("fwd", C.c_uint32 * SPILL_SYMS), ("rev", C.c_uint32 * SPILL_SYMS),
@@ -180,6 +188,8 @@ SIGNATURES = {
     "snpgpu_merge_regions_dev": (C.c_int, [_P, _P, _P, _P, C.c_uint32, _P, _P, _P, _P]),
     "snpgpu_in_regions_dev": (C.c_int, [_P, _P, _P, C.c_uint32, _P, _P, _P, C.c_uint32, _P]),
     "snpgpu_merge_vcf_files": (C.c_int, [_P, C.POINTER(C.c_char_p), C.c_uint32, C.c_char_p, C.c_char_p, C.c_uint32, C.c_uint32, _P]),
+    "snpgpu_merge_vcf_files_opts": (C.c_int, [_P, C.POINTER(C.c_char_p), C.c_uint32, C.c_char_p, C.c_char_p, C.c_uint32, _P, _P, _P]),
+    "snpgpu_merge_plan": (C.c_int, [C.c_uint32, C.c_uint64, C.c_uint64, _P, _P]),
     "snpgpu_merge_sites_dev": (C.c_int, [_P, _P, _P, C.c_uint32, _P, _P, _P, _P]),
     "snpgpu_comm_available": (C.c_int, []),
     "snpgpu_comm_version": (C.c_int, [C.POINTER(C.c_int)]),

@@ -182,6 +182,31 @@ int snpgpu_enqueue_merge_contig_first(snpgpu_ctx *ctx, snpgpu_merge_cell *d_cell
 int snpgpu_enqueue_merge_site_keys(snpgpu_ctx *ctx, snpgpu_merge_cell *d_cells, uint64_t n, const uint32_t *d_rank, uint64_t *d_keys, uint32_t *d_cols);
 int snpgpu_enqueue_merge_scatter(snpgpu_ctx *ctx, const snpgpu_merge_cell *d_cells, uint64_t n, const uint64_t *d_sites, const uint32_t *d_n_sites, uint32_t n_col,
                                  uint32_t *d_table, uint64_t *d_ctl);
+// the bounded route: what the key pass keeps of a data line, and what the pass of a site range places its records by
+struct snpgpu_merge_key { uint64_t hash, off; uint32_t pos, column; };   // FNV-1a of CHROM, file offset of the line, POS, column
+struct snpgpu_merge_range {
+    const uint64_t *hashes;         // the n_contigs distinct CHROM hashes, ascending ...
+    const uint32_t *rank;           // ... and each one's contig number (order of first appearance over the columns)
+    const uint64_t *sites;          // the n_sites keys (contig << 32) | POS of the site union, ascending
+    uint32_t n_contigs, n_sites, lo, hi, n_col;                 // the range [lo, hi) of sites, the number of columns
+    snpgpu_merge_cell *cells;       // [hi - lo][n_col]
+    uint32_t *table;                // [hi - lo][n_col]: slot + 1 where the slot holds a record
+};
+int snpgpu_enqueue_merge_lines(snpgpu_ctx *ctx, const uint8_t *d_buf, uint32_t n, uint32_t own_from, uint64_t file_off, uint32_t column, snpgpu_merge_key *d_keys,
+                               uint64_t key_cap, const snpgpu_merge_range *range, uint64_t *d_ctl, uint64_t *d_unusual, uint32_t unusual_cap, const uint8_t *d_filt,
+                               const uint32_t *d_filt_off, uint32_t n_filt);
+int snpgpu_enqueue_merge_key_hashes(snpgpu_ctx *ctx, const snpgpu_merge_key *d_rec, uint32_t n, uint64_t *d_keys, uint32_t *d_zeros);
+int snpgpu_enqueue_merge_key_first(snpgpu_ctx *ctx, const snpgpu_merge_key *d_rec, uint32_t n, const uint64_t *d_uniq, const uint32_t *d_n_uniq, uint32_t *d_which,
+                                   uint64_t *d_first);
+int snpgpu_enqueue_merge_key_sites(snpgpu_ctx *ctx, const snpgpu_merge_key *d_rec, uint32_t n, const uint32_t *d_which, const uint32_t *d_id, uint64_t *d_keys,
+                                   uint32_t *d_zeros);
+int snpgpu_enqueue_merge_key_rank(snpgpu_ctx *ctx, uint64_t *d_keys, uint32_t n, const uint32_t *d_rank, uint32_t *d_zeros);
+int snpgpu_enqueue_merge_place(snpgpu_ctx *ctx, const snpgpu_merge_cell *d_extra, uint32_t n, uint32_t lo, uint32_t n_col, snpgpu_merge_cell *d_cells, uint32_t *d_table,
+                               uint64_t *d_ctl);
+// regions.hip: merge_sites in the caller's own workspace
+size_t snpgpu_merge_sites_ws_bytes(uint64_t n);
+int snpgpu_enqueue_merge_sites_ws(snpgpu_ctx *ctx, const uint64_t *d_keys, const uint32_t *d_sample_of_key, uint32_t n, uint64_t *d_out_unique, uint32_t *d_out_off,
+                                  uint32_t *d_out_carrier, uint32_t *d_out_n, void *d_ws);
 size_t snpgpu_merge_rows_scan_words(uint32_t n_sites);
 int snpgpu_enqueue_merge_rows(snpgpu_ctx *ctx, int write, const snpgpu_merge_cell *d_cells, const uint32_t *d_table, uint32_t n_col, const uint64_t *d_site_keys,
                               uint32_t n_sites, uint32_t site_lo, uint32_t site_hi, uint64_t out_base, const uint8_t *d_names, const uint32_t *d_name_off, const uint8_t *d_filt, const uint32_t *d_filt_off,

@@ -260,7 +260,7 @@ __global__ void k_sites_emit(const Pair *sorted, uint32_t n, const uint32_t *new
     if (new_key[i]) { out_unique[key_slot[i]] = sorted[i].key; out_off[key_slot[i]] = pair_slot[i]; }
 }
 
-size_t merge_sites_ws_bytes(uint32_t n) {
+size_t merge_sites_ws_bytes(uint64_t n) {
     return 3 * up256(sizeof(Pair) * (size_t)n) + 256 + 4 * up256(4ull * n) + 2 * up256(4 * prim_scan_workspace_words(n)) + 256;
 }
 
@@ -521,3 +521,13 @@ int snpgpu_merge_sites(snpgpu_ctx *ctx, const uint64_t *keys, const uint32_t *sa
 }
 
 }  // extern "C"
+
+// merge_sites with the caller's own workspace (snpgpu_merge_sites_ws_bytes(n) bytes): for a caller that holds other data in the
+// context's scratch meanwhile (the bounded merge_vcfs folds key batches while the stream's piece buffers live there)
+size_t snpgpu_merge_sites_ws_bytes(uint64_t n) { return merge_sites_ws_bytes(n); }
+
+int snpgpu_enqueue_merge_sites_ws(snpgpu_ctx *ctx, const uint64_t *d_keys, const uint32_t *d_sample_of_key, uint32_t n, uint64_t *d_out_unique, uint32_t *d_out_off,
+                                  uint32_t *d_out_carrier, uint32_t *d_out_n, void *d_ws) {
+    if (n > 0x7FFFFFFFu) return snpgpu_set_error(ctx, SNPGPU_E_UNSUPPORTED, "too many site records");
+    return merge_sites_enqueue(ctx, d_keys, d_sample_of_key, n, d_out_unique, d_out_off, d_out_carrier, d_out_n, (char *)d_ws);
+}

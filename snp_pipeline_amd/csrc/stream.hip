@@ -37,6 +37,8 @@
 
 #include <algorithm>
 
+#include <unordered_map>
+
 #include "internal.h"
 
 namespace {
@@ -2109,6 +2111,9 @@ bool merge_read_line(int fd, uint64_t off, std::string &line, uint64_t *start) {
 struct MergeBuffers {                // everything merge_vcf_files allocates on the device, freed on every way out
     std::vector<void *> d;
     ~MergeBuffers() { for (void *p : d) if (p) (void)hipFree(p); }
+    void release(void *p) {         // one of them, early
+        for (void *&q : d) if (q == p && p) { (void)hipFree(p); q = nullptr; }
+    }
     template <class T> hipError_t get(T **out, size_t bytes) {
         void *p = nullptr;
         const hipError_t e = hipMalloc(&p, bytes ? bytes : 256);
@@ -2120,17 +2125,23 @@ struct MergeBuffers {                // everything merge_vcf_files allocates on 
 
 double seconds_since(const std::chrono::steady_clock::time_point &t0) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); }
 
-int merge_vcf_files(snpgpu_ctx *ctx, const char *const *paths, uint32_t n_files, const char *out_path, const char *own_lines, uint32_t own_len,
-                    uint64_t out_cap, snpgpu_merge_stats *stats) {
-    constexpr uint32_t UNUSUAL_CAP = 1u << 16;
-    HIP_TRY(ctx, snpgpu_enter(ctx));
-    hipStream_t st = ctx->stream;
-    auto t0 = std::chrono::steady_clock::now();
-    // the headers: the first file's lines, every file's column name, the filter ids the records are held against
-    std::vector<std::string> header, names(n_files);
+constexpr uint32_t MERGE_UNUSUAL_CAP = 1u << 16;            // lines outside the kernel's grammar the host takes in one merge
+
+// the headers: the first file's lines, every file's column name, the filter ids the records are held against
+struct MergeInput {
+    std::vector<std::string> header, names;
     std::string filt;
-    std::vector<uint32_t> filt_off(1, 0);
+    std::vector<uint32_t> filt_off;
     uint64_t total_bytes = 0;
+};
+
+int merge_read_input(snpgpu_ctx *ctx, const char *const *paths, uint32_t n_files, snpgpu_merge_stats *stats, MergeInput &in) {
+    std::vector<std::string> &header = in.header, &names = in.names;
+    std::string &filt = in.filt;
+    std::vector<uint32_t> &filt_off = in.filt_off;
+    uint64_t &total_bytes = in.total_bytes;
+    names.resize(n_files);
+    filt_off.assign(1, 0);
     for (uint32_t f = 0; f < n_files; ++f) {
         std::vector<std::string> h;
         std::string chrom;
@@ -2157,8 +2168,188 @@ int merge_vcf_files(snpgpu_ctx *ctx, const char *const *paths, uint32_t n_files,
         filt += id;
         filt_off.push_back((uint32_t)filt.size());
     }
+    if (filt_off.size() - 1 > 31) return snpgpu_set_error(ctx, SNPGPU_E_UNSUPPORTED, "%s: more than 31 filters", paths[0]);
+    return SNPGPU_OK;
+}
+
+// The lines the kernel left alone ((column, offset) pairs, as the parse kernel reports them): one at a time on the host, by the same
+// routine in its wider setting.  Their records (key: the CHROM hash, off and column set) are appended to `extra`.
+int merge_host_lines(snpgpu_ctx *ctx, const char *const *paths, const std::vector<uint64_t> &unusual, const MergeInput &in, snpgpu_merge_stats *stats,
+                     std::vector<snpgpu_merge_cell> &extra) {
+    const uint32_t n_filt = (uint32_t)in.filt_off.size() - 1;
+    std::string line;
+    for (size_t k = 0; k < unusual.size() / 2; ++k) {
+        const uint32_t f = (uint32_t)unusual[2 * k];
+        const int fd = open(paths[f], O_RDONLY | O_CLOEXEC);
+        uint64_t start = 0;
+        const bool got = fd >= 0 && merge_read_line(fd, unusual[2 * k + 1], line, &start);
+        if (fd >= 0) close(fd);
+        if (!got) { stats->bad_file = f; return snpgpu_set_error(ctx, SNPGPU_E_IO, "cannot open or read the VCF file %s", paths[f]); }
+        if (line.empty() || line[0] == '#') continue;
+        snpgpu_merge_cell c;
+        if (line.size() > 0x7FFFFFFFu ||
+            !snpgpu_merge_parse_line((const uint8_t *)line.data(), 0, (uint32_t)line.size(), (const uint8_t *)in.filt.data(), in.filt_off.data(), n_filt, false, &c)) {
+            stats->bad_file = f;
+            stats->bad_offset = start;
+            return snpgpu_set_error(ctx, SNPGPU_E_UNSUPPORTED, "%s: the line at byte %llu is outside the pipeline's own VCF grammar, on which alone the merge is pinned",
+                                    paths[f], (unsigned long long)start);
+        }
+        c.off = start;
+        c.column = f;
+        extra.push_back(c);
+        ++stats->host_lines;
+    }
+    return SNPGPU_OK;
+}
+
+// The contigs in order of first appearance over the columns.  first[i]: column << 40 | offset of the first line that carries contig i.
+// rank[i]: its place in that order; contigs: the names in that order, read from those lines.
+int merge_contig_order(snpgpu_ctx *ctx, const char *const *paths, const std::vector<uint64_t> &first, snpgpu_merge_stats *stats, std::vector<uint32_t> &rank,
+                       std::vector<std::string> &contigs, std::string &all_names, std::vector<uint32_t> &name_off) {
+    const uint32_t n = (uint32_t)first.size();
+    std::vector<uint32_t> order(n);
+    rank.resize(n);
+    name_off.assign(1, 0);
+    for (uint32_t i = 0; i < n; ++i) order[i] = i;
+    std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return first[a] < first[b]; });
+    std::string line;
+    for (uint32_t r = 0; r < n; ++r) {
+        rank[order[r]] = r;
+        const uint32_t f = (uint32_t)(first[order[r]] >> 40);
+        const int fd = open(paths[f], O_RDONLY | O_CLOEXEC);
+        uint64_t start = 0;
+        const bool got = fd >= 0 && merge_read_line(fd, first[order[r]] & ((1ull << 40) - 1), line, &start);
+        if (fd >= 0) close(fd);
+        if (!got) { stats->bad_file = f; return snpgpu_set_error(ctx, SNPGPU_E_IO, "cannot open or read the VCF file %s", paths[f]); }
+        contigs.push_back(line.substr(0, line.find('\t')));
+        all_names += contigs.back();
+        name_off.push_back((uint32_t)all_names.size());
+    }
+    return SNPGPU_OK;
+}
+
+// the header of the merged file
+std::string merge_head_text(const MergeInput &in, const std::vector<std::string> &contigs, const char *own_lines, uint32_t own_len) {
+    std::string head;
+    const std::string pass_line = "##FILTER=<ID=PASS,Description=\"All filters passed\">";
+    std::vector<std::string> lines;
+    for (const std::string &h : in.header) if (h != pass_line) lines.push_back(h);
+    lines.insert(lines.begin() + ((!lines.empty() && lines[0].compare(0, 12, "##fileformat") == 0) ? 1 : 0), pass_line);
+    for (const std::string &l : lines) { head += l; head += '\n'; }
+    for (const std::string &c : contigs) { head += "##contig=<ID=" + c + ">\n"; }
+    if (own_lines && own_len) head.append(own_lines, own_len);
+    head += "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT";
+    for (const std::string &n : in.names) { head += '\t'; head += n; }
+    head += '\n';
+    return head;
+}
+
+// The text of device buffers to a file: copied back in 16 MiB pieces through the staging ring, each piece written at its place by
+// a writer thread.  start(), any number of copy(), finish().
+struct MergeWriter {
+    struct Piece { uint64_t slot, off, len; };                  // staging buffer, offset in the file, bytes
+    static constexpr size_t CHUNK = (size_t)16 << 20;
+    snpgpu_ctx *ctx;
+    int fd;
+    snpgpu_stream_pool *p = nullptr;
+    uint64_t R = 0, j = 0;
+    std::mutex mu;
+    std::condition_variable cv;
+    std::vector<Piece> ready;                                   // pieces copied back, waiting for a writer
+    std::vector<char> busy;                                     // staging buffer in use (being filled or written)
+    bool closing = false, failed = false;
+    std::vector<std::thread> writers;
+    hipError_t herr = hipSuccess;
+
+    MergeWriter(snpgpu_ctx *c, int f) : ctx(c), fd(f) {}
+    ~MergeWriter() { (void)finish(); }
+    static uint64_t pieces(uint64_t len) { return (len + CHUNK - 1) / CHUNK; }
+    void writer_main() {
+        for (;;) {
+            Piece pc;
+            {
+                std::unique_lock<std::mutex> lk(mu);
+                cv.wait(lk, [&] { return closing || !ready.empty(); });
+                if (ready.empty()) return;
+                pc = ready.back();
+                ready.pop_back();
+            }
+            const char *h = (const char *)p->staging[pc.slot];
+            bool ok = true;
+            for (uint64_t at = 0; at < pc.len && ok;) {
+                const ssize_t w = pwrite(fd, h + at, pc.len - at, (off_t)(pc.off + at));
+                if (w <= 0) ok = false; else at += (uint64_t)w;
+            }
+            {
+                std::lock_guard<std::mutex> lk(mu);
+                busy[pc.slot] = 0;
+                if (!ok) failed = true;
+            }
+            cv.notify_all();
+        }
+    }
+    // n_pieces: how many pieces the copies will come to (at least 1); *n_writers: the threads that run
+    int start(uint64_t n_pieces, uint32_t *n_writers) {
+        uint32_t n = snpgpu_writer_threads(16);
+        if (n > n_pieces) n = (uint32_t)n_pieces;
+        if (n < 1) n = 1;
+        *n_writers = n;
+        const uint32_t n_ring = (uint32_t)(n_pieces < n + 2 ? n_pieces : n + 2);
+        const int rc = pool_ensure(ctx, CHUNK, n_ring, 0, 0, 0, 0);
+        if (rc) return rc;
+        p = ctx->pool;
+        R = p->staging.size() < n_ring ? p->staging.size() : n_ring;
+        busy.assign(R, 0);
+        try {
+            for (uint32_t i = 0; i < n; ++i) writers.emplace_back([this] { writer_main(); });
+        } catch (const std::exception &) {
+            if (writers.empty()) return snpgpu_set_error(ctx, SNPGPU_E_NOMEM, "cannot start a writer thread");
+        }
+        return SNPGPU_OK;
+    }
+    // d_src[0, len) to the file at file_off (after an error of the device nothing more is copied: see herr)
+    void copy(const uint8_t *d_src, uint64_t len, uint64_t file_off) {
+        for (uint64_t lo = 0; lo < len && herr == hipSuccess; lo += CHUNK, ++j) {
+            const uint64_t slot = j % R;
+            {
+                std::unique_lock<std::mutex> lk(mu);
+                cv.wait(lk, [&] { return !busy[slot]; });
+                busy[slot] = 1;
+            }
+            const uint64_t n = len - lo < CHUNK ? len - lo : CHUNK;
+            herr = hipMemcpyAsync(p->staging[slot], d_src + lo, n, hipMemcpyDeviceToHost, ctx->stream);
+            if (herr == hipSuccess) herr = hipStreamSynchronize(ctx->stream);
+            if (herr != hipSuccess) break;
+            { std::lock_guard<std::mutex> lk(mu); ready.push_back(Piece{slot, file_off + lo, n}); }
+            cv.notify_all();
+        }
+    }
+    // every piece is written (false: a write failed)
+    bool finish() {
+        { std::lock_guard<std::mutex> lk(mu); closing = true; }
+        cv.notify_all();
+        for (auto &t : writers) t.join();
+        writers.clear();
+        return !failed;
+    }
+};
+
+int merge_vcf_files(snpgpu_ctx *ctx, const char *const *paths, uint32_t n_files, const char *out_path, const char *own_lines, uint32_t own_len,
+                    uint64_t out_cap, snpgpu_merge_stats *stats, const MergeInput *given = nullptr) {
+    constexpr uint32_t UNUSUAL_CAP = MERGE_UNUSUAL_CAP;
+    HIP_TRY(ctx, snpgpu_enter(ctx));
+    hipStream_t st = ctx->stream;
+    auto t0 = std::chrono::steady_clock::now();
+    MergeInput own_input;
+    if (!given) {
+        const int hrc = merge_read_input(ctx, paths, n_files, stats, own_input);
+        if (hrc) return hrc;
+        given = &own_input;
+    }
+    const std::string &filt = given->filt;
+    const std::vector<uint32_t> &filt_off = given->filt_off;
+    const uint64_t total_bytes = given->total_bytes;
     const uint32_t n_filt = (uint32_t)filt_off.size() - 1;
-    if (n_filt > 31) return snpgpu_set_error(ctx, SNPGPU_E_UNSUPPORTED, "%s: more than 31 filters", paths[0]);
 
     MergeBuffers mem;
     const uint64_t cell_cap = total_bytes / 56 + UNUSUAL_CAP + 64;      // (no line of the grammar is shorter than 56 bytes)
@@ -2201,28 +2392,8 @@ int merge_vcf_files(snpgpu_ctx *ctx, const char *const *paths, uint32_t n_files,
         std::vector<uint64_t> unusual(2 * ctl[1]);
         HIP_TRY(ctx, hipMemcpy(unusual.data(), d_unusual, 16 * ctl[1], hipMemcpyDeviceToHost));
         std::vector<snpgpu_merge_cell> extra;
-        std::string line;
-        for (uint64_t k = 0; k < ctl[1]; ++k) {
-            const uint32_t f = (uint32_t)unusual[2 * k];
-            const int fd = open(paths[f], O_RDONLY | O_CLOEXEC);
-            uint64_t start = 0;
-            const bool got = fd >= 0 && merge_read_line(fd, unusual[2 * k + 1], line, &start);
-            if (fd >= 0) close(fd);
-            if (!got) { stats->bad_file = f; return snpgpu_set_error(ctx, SNPGPU_E_IO, "cannot open or read the VCF file %s", paths[f]); }
-            if (line.empty() || line[0] == '#') continue;
-            snpgpu_merge_cell c;
-            if (line.size() > 0x7FFFFFFFu ||
-                !snpgpu_merge_parse_line((const uint8_t *)line.data(), 0, (uint32_t)line.size(), (const uint8_t *)filt.data(), filt_off.data(), n_filt, false, &c)) {
-                stats->bad_file = f;
-                stats->bad_offset = start;
-                return snpgpu_set_error(ctx, SNPGPU_E_UNSUPPORTED, "%s: the line at byte %llu is outside the pipeline's own VCF grammar, on which alone the merge is pinned",
-                                        paths[f], (unsigned long long)start);
-            }
-            c.off = start;
-            c.column = f;
-            extra.push_back(c);
-            ++stats->host_lines;
-        }
+        rc = merge_host_lines(ctx, paths, unusual, *given, stats, extra);
+        if (rc) return rc;
         if (n_cells + extra.size() > cell_cap) return snpgpu_set_error(ctx, SNPGPU_E_UNSUPPORTED, "more VCF records than the merge made room for");
         if (!extra.empty()) HIP_TRY(ctx, hipMemcpy(d_cells + n_cells, extra.data(), extra.size() * sizeof(snpgpu_merge_cell), hipMemcpyHostToDevice));
         n_cells += extra.size();
@@ -2259,22 +2430,10 @@ int merge_vcf_files(snpgpu_ctx *ctx, const char *const *paths, uint32_t n_files,
         std::vector<uint64_t> first(n_u[0]);
         HIP_TRY(ctx, hipMemcpyAsync(first.data(), d_first, 8ull * n_u[0], hipMemcpyDeviceToHost, st));
         HIP_TRY(ctx, hipStreamSynchronize(st));
-        std::vector<uint32_t> order(n_u[0]), rank(n_u[0]), name_off(1, 0);
-        for (uint32_t i = 0; i < n_u[0]; ++i) order[i] = i;
-        std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return first[a] < first[b]; });
-        std::string all_names, line;
-        for (uint32_t r = 0; r < n_u[0]; ++r) {
-            rank[order[r]] = r;
-            const uint32_t f = (uint32_t)(first[order[r]] >> 40);
-            const int fd = open(paths[f], O_RDONLY | O_CLOEXEC);
-            uint64_t start = 0;
-            const bool got = fd >= 0 && merge_read_line(fd, first[order[r]] & ((1ull << 40) - 1), line, &start);
-            if (fd >= 0) close(fd);
-            if (!got) { stats->bad_file = f; return snpgpu_set_error(ctx, SNPGPU_E_IO, "cannot open or read the VCF file %s", paths[f]); }
-            contigs.push_back(line.substr(0, line.find('\t')));
-            all_names += contigs.back();
-            name_off.push_back((uint32_t)all_names.size());
-        }
+        std::vector<uint32_t> rank, name_off;
+        std::string all_names;
+        rc = merge_contig_order(ctx, paths, first, stats, rank, contigs, all_names, name_off);
+        if (rc) return rc;
         HIP_TRY(ctx, mem.get(&d_names, all_names.size() + 16));
         HIP_TRY(ctx, mem.get(&d_name_off, 4 * name_off.size()));
         HIP_TRY(ctx, hipMemcpyAsync(d_names, all_names.data(), all_names.size(), hipMemcpyHostToDevice, st));
@@ -2295,20 +2454,7 @@ int merge_vcf_files(snpgpu_ctx *ctx, const char *const *paths, uint32_t n_files,
     }
     stats->sites = n_sites;
 
-    // the header
-    std::string head;
-    {
-        const std::string pass_line = "##FILTER=<ID=PASS,Description=\"All filters passed\">";
-        std::vector<std::string> lines;
-        for (const std::string &h : header) if (h != pass_line) lines.push_back(h);
-        lines.insert(lines.begin() + ((!lines.empty() && lines[0].compare(0, 12, "##fileformat") == 0) ? 1 : 0), pass_line);
-        for (const std::string &l : lines) { head += l; head += '\n'; }
-        for (const std::string &c : contigs) { head += "##contig=<ID=" + c + ">\n"; }
-        if (own_lines && own_len) head.append(own_lines, own_len);
-        head += "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT";
-        for (const std::string &n : names) { head += '\t'; head += n; }
-        head += '\n';
-    }
+    const std::string head = merge_head_text(*given, contigs, own_lines, own_len);
 
     // rows: the lengths and offsets of all sites (16 bytes a site) ...
     uint64_t out_bytes = 0;
@@ -2364,84 +2510,24 @@ int merge_vcf_files(snpgpu_ctx *ctx, const char *const *paths, uint32_t n_files,
         const ssize_t w = pwrite(fd, head.data() + at, head.size() - at, (off_t)at);
         if (w <= 0) io_ok = false; else at += (size_t)w;
     }
-    const size_t chunk = (size_t)16 << 20;
     uint64_t n_pieces = 0;
-    for (const Round &r : rounds) n_pieces += (r.len + chunk - 1) / chunk;
-    uint32_t n_writers = snpgpu_writer_threads(16);
-    if (n_writers > n_pieces) n_writers = (uint32_t)n_pieces;
-    if (n_writers < 1) n_writers = 1;
-    stats->writer_threads = n_writers;
+    for (const Round &r : rounds) n_pieces += MergeWriter::pieces(r.len);
     rc = SNPGPU_OK;
+    stats->writer_threads = 1;
     if (n_pieces) {
-        const uint32_t n_ring = (uint32_t)(n_pieces < n_writers + 2 ? n_pieces : n_writers + 2);
-        rc = pool_ensure(ctx, chunk, n_ring, 0, 0, 0, 0);
+        MergeWriter wr(ctx, fd);
+        rc = wr.start(n_pieces, &stats->writer_threads);
         if (rc) { close(fd); return rc; }
-        snpgpu_stream_pool *p = ctx->pool;
-        const uint64_t R = p->staging.size() < n_ring ? p->staging.size() : n_ring;
-        struct Piece { uint64_t slot, off, len; };              // staging buffer, offset in the rows' text, bytes
-        std::mutex mu;
-        std::condition_variable cv;
-        std::vector<Piece> ready;                               // pieces copied back, waiting for a writer
-        std::vector<char> busy(R, 0);                           // staging buffer in use (being filled or written)
-        bool closing = false, failed = false;
-        std::vector<std::thread> writers;
-        auto writer_main = [&] {
-            for (;;) {
-                Piece pc;
-                {
-                    std::unique_lock<std::mutex> lk(mu);
-                    cv.wait(lk, [&] { return closing || !ready.empty(); });
-                    if (ready.empty()) return;
-                    pc = ready.back();
-                    ready.pop_back();
-                }
-                const char *h = (const char *)p->staging[pc.slot];
-                bool ok = true;
-                for (uint64_t at = 0; at < pc.len && ok;) {
-                    const ssize_t w = pwrite(fd, h + at, pc.len - at, (off_t)(head.size() + pc.off + at));
-                    if (w <= 0) ok = false; else at += (uint64_t)w;
-                }
-                {
-                    std::lock_guard<std::mutex> lk(mu);
-                    busy[pc.slot] = 0;
-                    if (!ok) failed = true;
-                }
-                cv.notify_all();
-            }
-        };
-        try {
-            for (uint32_t i = 0; i < n_writers; ++i) writers.emplace_back(writer_main);
-        } catch (const std::exception &) {
-            if (writers.empty()) { close(fd); return snpgpu_set_error(ctx, SNPGPU_E_NOMEM, "cannot start a writer thread"); }
-        }
-        hipError_t herr = hipSuccess;
         int krc = SNPGPU_OK;
-        uint64_t j = 0;
-        for (size_t r = 0; r < rounds.size() && herr == hipSuccess && krc == SNPGPU_OK; ++r) {
+        for (size_t r = 0; r < rounds.size() && wr.herr == hipSuccess && krc == SNPGPU_OK; ++r) {
             const Round &rd = rounds[r];                        // (the copies of the round before are complete: the buffer is free)
             krc = snpgpu_enqueue_merge_rows(ctx, 1, d_cells, d_table, n_files, d_uniq, n_sites, rd.lo, rd.hi, rd.base, d_names, d_name_off, d_filt, d_filt_off, d_row_len,
                                             d_row_end, d_scan, d_out, d_ctl);
-            for (uint64_t lo = 0; lo < rd.len && herr == hipSuccess && krc == SNPGPU_OK; lo += chunk, ++j) {
-                const uint64_t slot = j % R;
-                {
-                    std::unique_lock<std::mutex> lk(mu);
-                    cv.wait(lk, [&] { return !busy[slot]; });
-                    busy[slot] = 1;
-                }
-                const uint64_t len = rd.len - lo < chunk ? rd.len - lo : chunk;
-                herr = hipMemcpyAsync(p->staging[slot], d_out + lo, len, hipMemcpyDeviceToHost, st);
-                if (herr == hipSuccess) herr = hipStreamSynchronize(st);
-                if (herr != hipSuccess) break;
-                { std::lock_guard<std::mutex> lk(mu); ready.push_back(Piece{slot, rd.base + lo, len}); }
-                cv.notify_all();
-            }
+            if (krc == SNPGPU_OK) wr.copy(d_out, rd.len, head.size() + rd.base);
         }
-        { std::lock_guard<std::mutex> lk(mu); closing = true; }
-        cv.notify_all();
-        for (auto &t : writers) t.join();
+        if (!wr.finish()) io_ok = false;
         if (krc) rc = krc;
-        else if (herr != hipSuccess) rc = snpgpu_set_error(ctx, SNPGPU_E_HIP, "copying the merged text back failed: %s", hipGetErrorString(herr));
-        if (failed) io_ok = false;
+        else if (wr.herr != hipSuccess) rc = snpgpu_set_error(ctx, SNPGPU_E_HIP, "copying the merged text back failed: %s", hipGetErrorString(wr.herr));
     }
     if (close(fd) != 0) io_ok = false;
     if (rc) return rc;
@@ -2449,6 +2535,486 @@ int merge_vcf_files(snpgpu_ctx *ctx, const char *const *paths, uint32_t n_files,
     stats->bytes = head.size() + out_bytes;
     stats->seconds_write = seconds_since(t0);
     return SNPGPU_OK;
+}
+
+// ---- merge_vcfs in bounded memory -----------------------------------------------------------------------------------------------
+// The plan (include/snpgpu.h: snpgpu_merge_plan).  Everything is a figure of (n_files, n_sites, input bytes, budget, output buffer).
+constexpr uint64_t MERGE_MAX_RECORDS = 0x7FFFFFFEull;
+constexpr uint64_t MERGE_STREAM_BYTES = 3 * (((uint64_t)16 << 20) + 256) + 512;     // vcf_stream's piece buffers
+constexpr uint64_t MERGE_SMALL_BYTES = (16ull * MERGE_UNUSUAL_CAP) + (64 << 10);     // the list of the host's lines; control words, filters, contigs
+constexpr uint64_t MERGE_MIN_KEYS = 4096, MERGE_MAX_KEYS = 1ull << 30;
+constexpr uint32_t MERGE_EXTRA_BUF = 1024;                   // records of host-parsed lines go to their slots this many at a time
+constexpr uint64_t MERGE_NO_BUDGET = 1ull << 62;
+
+struct MergePlan {
+    snpgpu_merge_passes p;
+    uint64_t key_cap;               // keys a batch of the key pass holds
+    uint64_t out_buf;               // bytes of the output buffer of a site round
+};
+
+inline uint64_t merge_row_estimate(uint32_t n_files) { return 256 + 48ull * n_files; }
+inline uint64_t merge_min64(uint64_t a, uint64_t b) { return a < b ? a : b; }
+// the arrays of one sort + unique over m keys: keys, zeros, unique keys, offsets, carriers, the counts, the sort's workspace
+inline uint64_t merge_fold_bytes(uint64_t m) { return 28 * m + 4 + 16 + 6 * 256 + snpgpu_merge_sites_ws_bytes(m); }
+
+// the single pass by the dense bound; UINT64_MAX where it cannot run at any budget
+uint64_t merge_single_bytes(uint32_t n_files, uint64_t total_bytes, uint64_t out_cap) {
+    const uint64_t cap = total_bytes / 56 + MERGE_UNUSUAL_CAP + 64;
+    if (cap > MERGE_MAX_RECORDS) return UINT64_MAX;
+    const uint64_t sites = (cap + n_files - 1) / n_files;
+    return MERGE_STREAM_BYTES + MERGE_SMALL_BYTES + cap * sizeof(snpgpu_merge_cell) + merge_fold_bytes(cap) + 4 * cap /* the table */ + 16 * sites +
+           8 * (snpgpu_merge_rows_scan_words((uint32_t)sites) + 1) + merge_min64(out_cap, sites * merge_row_estimate(n_files)) + 16;
+}
+
+uint64_t merge_round_out_bytes(uint32_t n_files, uint64_t s, uint64_t out_cap) {
+    const uint64_t row = merge_row_estimate(n_files);
+    return s * row < out_cap ? s * row : (out_cap > row ? out_cap : row);
+}
+
+// the bounded form with rounds of s sites: the key pass (a batch and its fold into the union, the union before and after) and a
+// site round (the union, the slots, the row arrays, the output buffer), beside what both hold.  The key pass's arrays are freed
+// before the first round: the plan counts both all the same, so that every number of sites a round has a budget of its own
+uint64_t merge_bounded_bytes(uint32_t n_files, uint64_t n_sites, uint64_t key_cap, uint64_t s, uint64_t out_cap) {
+    const uint64_t key_pass = key_cap * (sizeof(snpgpu_merge_key) + 4) + merge_fold_bytes(key_cap + n_sites) + 16 * n_sites;
+    const uint64_t round = 8 * n_sites + s * n_files * (sizeof(snpgpu_merge_cell) + 4) + 16 * s + 8 * (snpgpu_merge_rows_scan_words((uint32_t)s) + 1) +
+                           merge_round_out_bytes(n_files, s, out_cap) + 16 + MERGE_EXTRA_BUF * sizeof(snpgpu_merge_cell);
+    return MERGE_STREAM_BYTES + MERGE_SMALL_BYTES + key_pass + round;
+}
+
+// SNPGPU_OK, or SNPGPU_E_NOMEM with pl->p.device_bytes = the bytes a round of one site needs
+int merge_plan(uint32_t n_files, uint64_t n_sites, uint64_t total_bytes, uint64_t budget, uint64_t out_cap, MergePlan *pl) {
+    *pl = MergePlan{};
+    if (!budget) budget = MERGE_NO_BUDGET;
+    if (budget > MERGE_NO_BUDGET) budget = MERGE_NO_BUDGET;
+    const uint64_t always = MERGE_STREAM_BYTES + MERGE_SMALL_BYTES;
+    uint64_t key_cap = (budget > always ? budget - always : 0) / 8 / 128;      // (about 128 bytes a key: its 24, and its share of the fold)
+    key_cap = key_cap < MERGE_MIN_KEYS ? MERGE_MIN_KEYS : key_cap > MERGE_MAX_KEYS ? MERGE_MAX_KEYS : key_cap;
+    pl->key_cap = key_cap;
+    const uint64_t sites = n_sites > 0xFFFFFFFEull ? 0xFFFFFFFEull : n_sites;
+    const uint64_t single = merge_single_bytes(n_files, total_bytes, out_cap);
+    const bool single_fits = single <= budget;
+    // the most sites a round holds
+    uint64_t lo = 0, hi = MERGE_MAX_RECORDS / n_files;         // (need(lo) fits, or lo is 0)
+    if (hi > 0xFFFFFFFEull) hi = 0xFFFFFFFEull;
+    while (lo < hi) {
+        const uint64_t mid = lo + (hi - lo + 1) / 2;
+        if (merge_bounded_bytes(n_files, sites, key_cap, mid, out_cap) <= budget) lo = mid; else hi = mid - 1;
+    }
+    if (single_fits) {
+        pl->p.input_passes = 1;
+        pl->p.site_rounds = 0;
+        pl->p.sites_per_round = lo > sites ? lo : sites;       // (the one round holds every site)
+        pl->p.device_bytes = single;
+        return SNPGPU_OK;
+    }
+    if (lo == 0) {
+        pl->p.device_bytes = merge_bounded_bytes(n_files, sites, MERGE_MIN_KEYS, 1, out_cap);
+        return SNPGPU_E_NOMEM;
+    }
+    if (single != UINT64_MAX && sites >= 2 && lo >= sites) lo = sites - 1;     // (the round of all sites is the single pass, and that does not fit)
+    pl->p.sites_per_round = lo;
+    pl->p.site_rounds = (uint32_t)((sites + lo - 1) / lo);
+    pl->p.input_passes = 1 + pl->p.site_rounds;
+    pl->p.device_bytes = merge_bounded_bytes(n_files, sites, key_cap, lo, out_cap);
+    pl->out_buf = merge_round_out_bytes(n_files, lo, out_cap);
+    return SNPGPU_OK;
+}
+
+// the merged file under a sibling name until it is whole: renamed at the end, removed on every other way out
+struct MergeTemp {
+    std::string path;
+    int fd = -1;
+    ~MergeTemp() {
+        if (fd >= 0) close(fd);
+        if (!path.empty()) (void)unlink(path.c_str());
+    }
+    bool create(const char *out_path) {
+        static std::atomic<uint32_t> serial{0};
+        for (int k = 0; k < 100 && fd < 0; ++k) {
+            char tail[64];
+            snprintf(tail, sizeof tail, ".snpgpu-merge.%ld.%u", (long)getpid(), serial.fetch_add(1));
+            path = std::string(out_path) + tail;
+            fd = open(path.c_str(), O_WRONLY | O_CREAT | O_EXCL | O_CLOEXEC, 0666);
+            if (fd < 0 && errno != EEXIST) break;
+        }
+        if (fd < 0) path.clear();
+        return fd >= 0;
+    }
+    bool commit(const char *out_path) {
+        const bool closed = close(fd) == 0;
+        fd = -1;
+        if (!closed || rename(path.c_str(), out_path) != 0) return false;
+        path.clear();
+        return true;
+    }
+};
+
+int merge_vcf_files_bounded(snpgpu_ctx *ctx, const char *const *paths, uint32_t n_files, const char *out_path, const char *own_lines, uint32_t own_len,
+                            uint64_t out_cap, uint64_t budget, const MergeInput &in, snpgpu_merge_stats *stats, snpgpu_merge_passes *passes) {
+    hipStream_t st = ctx->stream;
+    auto t0 = std::chrono::steady_clock::now();
+    const uint32_t n_filt = (uint32_t)in.filt_off.size() - 1;
+    MergePlan pl;
+    auto no_memory = [&](const MergePlan &q) {
+        *passes = q.p;
+        return snpgpu_set_error(ctx, SNPGPU_E_NOMEM, "merge_vcfs needs %llu bytes of device memory for its key pass and a round of one site of %u columns: the budget is %llu",
+                                (unsigned long long)q.p.device_bytes, n_files, (unsigned long long)budget);
+    };
+    if (merge_plan(n_files, 1, in.total_bytes, budget, out_cap, &pl)) return no_memory(pl);      // (before anything is read: no number of sites makes it fit)
+    const uint64_t key_cap = pl.key_cap;
+
+    MergeBuffers mem;
+    snpgpu_merge_key *d_krec = nullptr;
+    uint64_t *d_ctl = nullptr, *d_unusual = nullptr;
+    uint8_t *d_filt = nullptr;
+    uint32_t *d_filt_off = nullptr;
+    HIP_TRY(ctx, mem.get(&d_krec, key_cap * sizeof(snpgpu_merge_key)));
+    HIP_TRY(ctx, mem.get(&d_ctl, 64));
+    HIP_TRY(ctx, mem.get(&d_unusual, 16ull * MERGE_UNUSUAL_CAP));
+    HIP_TRY(ctx, mem.get(&d_filt, in.filt.size() + 16));
+    HIP_TRY(ctx, mem.get(&d_filt_off, 4 * in.filt_off.size()));
+    HIP_TRY(ctx, hipMemsetAsync(d_ctl, 0, 64, st));
+    if (!in.filt.empty()) HIP_TRY(ctx, hipMemcpyAsync(d_filt, in.filt.data(), in.filt.size(), hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(d_filt_off, in.filt_off.data(), 4 * in.filt_off.size(), hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+
+    // ---- the key pass: batches of keys, each sorted, uniqued and folded into the running union ----
+    std::unordered_map<uint64_t, uint32_t> id_of;               // CHROM hash -> the contig's number for now (order of appearance over the batches)
+    std::vector<uint64_t> hash_of, first_of;                    // per such number: its hash, the first (column << 40 | offset) that carries it
+    uint64_t *d_union = nullptr;                                // (number << 32) | POS, ascending
+    uint32_t n_union = 0;
+    std::vector<uint64_t> unusual;                              // (column, offset) of the lines left to the host, over all batches
+    uint64_t n_unusual = 0;
+    auto fold = [&](uint32_t n) -> int {                        // d_krec[0, n) into the union
+        if (!n) return (int)SNPGPU_OK;
+        const uint64_t m = (uint64_t)n + n_union;
+        if (m > 0x7FFFFFFFull) return snpgpu_set_error(ctx, SNPGPU_E_UNSUPPORTED, "too many sites for one merge");
+        MergeBuffers tmp;
+        uint64_t *d_keys = nullptr, *d_uniq = nullptr, *d_first = nullptr, *d_new = nullptr;
+        uint32_t *d_zeros = nullptr, *d_off = nullptr, *d_carrier = nullptr, *d_n = nullptr, *d_which = nullptr, *d_id = nullptr;
+        void *d_ws = nullptr;
+        HIP_TRY(ctx, tmp.get(&d_keys, 8 * m));
+        HIP_TRY(ctx, tmp.get(&d_uniq, 8 * m));
+        HIP_TRY(ctx, tmp.get(&d_zeros, 4 * m));
+        HIP_TRY(ctx, tmp.get(&d_off, 4 * (m + 1)));
+        HIP_TRY(ctx, tmp.get(&d_carrier, 4 * m));
+        HIP_TRY(ctx, tmp.get(&d_n, 16));
+        HIP_TRY(ctx, tmp.get(&d_which, 4ull * n));
+        HIP_TRY(ctx, tmp.get(&d_ws, snpgpu_merge_sites_ws_bytes(m)));
+        int rc = snpgpu_enqueue_merge_key_hashes(ctx, d_krec, n, d_keys, d_zeros);
+        if (rc) return rc;
+        rc = snpgpu_enqueue_merge_sites_ws(ctx, d_keys, d_zeros, n, d_uniq, d_off, d_carrier, d_n, d_ws);
+        if (rc) return rc;
+        uint32_t n_u[2] = {0, 0};
+        HIP_TRY(ctx, hipMemcpyAsync(n_u, d_n, 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, hipStreamSynchronize(st));
+        HIP_TRY(ctx, tmp.get(&d_first, 8ull * n_u[0]));
+        HIP_TRY(ctx, tmp.get(&d_id, 4ull * n_u[0]));
+        HIP_TRY(ctx, hipMemsetAsync(d_first, 0xFF, 8ull * n_u[0], st));
+        rc = snpgpu_enqueue_merge_key_first(ctx, d_krec, n, d_uniq, d_n, d_which, d_first);
+        if (rc) return rc;
+        std::vector<uint64_t> uniq(n_u[0]), first(n_u[0]);
+        std::vector<uint32_t> id(n_u[0]);
+        HIP_TRY(ctx, hipMemcpyAsync(uniq.data(), d_uniq, 8ull * n_u[0], hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, hipMemcpyAsync(first.data(), d_first, 8ull * n_u[0], hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, hipStreamSynchronize(st));
+        for (uint32_t k = 0; k < n_u[0]; ++k) {
+            const auto at = id_of.emplace(uniq[k], (uint32_t)hash_of.size());
+            if (at.second) { hash_of.push_back(uniq[k]); first_of.push_back(UINT64_MAX); }
+            id[k] = at.first->second;
+            if (first[k] < first_of[id[k]]) first_of[id[k]] = first[k];
+        }
+        HIP_TRY(ctx, hipMemcpyAsync(d_id, id.data(), 4ull * n_u[0], hipMemcpyHostToDevice, st));
+        rc = snpgpu_enqueue_merge_key_sites(ctx, d_krec, n, d_which, d_id, d_keys, d_zeros);
+        if (rc) return rc;
+        if (n_union) {
+            HIP_TRY(ctx, hipMemcpyAsync(d_keys + n, d_union, 8ull * n_union, hipMemcpyDeviceToDevice, st));
+            HIP_TRY(ctx, hipMemsetAsync(d_zeros + n, 0, 4ull * n_union, st));
+        }
+        rc = snpgpu_enqueue_merge_sites_ws(ctx, d_keys, d_zeros, (uint32_t)m, d_uniq, d_off, d_carrier, d_n, d_ws);
+        if (rc) return rc;
+        HIP_TRY(ctx, hipMemcpyAsync(n_u, d_n, 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, hipStreamSynchronize(st));                 // (id was copied from)
+        HIP_TRY(ctx, mem.get(&d_new, 8ull * n_u[0]));
+        HIP_TRY(ctx, hipMemcpyAsync(d_new, d_uniq, 8ull * n_u[0], hipMemcpyDeviceToDevice, st));
+        HIP_TRY(ctx, hipStreamSynchronize(st));
+        mem.release(d_union);
+        d_union = d_new;
+        n_union = n_u[0];
+        return (int)SNPGPU_OK;
+    };
+    uint64_t pending = 0;                                       // the most keys the launches since the last flush may have left
+    auto flush = [&]() -> int {                                 // the batch so far: its keys into the union, its other lines to the list
+        uint64_t ctl[8];
+        HIP_TRY(ctx, hipMemcpyAsync(ctl, d_ctl, 64, hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, hipStreamSynchronize(st));
+        pending = 0;
+        if (ctl[2] & 1) return snpgpu_set_error(ctx, SNPGPU_E_UNSUPPORTED, "more VCF records than the merge made room for");
+        n_unusual += ctl[1];
+        if (n_unusual > MERGE_UNUSUAL_CAP)
+            return snpgpu_set_error(ctx, SNPGPU_E_UNSUPPORTED, "%llu lines outside the kernel's grammar: more than the %u the host takes", (unsigned long long)n_unusual, MERGE_UNUSUAL_CAP);
+        if (ctl[1]) {
+            const size_t at = unusual.size();
+            unusual.resize(at + 2 * ctl[1]);
+            HIP_TRY(ctx, hipMemcpy(unusual.data() + at, d_unusual, 16 * ctl[1], hipMemcpyDeviceToHost));
+        }
+        const int rc = fold((uint32_t)ctl[0]);
+        if (rc) return rc;
+        HIP_TRY(ctx, hipMemsetAsync(d_ctl, 0, 16, st));
+        return (int)SNPGPU_OK;
+    };
+    std::vector<int32_t> file_rc(n_files, 0);
+    int rc = vcf_stream(ctx, paths, n_files, 0, file_rc.data(),
+        [&](void *) { return (int)SNPGPU_OK; },
+        [&](const uint8_t *d_buf, uint32_t len, uint32_t own_from, const Job &jb) {
+            // the piece in parts of whole tiles, each no longer than the batch has room for (a line of the grammar has 56 bytes or more)
+            for (uint32_t a = own_from; a < len;) {
+                const uint64_t room = key_cap - pending;
+                const uint64_t take = room > 2 ? (room - 2) * 56 / SNPGPU_VCF_TILE * SNPGPU_VCF_TILE : 0;
+                if (!take) {
+                    const int frc = flush();
+                    if (frc) return frc;
+                    continue;
+                }
+                const uint32_t b = len - a <= take ? len : a + (uint32_t)take;
+                const int krc = a == own_from
+                    ? snpgpu_enqueue_merge_lines(ctx, d_buf, b, own_from, jb.off, jb.file, d_krec, key_cap, nullptr, d_ctl, d_unusual, MERGE_UNUSUAL_CAP, d_filt, d_filt_off, n_filt)
+                    : snpgpu_enqueue_merge_lines(ctx, d_buf + a - SNPGPU_VCF_LOOK, b - a + SNPGPU_VCF_LOOK, SNPGPU_VCF_LOOK, jb.off + a - SNPGPU_VCF_LOOK, jb.file, d_krec,
+                                                 key_cap, nullptr, d_ctl, d_unusual, MERGE_UNUSUAL_CAP, d_filt, d_filt_off, n_filt);
+                if (krc) return krc;
+                pending += (b - a) / 56 + 2;
+                a = b;
+            }
+            return (int)SNPGPU_OK;
+        },
+        [&](void *) { return flush(); });
+    if (rc) return rc;
+    for (uint32_t f = 0; f < n_files; ++f)
+        if (file_rc[f]) { stats->bad_file = f; return snpgpu_set_error(ctx, SNPGPU_E_IO, "cannot open or read the VCF file %s", paths[f]); }
+    // the lines the kernel left alone: parsed once, here; their records stay on the host and go to their slots in their round
+    std::vector<snpgpu_merge_cell> extra;
+    rc = merge_host_lines(ctx, paths, unusual, in, stats, extra);
+    if (rc) return rc;
+    for (size_t at = 0; at < extra.size();) {
+        const size_t n = extra.size() - at < key_cap ? extra.size() - at : (size_t)key_cap;
+        std::vector<snpgpu_merge_key> rec(n);
+        for (size_t k = 0; k < n; ++k) rec[k] = snpgpu_merge_key{extra[at + k].key, extra[at + k].off, extra[at + k].pos, extra[at + k].column};
+        HIP_TRY(ctx, hipMemcpy(d_krec, rec.data(), n * sizeof(snpgpu_merge_key), hipMemcpyHostToDevice));
+        rc = fold((uint32_t)n);
+        if (rc) return rc;
+        at += n;
+    }
+    mem.release(d_krec);
+    mem.release(d_unusual);
+    d_krec = nullptr;
+    d_unusual = nullptr;
+
+    // the contigs in order of first appearance over the columns; the union under those numbers, sorted once more
+    const uint32_t n_sites = n_union, n_contigs = (uint32_t)hash_of.size();
+    std::vector<uint32_t> rank, name_off;
+    std::vector<std::string> contigs;
+    std::string all_names;
+    rc = merge_contig_order(ctx, paths, first_of, stats, rank, contigs, all_names, name_off);
+    if (rc) return rc;
+    std::vector<uint64_t> sites(n_sites);
+    uint64_t *d_sites = nullptr, *d_hashes = nullptr;
+    uint32_t *d_rank = nullptr, *d_name_off = nullptr;
+    uint8_t *d_names = nullptr;
+    if (n_sites) {
+        std::vector<uint32_t> by_hash(n_contigs), rank_by_hash(n_contigs);
+        std::vector<uint64_t> hashes(n_contigs);
+        for (uint32_t i = 0; i < n_contigs; ++i) by_hash[i] = i;
+        std::sort(by_hash.begin(), by_hash.end(), [&](uint32_t a, uint32_t b) { return hash_of[a] < hash_of[b]; });
+        for (uint32_t i = 0; i < n_contigs; ++i) { hashes[i] = hash_of[by_hash[i]]; rank_by_hash[i] = rank[by_hash[i]]; }
+        MergeBuffers tmp;
+        uint64_t *d_uniq = nullptr;
+        uint32_t *d_zeros = nullptr, *d_off = nullptr, *d_carrier = nullptr, *d_n = nullptr, *d_rank_of = nullptr;
+        void *d_ws = nullptr;
+        HIP_TRY(ctx, tmp.get(&d_uniq, 8ull * n_sites));
+        HIP_TRY(ctx, tmp.get(&d_zeros, 4ull * n_sites));
+        HIP_TRY(ctx, tmp.get(&d_off, 4ull * (n_sites + 1)));
+        HIP_TRY(ctx, tmp.get(&d_carrier, 4ull * n_sites));
+        HIP_TRY(ctx, tmp.get(&d_n, 16));
+        HIP_TRY(ctx, tmp.get(&d_rank_of, 4ull * n_contigs));
+        HIP_TRY(ctx, tmp.get(&d_ws, snpgpu_merge_sites_ws_bytes(n_sites)));
+        HIP_TRY(ctx, mem.get(&d_hashes, 8ull * n_contigs));
+        HIP_TRY(ctx, mem.get(&d_rank, 4ull * n_contigs));
+        HIP_TRY(ctx, mem.get(&d_names, all_names.size() + 16));
+        HIP_TRY(ctx, mem.get(&d_name_off, 4 * name_off.size()));
+        HIP_TRY(ctx, hipMemcpyAsync(d_rank_of, rank.data(), 4ull * n_contigs, hipMemcpyHostToDevice, st));
+        HIP_TRY(ctx, hipMemcpyAsync(d_hashes, hashes.data(), 8ull * n_contigs, hipMemcpyHostToDevice, st));
+        HIP_TRY(ctx, hipMemcpyAsync(d_rank, rank_by_hash.data(), 4ull * n_contigs, hipMemcpyHostToDevice, st));
+        HIP_TRY(ctx, hipMemcpyAsync(d_names, all_names.data(), all_names.size(), hipMemcpyHostToDevice, st));
+        HIP_TRY(ctx, hipMemcpyAsync(d_name_off, name_off.data(), 4 * name_off.size(), hipMemcpyHostToDevice, st));
+        rc = snpgpu_enqueue_merge_key_rank(ctx, d_union, n_sites, d_rank_of, d_zeros);
+        if (rc) return rc;
+        rc = snpgpu_enqueue_merge_sites_ws(ctx, d_union, d_zeros, n_sites, d_uniq, d_off, d_carrier, d_n, d_ws);
+        if (rc) return rc;
+        HIP_TRY(ctx, hipMemcpyAsync(d_union, d_uniq, 8ull * n_sites, hipMemcpyDeviceToDevice, st));
+        HIP_TRY(ctx, hipMemcpyAsync(sites.data(), d_uniq, 8ull * n_sites, hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, hipStreamSynchronize(st));                 // (the host vectors above were copied from)
+        d_sites = d_union;
+    }
+    stats->sites = n_sites;
+    for (snpgpu_merge_cell &c : extra) {                        // the host's records: their site's key and rank
+        c.key = ((uint64_t)rank[id_of[c.key]] << 32) | c.pos;
+        c.idx = (uint32_t)(std::lower_bound(sites.begin(), sites.end(), c.key) - sites.begin());
+    }
+    std::sort(extra.begin(), extra.end(), [](const snpgpu_merge_cell &a, const snpgpu_merge_cell &b) { return a.idx < b.idx; });
+
+    if (merge_plan(n_files, n_sites, in.total_bytes, budget, out_cap, &pl)) return no_memory(pl);
+    *passes = pl.p;
+    const uint32_t per_round = (uint32_t)pl.p.sites_per_round;
+    stats->seconds_parse = seconds_since(t0);
+    t0 = std::chrono::steady_clock::now();
+
+    // ---- the site rounds ----
+    const std::string head = merge_head_text(in, contigs, own_lines, own_len);
+    MergeTemp tmp_file;
+    if (!tmp_file.create(out_path)) return snpgpu_set_error(ctx, SNPGPU_E_IO, "cannot create %s", out_path);
+    bool io_ok = true;
+    for (size_t at = 0; at < head.size() && io_ok;) {
+        const ssize_t w = pwrite(tmp_file.fd, head.data() + at, head.size() - at, (off_t)at);
+        if (w <= 0) io_ok = false; else at += (size_t)w;
+    }
+    snpgpu_merge_cell *d_cells = nullptr, *d_extra = nullptr;
+    uint32_t *d_table = nullptr;
+    uint64_t *d_row_len = nullptr, *d_row_end = nullptr, *d_scan = nullptr;
+    uint8_t *d_out = nullptr;
+    uint64_t out_bytes = pl.out_buf, text_bytes = 0, n_rounds = 0;
+    if (n_sites) {
+        const uint64_t slots = (uint64_t)per_round * n_files;
+        HIP_TRY(ctx, mem.get(&d_cells, slots * sizeof(snpgpu_merge_cell)));
+        HIP_TRY(ctx, mem.get(&d_table, 4 * slots));
+        HIP_TRY(ctx, mem.get(&d_row_len, 8ull * per_round));
+        HIP_TRY(ctx, mem.get(&d_row_end, 8ull * per_round));
+        HIP_TRY(ctx, mem.get(&d_scan, 8 * (snpgpu_merge_rows_scan_words(per_round) + 1)));
+        HIP_TRY(ctx, mem.get(&d_out, out_bytes + 16));
+        if (!extra.empty()) HIP_TRY(ctx, mem.get(&d_extra, MERGE_EXTRA_BUF * sizeof(snpgpu_merge_cell)));
+    }
+    stats->seconds_merge = seconds_since(t0);
+    size_t next_extra = 0;
+    std::vector<uint64_t> row_end;
+    stats->writer_threads = 1;
+    for (uint32_t lo = 0; lo < n_sites && io_ok; lo += per_round) {
+        t0 = std::chrono::steady_clock::now();
+        const uint32_t hi = n_sites - lo < per_round ? n_sites : lo + per_round, n_local = hi - lo;
+        HIP_TRY(ctx, hipMemsetAsync(d_table, 0, 4ull * n_local * n_files, st));
+        HIP_TRY(ctx, hipMemsetAsync(d_ctl, 0, 64, st));
+        const snpgpu_merge_range range{d_hashes, d_rank, d_sites, n_contigs, n_sites, lo, hi, n_files, d_cells, d_table};
+        rc = vcf_stream(ctx, paths, n_files, 0, file_rc.data(),
+            [&](void *) { return (int)SNPGPU_OK; },
+            [&](const uint8_t *d_buf, uint32_t len, uint32_t own_from, const Job &jb) {
+                return snpgpu_enqueue_merge_lines(ctx, d_buf, len, own_from, jb.off, jb.file, nullptr, 0, &range, d_ctl, nullptr, 0, d_filt, d_filt_off, n_filt);
+            },
+            [&](void *) {
+                HIP_TRY(ctx, hipStreamSynchronize(st));
+                return (int)SNPGPU_OK;
+            });
+        if (rc) return rc;
+        for (uint32_t f = 0; f < n_files; ++f)
+            if (file_rc[f]) { stats->bad_file = f; return snpgpu_set_error(ctx, SNPGPU_E_IO, "cannot open or read the VCF file %s", paths[f]); }
+        while (next_extra < extra.size() && extra[next_extra].idx < hi) {
+            size_t n = 0;
+            while (n < MERGE_EXTRA_BUF && next_extra + n < extra.size() && extra[next_extra + n].idx < hi) ++n;
+            HIP_TRY(ctx, hipMemcpy(d_extra, extra.data() + next_extra, n * sizeof(snpgpu_merge_cell), hipMemcpyHostToDevice));
+            rc = snpgpu_enqueue_merge_place(ctx, d_extra, (uint32_t)n, lo, n_files, d_cells, d_table, d_ctl);
+            if (rc) return rc;
+            HIP_TRY(ctx, hipStreamSynchronize(st));
+            next_extra += n;
+        }
+        stats->seconds_parse += seconds_since(t0);
+        t0 = std::chrono::steady_clock::now();
+        // rows: the lengths and offsets of the round's sites, and the errors only the records show
+        rc = snpgpu_enqueue_merge_rows(ctx, 0, d_cells, d_table, n_files, d_sites + lo, n_local, 0, n_local, 0, d_names, d_name_off, d_filt, d_filt_off, d_row_len, d_row_end,
+                                       d_scan, nullptr, d_ctl);
+        if (rc) return rc;
+        uint64_t ctl[8];
+        row_end.resize(n_local);
+        HIP_TRY(ctx, hipMemcpyAsync(row_end.data(), d_row_end, 8ull * n_local, hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, hipMemcpyAsync(ctl, d_ctl, 64, hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, hipStreamSynchronize(st));
+        if (ctl[2] & 2) {
+            const uint32_t f = (uint32_t)(ctl[3] >> 40);
+            const uint64_t off = ctl[3] & ((1ull << 40) - 1);
+            stats->bad_file = f;
+            stats->bad_offset = off;
+            return snpgpu_set_error(ctx, SNPGPU_E_UNSUPPORTED, "%s: the position of the line at byte %llu comes twice in the file", paths[f], (unsigned long long)off);
+        }
+        if (ctl[2] & 4) return snpgpu_set_error(ctx, SNPGPU_E_UNSUPPORTED, "records of different REF at one position: outside the grammar the merge is pinned on");
+        stats->cells += ctl[0];
+        // the text in ranges of whole rows that the output buffer holds (a row longer than the buffer: the buffer grows to it)
+        struct Round { uint32_t lo, hi; uint64_t base, len; };
+        std::vector<Round> rounds;
+        uint64_t longest = 0, n_pieces = 0;
+        for (uint32_t a = 0; a < n_local;) {
+            const uint64_t base = a ? row_end[a - 1] : 0;
+            uint32_t b = (uint32_t)(std::upper_bound(row_end.begin() + a, row_end.end(), base + pl.out_buf) - row_end.begin());
+            if (b == a) b = a + 1;
+            rounds.push_back(Round{a, b, base, row_end[b - 1] - base});
+            if (rounds.back().len > longest) longest = rounds.back().len;
+            n_pieces += MergeWriter::pieces(rounds.back().len);
+            a = b;
+        }
+        if (longest > out_bytes) {
+            mem.release(d_out);
+            d_out = nullptr;
+            HIP_TRY(ctx, mem.get(&d_out, longest + 16));
+            out_bytes = longest;
+        }
+        n_rounds += rounds.size();
+        stats->seconds_merge += seconds_since(t0);
+        t0 = std::chrono::steady_clock::now();
+        {
+            MergeWriter wr(ctx, tmp_file.fd);
+            uint32_t n_writers = 1;
+            rc = wr.start(n_pieces, &n_writers);
+            if (rc) return rc;
+            if (n_writers > stats->writer_threads) stats->writer_threads = n_writers;
+            int krc = SNPGPU_OK;
+            for (size_t r = 0; r < rounds.size() && wr.herr == hipSuccess && krc == SNPGPU_OK; ++r) {
+                const Round &rd = rounds[r];
+                krc = snpgpu_enqueue_merge_rows(ctx, 1, d_cells, d_table, n_files, d_sites + lo, n_local, rd.lo, rd.hi, rd.base, d_names, d_name_off, d_filt, d_filt_off,
+                                                d_row_len, d_row_end, d_scan, d_out, d_ctl);
+                if (krc == SNPGPU_OK) wr.copy(d_out, rd.len, head.size() + text_bytes + rd.base);
+            }
+            if (!wr.finish()) io_ok = false;
+            if (krc) return krc;
+            if (wr.herr != hipSuccess) return snpgpu_set_error(ctx, SNPGPU_E_HIP, "copying the merged text back failed: %s", hipGetErrorString(wr.herr));
+        }
+        text_bytes += row_end[n_local - 1];
+        stats->seconds_write += seconds_since(t0);
+    }
+    stats->rounds = (uint32_t)(n_rounds < 0xFFFFFFFFu ? n_rounds : 0xFFFFFFFFu);
+    if (!io_ok || !tmp_file.commit(out_path)) return snpgpu_set_error(ctx, SNPGPU_E_IO, "cannot write %s", out_path);
+    stats->bytes = head.size() + text_bytes;
+    return SNPGPU_OK;
+}
+
+// the route by the plan: the single pass where it fits the budget, else the bounded form
+int merge_vcf_files_planned(snpgpu_ctx *ctx, const char *const *paths, uint32_t n_files, const char *out_path, const char *own_lines, uint32_t own_len,
+                            const snpgpu_merge_opts &opts, snpgpu_merge_stats *stats, snpgpu_merge_passes *passes) {
+    HIP_TRY(ctx, snpgpu_enter(ctx));
+    const uint64_t out_cap = 1ull << (opts.out_buffer_log2 ? opts.out_buffer_log2 : 26);
+    uint64_t budget = opts.device_bytes;
+    if (!budget) {
+        size_t free_bytes = 0, all_bytes = 0;
+        HIP_TRY(ctx, hipMemGetInfo(&free_bytes, &all_bytes));
+        const uint64_t reserve = free_bytes / 16 > (1ull << 30) ? free_bytes / 16 : 1ull << 30;
+        budget = free_bytes > reserve ? free_bytes - reserve : 1;
+    }
+    MergeInput in;
+    int rc = merge_read_input(ctx, paths, n_files, stats, in);
+    if (rc) return rc;
+    const uint64_t single = merge_single_bytes(n_files, in.total_bytes, out_cap);
+    if (single <= budget) {
+        *passes = snpgpu_merge_passes{1, 0, 0, single};
+        rc = merge_vcf_files(ctx, paths, n_files, out_path, own_lines, own_len, out_cap, stats, &in);
+        MergePlan pl;
+        if (rc == SNPGPU_OK && merge_plan(n_files, stats->sites, in.total_bytes, budget, out_cap, &pl) == SNPGPU_OK) *passes = pl.p;
+        return rc;
+    }
+    return merge_vcf_files_bounded(ctx, paths, n_files, out_path, own_lines, own_len, out_cap, budget, in, stats, passes);
 }
 
 }  // namespace
@@ -2482,6 +3048,36 @@ int snpgpu_merge_vcf_files(snpgpu_ctx *ctx, const char *const *paths, uint32_t n
     stats->bad_file = stats->bad_offset = UINT64_MAX;
     try {
         return merge_vcf_files(ctx, paths, n_files, out_path, own_lines, own_len, 1ull << (options ? options : 26), stats);
+    } catch (const std::exception &e) {                         // (no exception may leave through the C ABI)
+        return snpgpu_set_error(ctx, SNPGPU_E_NOMEM, "merge_vcf_files: %s", e.what());
+    }
+}
+
+int snpgpu_merge_plan(uint32_t n_files, uint64_t n_sites, uint64_t total_input_bytes, const snpgpu_merge_opts *opts, snpgpu_merge_passes *out) {
+    if (!out || n_files == 0 || n_files >= (1u << 24)) return SNPGPU_E_ARG;
+    const uint32_t log2 = opts ? opts->out_buffer_log2 : 0;
+    if (log2 && (log2 < 12 || log2 > 32)) return SNPGPU_E_ARG;
+    MergePlan pl;
+    const int rc = merge_plan(n_files, n_sites, total_input_bytes, opts ? opts->device_bytes : 0, 1ull << (log2 ? log2 : 26), &pl);
+    *out = pl.p;
+    return rc;
+}
+
+int snpgpu_merge_vcf_files_opts(snpgpu_ctx *ctx, const char *const *paths, uint32_t n_files, const char *out_path, const char *own_lines, uint32_t own_len,
+                                const snpgpu_merge_opts *opts, snpgpu_merge_stats *stats, snpgpu_merge_passes *passes) {
+    if (!ctx || !paths || !out_path || !stats || (own_len && !own_lines)) return snpgpu_set_error(ctx, SNPGPU_E_ARG, "null argument");
+    const snpgpu_merge_opts o = opts ? *opts : snpgpu_merge_opts{};
+    if (o.out_buffer_log2 && (o.out_buffer_log2 < 12 || o.out_buffer_log2 > 32))
+        return snpgpu_set_error(ctx, SNPGPU_E_ARG, "out_buffer_log2: 0, or 12 to 32, the log2 of the output buffer's bytes");
+    if (n_files == 0 || n_files >= (1u << 24)) return snpgpu_set_error(ctx, SNPGPU_E_ARG, "the merge takes 1 to 2^24 - 1 files");
+    *stats = snpgpu_merge_stats{};
+    stats->columns = n_files;
+    stats->bad_file = stats->bad_offset = UINT64_MAX;
+    snpgpu_merge_passes mine{};
+    try {
+        const int rc = merge_vcf_files_planned(ctx, paths, n_files, out_path, own_lines, own_len, o, stats, &mine);
+        if (passes) *passes = mine;
+        return rc;
     } catch (const std::exception &e) {                         // (no exception may leave through the C ABI)
         return snpgpu_set_error(ctx, SNPGPU_E_NOMEM, "merge_vcf_files: %s", e.what());
     }

@@ -10,6 +10,8 @@
 //           index in that column's ALT) that carries it, symbols ordered by that pair —, the union of the filters likewise, NS,
 //           and the byte length of the row (columns beyond 64 are a loop of the same wave) ...
 //   write   ... and, after a prefix sum over the row lengths, the same walk again writing the text at each row's offset.
+// Where the records would not fit the device the merge runs in bounded memory (snpgpu_merge_vcf_files_opts): the `lines` kernel
+// below is the parse kernel's walk once for the keys of all lines and once per range of sites for that range's records.
 //
 // The grammar (the pipeline's own writer, vcf_rows.hip): ten TAB-separated columns; POS a count; ID and QUAL '.'; REF one byte;
 // ALT '.' or up to 8 distinct one-byte symbols; FILTER equal to FT; INFO NS=<n>; FORMAT GT:SDP:RD:AD:RDF:RDR:ADF:ADR:FT; GT '.'
@@ -237,6 +239,126 @@ __global__ void merge_scatter_kernel(const snpgpu_merge_cell *cells, uint64_t n,
     }
 }
 
+// ---- the bounded route (stream.hip: merge_vcf_files_bounded): a key pass over all files, then one pass per range of sites -----
+// CHROM hash and POS of the line p[s, e) as snpgpu_merge_parse_line (strict) derives them; false where it fails on them
+__device__ __forceinline__ bool mg_line_key(const uint8_t *p, uint32_t s, uint32_t e, uint64_t *hash, uint32_t *pos) {
+    uint32_t t0 = s;
+    uint64_t h = 1469598103934665603ull;
+    for (; t0 < e && p[t0] != '\t'; ++t0) h = (h ^ p[t0]) * 1099511628211ull;
+    if (t0 == s || t0 == e) return false;
+    uint32_t t1 = t0 + 1;
+    while (t1 < e && p[t1] != '\t') ++t1;
+    *hash = h;
+    return t1 < e && mg_num(p, t0 + 1, t1, 9, pos);
+}
+
+// a record of the site range into its slot [site - lo][column]; a slot taken is a position that comes twice in one file
+// (ctl[2] bit 1, ctl[3] = column << 40 | offset of a line of it)
+__device__ __forceinline__ void mg_place(const snpgpu_merge_cell &c, uint64_t slot, snpgpu_merge_cell *cells, uint32_t *table, unsigned long long *ctl) {
+    if (atomicCAS(&table[slot], 0u, (uint32_t)slot + 1) == 0) {
+        cells[slot] = c;
+        atomicAdd(&ctl[0], 1ull);
+    } else {
+        atomicOr(&ctl[2], 2ull);
+        ctl[3] = ((unsigned long long)c.column << 40) | (c.off & ((1ull << 40) - 1));
+    }
+}
+
+// The walk of merge_parse_kernel over the same bytes with the same ownership rule.  kKeys: every line inside the grammar leaves its
+// snpgpu_merge_key, every other line its (column, offset) for the host, as there.  !kKeys: a line whose (contig, POS) ranks inside
+// [rg.lo, rg.hi) of the sorted site keys becomes the record of its slot; the lines of the host are the host's (it holds their
+// records from the key pass), so nothing is reported.
+template <bool kKeys>
+__global__ void __launch_bounds__(MG_THREADS) merge_lines_kernel(const uint8_t *__restrict__ buf, uint32_t n, uint32_t own_from, uint64_t file_off, uint32_t column,
+                                                                  snpgpu_merge_key *__restrict__ keys, uint64_t key_cap, const snpgpu_merge_range rg,
+                                                                  unsigned long long *__restrict__ ctl, unsigned long long *__restrict__ unusual, uint32_t unusual_cap,
+                                                                  const uint8_t *__restrict__ filt, const uint32_t *__restrict__ filt_off, uint32_t n_filt) {
+    __shared__ u32x4 tile4[(MG_LOOK + MG_TILE) / 16];
+    const uint32_t t0 = own_from + blockIdx.x * MG_TILE;
+    const uint32_t t1 = n - t0 < MG_TILE ? n : t0 + MG_TILE;
+    const uint32_t l0 = t0 >= MG_LOOK ? t0 - MG_LOOK : 0;
+    for (uint32_t i = threadIdx.x; i < (MG_LOOK + MG_TILE) / 16; i += MG_THREADS)
+        if (l0 + i * 16 < t1) tile4[i] = __builtin_nontemporal_load((const u32x4 *)(buf + l0) + i);
+    __syncthreads();
+    const uint8_t *lds = (const uint8_t *)tile4;                 // lds[i] is buf[l0 + i]
+    const uint32_t lane0 = t0 + threadIdx.x * MG_LANE_BYTES;
+    for (uint32_t w = 0; w < MG_LANE_BYTES / 16 && lane0 + w * 16 < t1; ++w) {
+        const u32x4 v = tile4[(lane0 + w * 16 - l0) / 16];
+        const uint32_t words[4] = {v.x, v.y, v.z, v.w};
+        for (uint32_t k = 0; k < 16; ++k) {
+            if (((words[k / 4] >> (8 * (k % 4))) & 0xFF) != '\n') continue;
+            const uint32_t p = lane0 + w * 16 + k;
+            if (p >= t1) continue;
+            const uint32_t lim = p >= MG_LOOK ? p - MG_LOOK + 1 : 0;
+            uint32_t s = p;
+            while (s > lim && lds[s - 1 - l0] != '\n') --s;
+            const bool found = s == 0 ? file_off == 0 : lds[s - 1 - l0] == '\n';
+            uint32_t e = p;
+            if (e > s && lds[e - 1 - l0] == '\r') --e;
+            if (found && (e == s || lds[s - l0] == '#')) continue;
+            snpgpu_merge_cell c;
+            if (kKeys) {
+                const uint64_t where = found ? file_off + s : (file_off + p) | (1ull << 63);
+                if (found && snpgpu_merge_parse_line(lds, s - l0, e - l0, filt, filt_off, n_filt, true, &c)) {
+                    const unsigned long long at = atomicAdd(&ctl[0], 1ull);
+                    if (at < key_cap) keys[at] = snpgpu_merge_key{c.key, where, c.pos, column};
+                    else atomicOr(&ctl[2], 1ull);
+                } else {
+                    const unsigned long long at = atomicAdd(&ctl[1], 1ull);
+                    if (at < unusual_cap) { unusual[2 * at] = column; unusual[2 * at + 1] = where; }
+                }
+            } else {
+                uint64_t hash;
+                uint32_t pos;
+                if (!found || !mg_line_key(lds, s - l0, e - l0, &hash, &pos)) continue;
+                const uint32_t contig = lower_bound64(rg.hashes, rg.n_contigs, hash);
+                if (contig == rg.n_contigs || rg.hashes[contig] != hash) continue;
+                const uint64_t key = ((uint64_t)rg.rank[contig] << 32) | pos;
+                const uint32_t site = lower_bound64(rg.sites, rg.n_sites, key);
+                if (site < rg.lo || site >= rg.hi || rg.sites[site] != key) continue;
+                if (!snpgpu_merge_parse_line(lds, s - l0, e - l0, filt, filt_off, n_filt, true, &c)) continue;
+                c.key = key;
+                c.idx = site;
+                c.off = file_off + s;
+                c.column = column;
+                mg_place(c, (uint64_t)(site - rg.lo) * rg.n_col + column, rg.cells, rg.table, ctl);
+            }
+        }
+    }
+}
+
+__global__ void merge_key_hashes_kernel(const snpgpu_merge_key *rec, uint32_t n, uint64_t *keys, uint32_t *zeros) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) { keys[i] = rec[i].hash; zeros[i] = 0; }
+}
+
+// which of the batch's n_u distinct CHROM hashes a key has, and the first (column, offset) that carries each
+__global__ void merge_key_first_kernel(const snpgpu_merge_key *rec, uint32_t n, const uint64_t *uniq, const uint32_t *n_u, uint32_t *which, unsigned long long *first) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t at = lower_bound64(uniq, n_u[0], rec[i].hash);
+    which[i] = at;
+    atomicMin(&first[at], ((unsigned long long)rec[i].column << 40) | (rec[i].off & ((1ull << 40) - 1)));
+}
+
+// keys[i] = (id[which[i]] << 32) | POS: id is the contig's number for now (order of appearance over the batches)
+__global__ void merge_key_sites_kernel(const snpgpu_merge_key *rec, uint32_t n, const uint32_t *which, const uint32_t *id, uint64_t *keys, uint32_t *zeros) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) { keys[i] = ((uint64_t)id[which[i]] << 32) | rec[i].pos; zeros[i] = 0; }
+}
+
+// the site union once every batch is in: the contig's number for now becomes its rank in order of first appearance over the columns
+__global__ void merge_key_rank_kernel(uint64_t *keys, uint32_t n, const uint32_t *rank, uint32_t *zeros) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) { keys[i] = ((uint64_t)rank[keys[i] >> 32] << 32) | (uint32_t)keys[i]; zeros[i] = 0; }
+}
+
+// the records the host parsed (idx = the site's rank, key and column set) into their slots of the range that starts at site lo
+__global__ void merge_place_kernel(const snpgpu_merge_cell *extra, uint32_t n, uint32_t lo, uint32_t n_col, snpgpu_merge_cell *cells, uint32_t *table, unsigned long long *ctl) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) mg_place(extra[i], (uint64_t)(extra[i].idx - lo) * n_col + extra[i].column, cells, table, ctl);
+}
+
 template <bool kWrite>
 struct Emit {
     uint8_t *p;
@@ -459,6 +581,61 @@ int snpgpu_enqueue_merge_site_keys(snpgpu_ctx *ctx, snpgpu_merge_cell *d_cells, 
 int snpgpu_enqueue_merge_scatter(snpgpu_ctx *ctx, const snpgpu_merge_cell *d_cells, uint64_t n, const uint64_t *d_sites, const uint32_t *d_n_sites, uint32_t n_col,
                                  uint32_t *d_table, uint64_t *d_ctl) {
     if (n) merge_scatter_kernel<<<nblk(n), 256, 0, ctx->stream>>>(d_cells, n, d_sites, d_n_sites, n_col, d_table, (unsigned long long *)d_ctl);
+    HIP_TRY(ctx, hipGetLastError());
+    return SNPGPU_OK;
+}
+
+// The bounded route.  keys != 0: the key pass (d_keys[key_cap], unusual as in snpgpu_enqueue_merge_parse); else the pass of a site range.
+int snpgpu_enqueue_merge_lines(snpgpu_ctx *ctx, const uint8_t *d_buf, uint32_t n, uint32_t own_from, uint64_t file_off, uint32_t column, snpgpu_merge_key *d_keys,
+                               uint64_t key_cap, const snpgpu_merge_range *range, uint64_t *d_ctl, uint64_t *d_unusual, uint32_t unusual_cap, const uint8_t *d_filt,
+                               const uint32_t *d_filt_off, uint32_t n_filt) {
+    if (((uintptr_t)d_buf & 15) || (own_from != 0 && own_from != MG_LOOK) || (own_from == 0) != (file_off == 0))
+        return snpgpu_set_error(ctx, SNPGPU_E_ARG, "vcf merge: a piece starts on a 16-byte boundary, with the look-back of the piece before it or at the start of the file");
+    if (!d_keys == !range) return snpgpu_set_error(ctx, SNPGPU_E_ARG, "vcf merge: either the key pass or a site range");
+    if (range && (range->lo >= range->hi || range->hi > range->n_sites)) return snpgpu_set_error(ctx, SNPGPU_E_ARG, "vcf merge: an empty or outlying range of sites");
+    if (n <= own_from) return SNPGPU_OK;
+    const uint32_t blocks = (n - own_from + MG_TILE - 1) / MG_TILE;
+    hipEvent_t ta = snpgpu_time_begin(ctx);
+    if (d_keys)
+        hipLaunchKernelGGL(merge_lines_kernel<true>, dim3(blocks), dim3(MG_THREADS), 0, ctx->stream, d_buf, n, own_from, file_off, column, d_keys, key_cap,
+                           snpgpu_merge_range{}, (unsigned long long *)d_ctl, (unsigned long long *)d_unusual, unusual_cap, d_filt, d_filt_off, n_filt);
+    else
+        hipLaunchKernelGGL(merge_lines_kernel<false>, dim3(blocks), dim3(MG_THREADS), 0, ctx->stream, d_buf, n, own_from, file_off, column, (snpgpu_merge_key *)nullptr,
+                           (uint64_t)0, *range, (unsigned long long *)d_ctl, (unsigned long long *)nullptr, 0u, d_filt, d_filt_off, n_filt);
+    snpgpu_time_end(ctx, SNPGPU_K_VCF_MERGE, ta);
+    HIP_TRY(ctx, hipGetLastError());
+    return SNPGPU_OK;
+}
+
+int snpgpu_enqueue_merge_key_hashes(snpgpu_ctx *ctx, const snpgpu_merge_key *d_rec, uint32_t n, uint64_t *d_keys, uint32_t *d_zeros) {
+    if (n) merge_key_hashes_kernel<<<nblk(n), 256, 0, ctx->stream>>>(d_rec, n, d_keys, d_zeros);
+    HIP_TRY(ctx, hipGetLastError());
+    return SNPGPU_OK;
+}
+
+int snpgpu_enqueue_merge_key_first(snpgpu_ctx *ctx, const snpgpu_merge_key *d_rec, uint32_t n, const uint64_t *d_uniq, const uint32_t *d_n_uniq, uint32_t *d_which,
+                                   uint64_t *d_first) {
+    if (n) merge_key_first_kernel<<<nblk(n), 256, 0, ctx->stream>>>(d_rec, n, d_uniq, d_n_uniq, d_which, (unsigned long long *)d_first);
+    HIP_TRY(ctx, hipGetLastError());
+    return SNPGPU_OK;
+}
+
+int snpgpu_enqueue_merge_key_sites(snpgpu_ctx *ctx, const snpgpu_merge_key *d_rec, uint32_t n, const uint32_t *d_which, const uint32_t *d_id, uint64_t *d_keys,
+                                   uint32_t *d_zeros) {
+    if (n) merge_key_sites_kernel<<<nblk(n), 256, 0, ctx->stream>>>(d_rec, n, d_which, d_id, d_keys, d_zeros);
+    HIP_TRY(ctx, hipGetLastError());
+    return SNPGPU_OK;
+}
+
+int snpgpu_enqueue_merge_key_rank(snpgpu_ctx *ctx, uint64_t *d_keys, uint32_t n, const uint32_t *d_rank, uint32_t *d_zeros) {
+    if (n) merge_key_rank_kernel<<<nblk(n), 256, 0, ctx->stream>>>(d_keys, n, d_rank, d_zeros);
+    HIP_TRY(ctx, hipGetLastError());
+    return SNPGPU_OK;
+}
+
+int snpgpu_enqueue_merge_place(snpgpu_ctx *ctx, const snpgpu_merge_cell *d_extra, uint32_t n, uint32_t lo, uint32_t n_col, snpgpu_merge_cell *d_cells, uint32_t *d_table,
+                               uint64_t *d_ctl) {
+    if (n) merge_place_kernel<<<nblk(n), 256, 0, ctx->stream>>>(d_extra, n, lo, n_col, d_cells, d_table, (unsigned long long *)d_ctl);
     HIP_TRY(ctx, hipGetLastError());
     return SNPGPU_OK;
 }

@@ -693,20 +693,43 @@ class Device(object):
                 out.append((int(counts[i, 0]), int(counts[i, 1]), int(counts[i, 2]), [int(x) for x in offsets[i, :k]], int(status[i])))
         return out
 
-    def merge_vcf_files(self, paths, out_path, own_lines=b"", out_buffer_log2=0):
-        """The multi-sample VCF file of `paths` (column order) written to out_path by the library (snpgpu_merge_vcf_files);
+    def merge_vcf_files(self, paths, out_path, own_lines=b"", out_buffer_log2=0, device_bytes=0):
+        """The multi-sample VCF file of `paths` (column order) written to out_path by the library (snpgpu_merge_vcf_files_opts);
         own_lines: header lines (bytes, each with its LF) that go in front of #CHROM; out_buffer_log2: 0 for the library's 64 MiB
-        output buffer, or 12 to 32 (the text leaves the device in rounds of sites that fit it).  Returns the statistics as a dict.  Raises
-        IOError for a file that cannot be read or written, SnpGpuError (E_UNSUPPORTED) for a line or a site outside the grammar the merge
-        is pinned on (the message names the file and the byte offset)."""
+        output buffer, or 12 to 32 (the text leaves the device in rounds of sites that fit it); device_bytes: the budget for what the
+        merge allocates on the device (0: the free memory less a reserve) — where the single pass does not fit it the merge runs in
+        bounded memory, a key pass and rounds of sites.  Returns the statistics as a dict, the plan that ran merged in (input_passes,
+        site_rounds, sites_per_round, device_bytes: see merge_plan).  Raises IOError for a file that cannot be read or written,
+        SnpGpuError (E_UNSUPPORTED) for a line or a site outside the grammar the merge is pinned on (the message names the file and the
+        byte offset), SnpGpuError (E_NOMEM) for a budget below a round of one site."""
         n = len(paths)
         arr = (C.c_char_p * n)(*[os.fsencode(p) for p in paths])
         stats = L.MergeStats()
-        rc = self.lib.snpgpu_merge_vcf_files(self.ctx, arr, n, os.fsencode(out_path), own_lines, len(own_lines), int(out_buffer_log2), C.byref(stats))
+        opts = L.MergeOpts(out_buffer_log2=int(out_buffer_log2), device_bytes=int(device_bytes))
+        passes = L.MergePasses()
+        rc = self.lib.snpgpu_merge_vcf_files_opts(self.ctx, arr, n, os.fsencode(out_path), own_lines, len(own_lines), C.byref(opts), C.byref(stats), C.byref(passes))
         if rc == L.E_IO:
             raise IOError(self.lib.snpgpu_last_error(self.ctx).decode("utf-8", "replace"))
         self._check(rc)
-        return {name: getattr(stats, name) for name, _ in L.MergeStats._fields_}
+        out = {name: getattr(stats, name) for name, _ in L.MergeStats._fields_}
+        out.update({name: getattr(passes, name) for name, _ in L.MergePasses._fields_})
+        return out
+
+    @staticmethod
+    def merge_plan(n_files, n_sites, total_input_bytes, device_bytes=0, out_buffer_log2=0):
+        """How merge_vcf_files runs for n_files files with n_sites sites and total_input_bytes bytes of input under a budget of
+        device_bytes (0: no budget) — snpgpu_merge_plan, host code that needs no device: {input_passes (1: the single pass, else
+        1 + site_rounds readings of the input), site_rounds, sites_per_round, device_bytes (what the plan holds)}.  Raises SnpGpuError
+        (E_NOMEM) for a budget below the key pass and a round of one site; its message names the bytes needed."""
+        opts = L.MergeOpts(out_buffer_log2=int(out_buffer_log2), device_bytes=int(device_bytes))
+        passes = L.MergePasses()
+        rc = L.load().snpgpu_merge_plan(int(n_files), int(n_sites), int(total_input_bytes), C.byref(opts), C.byref(passes))
+        if rc == L.E_NOMEM:
+            raise SnpGpuError(rc, "merge_vcfs needs %d bytes of device memory for its key pass and a round of one site of %d columns: the budget is %d"
+                              % (passes.device_bytes, n_files, device_bytes))
+        if rc != 0:
+            raise SnpGpuError(rc, "merge_plan: 1 to 2^24 - 1 files, out_buffer_log2 0 or 12 to 32")
+        return {name: getattr(passes, name) for name, _ in L.MergePasses._fields_}
 
     def raise_file_status(self, path, rc, res, check=True, wanted=None):
         """Raise for one file of call_consensus_files the way call_consensus does for its single pileup (wanted: see site_error)."""

@@ -1314,6 +1314,9 @@ def hot_path_batch(args):
     utils.print_arguments(args)
     if getattr(args, "mergeVcfs", False) and args.noConsensusVcf:
         utils.global_error("Error: --mergeVcfs merges the consensus.vcf files of the job: it cannot be combined with --noConsensusVcf.")
+    if getattr(args, "mergeVcfs", False):
+        from . import merge_vcfs as mv
+        mv.merge_device_bytes(getattr(args, "mergeDeviceBytes", None))      # (a value that is no count ends the job before it starts)
     comm = _Comm()
     job = _Job(args, comm)
     if not args.forceFlag and job.is_fresh():
@@ -1369,7 +1372,8 @@ def _merge_vcfs_stage(job):
     for listing, name, out in ((job.filtered1, "consensus.vcf", "snpma.vcf"), (job.filtered2, "consensus_preserved.vcf", "snpma_preserved.vcf")):
         with open(listing, "r") as f:
             dirs = [d for d in (line.rstrip() for line in f) if d]
-        routes[out] = mv.merge_sample_dirs(dirs, name, os.path.join(job.work_dir, out), force=True, merger=getattr(job.args, "vcfMerger", None))
+        routes[out] = mv.merge_sample_dirs(dirs, name, os.path.join(job.work_dir, out), force=True, merger=getattr(job.args, "vcfMerger", None),
+                                           device_bytes=getattr(job.args, "mergeDeviceBytes", None))
     job.timings["merge_vcfs"] = time.perf_counter() - t0
     if hot_path_batch.last_stats is not None:
         hot_path_batch.last_stats["merge_vcfs"] = routes
@@ -1428,6 +1432,7 @@ def add_arguments(sub):
     sub.add_argument("--mergedMetricsFile", dest="mergedMetricsFile", type=str, default=None, metavar="PATH", help="With --collectMetrics: the merged metrics table (default: metrics.tsv in the work directory)")
     sub.add_argument("--mergeVcfs", dest="mergeVcfs", action="store_true", help="At the end of the job write snpma.vcf and snpma_preserved.vcf (merge_vcfs) into the work directory, from the consensus.vcf / consensus_preserved.vcf files the job has just written; not with --noConsensusVcf")
     sub.add_argument("--vcfMerger", dest="vcfMerger", type=str, default=None, choices=("bcftools", "device", "auto"), metavar="MODE", help="With --mergeVcfs: who merges, as merge_vcfs --vcfMerger (default: $SNPGPU_VCF_MERGER, else auto)")
+    sub.add_argument("--mergeDeviceBytes", dest="mergeDeviceBytes", type=str, default=argparse.SUPPRESS, metavar="INT", help="With --mergeVcfs: the device memory the device route may allocate, as merge_vcfs --mergeDeviceBytes (default: $SNPGPU_MERGE_DEVICE_BYTES, else 0 = what is free, less a reserve)")
     sub.add_argument("--noConsensusVcf", dest="noConsensusVcf", action="store_true", help="Do not write consensus.vcf / consensus_preserved.vcf")
     sub.add_argument("--residentBytes", dest="residentBytes", type=int, default=0, metavar="INT", help="Device memory for resident pileups (0 = what is free, less 24 GiB); files past it are streamed twice in site calling mode device only: in modes existing and varscan --pileupRoute auto streams every pileup once instead")
     sub.add_argument("--pileupRoute", dest="pileupRoute", type=str, default=None, choices=PILEUP_ROUTES, metavar="ROUTE",

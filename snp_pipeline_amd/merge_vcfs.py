@@ -18,6 +18,7 @@ ships.  Outside that grammar nothing pins the rule, and a line outside it ends t
 """
 from __future__ import print_function
 
+import argparse
 import os
 import re
 import resource
@@ -236,9 +237,13 @@ def column_order(sample_dirs):
     return [by_name[k] for k in sorted(by_name, key=lambda s: s.encode("utf-8", "surrogateescape"))]
 
 
-def merge_files_device(dev, paths, out_path, command=""):
-    """The library's merge of `paths` (column order) into out_path.  Returns its statistics (device.MergeStats as a dict)."""
-    return dev.merge_vcf_files(paths, out_path, b"\n".join(own_header_lines(command)) + b"\n")
+def merge_files_device(dev, paths, out_path, command="", device_bytes=0):
+    """The library's merge of `paths` (column order) into out_path.  Returns its statistics (device.MergeStats as a dict).
+    device_bytes: the budget of --mergeDeviceBytes, handed on only when it is set."""
+    own = b"\n".join(own_header_lines(command)) + b"\n"
+    if device_bytes:
+        return dev.merge_vcf_files(paths, out_path, own, device_bytes=device_bytes)
+    return dev.merge_vcf_files(paths, out_path, own)
 
 
 # ---- the routes --------------------------------------------------------------------------------------------------------------
@@ -253,6 +258,16 @@ def choose_merger(asked=None):
     if mode == "auto":
         mode = "bcftools" if have_tools() else "device"
     return mode
+
+
+def merge_device_bytes(asked=None):
+    """--mergeDeviceBytes / SNPGPU_MERGE_DEVICE_BYTES: the device memory the device route may allocate (0: what is free, less a
+    reserve).  Where the records of all files do not fit it the merge runs in bounded memory, a key pass and rounds of sites."""
+    value = asked if asked is not None else (os.environ.get("SNPGPU_MERGE_DEVICE_BYTES") or "0")
+    text = str(value).strip()
+    if not (text.isascii() and text.isdigit()):
+        utils.global_error("Error: --mergeDeviceBytes / SNPGPU_MERGE_DEVICE_BYTES must be a non-negative integer, not %s." % value)
+    return int(text)
 
 
 def _run(command_line, stdout):
@@ -301,9 +316,10 @@ def check_device_params():
                            "'%s' does; use --vcfMerger bcftools for other parameters." % (params, DEFAULT_PARAMS))
 
 
-def merge_sample_dirs(sample_dirs, vcf_name, merged, force=False, merger=None, dev=None):
+def merge_sample_dirs(sample_dirs, vcf_name, merged, force=False, merger=None, dev=None, device_bytes=None):
     """The step for a list of sample directories (merge_vcfs.py:60-139).  Returns the route that ran: 'fresh', 'copy',
-    'bcftools' or 'device'."""
+    'bcftools' or 'device'.  device_bytes: --mergeDeviceBytes as given (None: the environment's, else 0)."""
+    budget = merge_device_bytes(device_bytes)
     vcf_files = [os.path.join(d, vcf_name) for d in sample_dirs]
     good = []
     for path in vcf_files:
@@ -328,6 +344,8 @@ def merge_sample_dirs(sample_dirs, vcf_name, merged, force=False, merger=None, d
         return "copy"
     if mode == "bcftools":
         verbose_print("# merge_vcfs route: bcftools (the reference's commands)")
+        if budget:
+            verbose_print("# --mergeDeviceBytes %d is ignored: it bounds the device route only" % budget)
         merge_bcftools(sample_dirs, good, vcf_name, merged)
         return "bcftools"
     check_device_params()
@@ -338,7 +356,7 @@ def merge_sample_dirs(sample_dirs, vcf_name, merged, force=False, merger=None, d
         from . import device as devmod
         dev = devmod.Device(int(os.environ.get("SNPGPU_DEVICE", os.environ.get("LOCAL_RANK", "0"))))
     try:
-        stats = merge_files_device(dev, paths, merged, "merge -o %s %s %s" % (merged, DEFAULT_PARAMS, " ".join(paths)))
+        stats = merge_files_device(dev, paths, merged, "merge -o %s %s %s" % (merged, DEFAULT_PARAMS, " ".join(paths)), budget)
     except Exception as err:                                  # noqa: B902 — a line outside the grammar, an unreadable file
         if os.path.exists(merged):
             os.unlink(merged)
@@ -349,6 +367,10 @@ def merge_sample_dirs(sample_dirs, vcf_name, merged, force=False, merger=None, d
     verbose_print("# %d columns, %d sites, %d records (%d of them parsed on the host), %d bytes in %d rounds; parse %.3f s, merge %.3f s, write %.3f s" %
                   (stats["columns"], stats["sites"], stats["cells"], stats["host_lines"], stats["bytes"], stats["rounds"],
                    stats["seconds_parse"], stats["seconds_merge"], stats["seconds_write"]))
+    if stats.get("input_passes", 1) > 1:
+        verbose_print("# device route, %d site rounds of %d sites, %d readings of the input" % (stats["site_rounds"], stats["sites_per_round"], stats["input_passes"]))
+    else:
+        verbose_print("# device route, single pass, 1 reading of the input")
     merge_sample_dirs.last_stats = stats
     return "device"
 
@@ -364,6 +386,9 @@ def add_arguments(sub):
     sub.add_argument("--vcfMerger", dest="vcfMerger", type=str, default=None, choices=MERGERS, metavar="MODE",
                      help="Who merges: bcftools (bgzip, tabix and bcftools on PATH, as the reference), device (this build's merge; parity pinned on the pipeline's own VCF grammar only), "
                           "auto (bcftools when all three tools are on PATH, else device).  Default: $SNPGPU_VCF_MERGER, else auto")
+    sub.add_argument("--mergeDeviceBytes", dest="mergeDeviceBytes", type=str, default=argparse.SUPPRESS, metavar="INT",
+                     help="Device memory the device route may allocate (0 = what is free, less a reserve); where the records of all files do not fit it the merge runs in "
+                          "bounded memory: a key pass over the files, then one reading per range of sites.  Ignored by the bcftools route.  Default: $SNPGPU_MERGE_DEVICE_BYTES, else 0")
 
 
 def merge_vcfs(args):
@@ -373,4 +398,5 @@ def merge_vcfs(args):
     utils.verify_non_empty_input_files("File of sample directories", [args.sampleDirsFile], error_handler="global")
     with open(args.sampleDirsFile, "r") as f:
         sample_dirs = [d for d in (line.rstrip() for line in f) if d]
-    merge_sample_dirs(sample_dirs, args.vcfFileName, args.mergedVcfFile, args.forceFlag, getattr(args, "vcfMerger", None))
+    merge_sample_dirs(sample_dirs, args.vcfFileName, args.mergedVcfFile, args.forceFlag, getattr(args, "vcfMerger", None),
+                      device_bytes=getattr(args, "mergeDeviceBytes", None))

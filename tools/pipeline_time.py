@@ -40,6 +40,8 @@ def main():
     ap.add_argument("--collect-metrics", type=int, default=0, metavar="RUNS",
                     help="after the timed runs: RUNS runs each of the job alone, of collect_metrics_batch -f after it (every pileup read again "
                          "for its depth sum) and of the job with --collectMetrics; medians, and whether both routes write the same metrics files")
+    ap.add_argument("--merge-device-bytes", type=int, default=0, metavar="N",
+                    help="with --merge-vcfs: the budget both merges run under (merge_vcfs --mergeDeviceBytes N, hot_path_batch --mergeDeviceBytes N); 0: the default")
     ap.add_argument("--merge-vcfs", type=int, default=0, metavar="RUNS",
                     help="after the timed runs: RUNS runs each of the job alone, of merge_vcfs -f (both flows, device route) after it and of the job "
                          "with --mergeVcfs; medians, and whether both routes write the same snpma.vcf / snpma_preserved.vcf")
@@ -187,6 +189,7 @@ def main():
             import statistics
             os.environ["SNPGPU_VCF_MERGER"] = "device"
             extra = " " + a.extra if a.extra else ""
+            budget = " --mergeDeviceBytes %d" % a.merge_device_bytes if a.merge_device_bytes else ""
             flows = (("consensus.vcf", "snpma.vcf", dirs_file + ".OrigVCF.filtered"), ("consensus_preserved.vcf", "snpma_preserved.vcf", dirs_file + ".PresVCF.filtered"))
 
             def merged_text():
@@ -197,14 +200,14 @@ def main():
                 alone.append(bench.run_cli(bench.hot_path_line(dirs_file, ref_path, extra), verbose=a.verbose))
                 wall = 0.0
                 for vcf, out, listing in flows:
-                    wall += bench.run_cli("merge_vcfs -f -n %s -o %s --verbose 0 %s" % (vcf, os.path.join(tmpdir, out), listing), verbose=a.verbose)
-                    library.append({k: mv.merge_sample_dirs.last_stats[k] for k in ("sites", "cells", "bytes", "rounds", "seconds_parse", "seconds_merge", "seconds_write")})
+                    wall += bench.run_cli("merge_vcfs -f -n %s -o %s --verbose 0%s %s" % (vcf, os.path.join(tmpdir, out), budget, listing), verbose=a.verbose)
+                    library.append({k: mv.merge_sample_dirs.last_stats[k] for k in ("sites", "cells", "bytes", "rounds", "seconds_parse", "seconds_merge", "seconds_write", "input_passes", "site_rounds", "sites_per_round")})
                 after.append(wall)
             separate_route = merged_text()
             for _ in range(a.merge_vcfs):
-                inside.append(bench.run_cli(bench.hot_path_line(dirs_file, ref_path, extra + " --mergeVcfs"), verbose=a.verbose))
+                inside.append(bench.run_cli(bench.hot_path_line(dirs_file, ref_path, extra + " --mergeVcfs" + budget), verbose=a.verbose))
                 phase.append(inside[-1] - hot_path.hot_path_batch.last_stats["seconds"])
-            out["merge_vcfs"] = {"runs": a.merge_vcfs, "job_alone_seconds": alone, "merge_vcfs_after_seconds": after, "job_with_mergeVcfs_seconds": inside,
+            out["merge_vcfs"] = {"runs": a.merge_vcfs, "merge_device_bytes": a.merge_device_bytes, "job_alone_seconds": alone, "merge_vcfs_after_seconds": after, "job_with_mergeVcfs_seconds": inside,
                                  "median_job_alone": statistics.median(alone), "median_after": statistics.median(after),
                                  "median_job_with_option": statistics.median(inside), "median_seconds_after_the_stages": statistics.median(phase),
                                  "option_cost_over_job": statistics.median(inside) / statistics.median(alone) - 1.0,
