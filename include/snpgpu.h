@@ -794,6 +794,84 @@ int  snpgpu_synth_reference_dev(snpgpu_ctx *ctx, uint64_t seed, uint32_t genome_
 int  snpgpu_synth_pileup_dev(snpgpu_ctx *ctx, const snpgpu_synth_params *p, const uint8_t *d_ref,
                              const uint8_t *d_site_alt, uint8_t *d_out, size_t capacity, size_t *out_nbytes);
 
+/* ---- BGZF-compressed pileups (`samtools mpileup | bgzip`): index on the host, inflate on the device ---------------
+ * (Additive in ABI 7.)  A BGZF file is a series of gzip members ("blocks") of at most 64 KiB of text each, every one with
+ * its compressed size in an extra subfield `BC`, so the blocks can be found without decoding and inflated independently.
+ * The index walks the headers; the inflate kernel takes one block per wave, decodes it into a 64 KiB window in LDS,
+ * checks its CRC32 there and writes the text at the block's plain offset.  A bad block is a status, never a fault. */
+#define SNPGPU_BGZF_E_NOT_GZIP   -101  /* no gzip magic at the start: the caller treats the file as plain text */
+#define SNPGPU_BGZF_E_NOT_BGZF   -102  /* gzip, but no BC subfield: unsupported ("recompress with bgzip") */
+#define SNPGPU_BGZF_E_TRUNCATED  -103  /* a block runs past the end of the data */
+#define SNPGPU_BGZF_E_ISIZE      -104  /* a block promises more than 65 536 bytes of text */
+#define SNPGPU_BGZF_E_MAGIC      -105  /* bad magic or header in mid-file */
+/* status of one block after inflate */
+#define SNPGPU_BGZF_ST_OK           0
+#define SNPGPU_BGZF_ST_BTYPE        1  /* reserved deflate block type */
+#define SNPGPU_BGZF_ST_STORED_LEN   2  /* stored block: LEN and NLEN disagree */
+#define SNPGPU_BGZF_ST_CODE_SET     3  /* over-subscribed or incomplete code lengths, bad repeat, no end-of-block code */
+#define SNPGPU_BGZF_ST_SYMBOL       4  /* bits that are no code of the set, or a reserved length / distance symbol */
+#define SNPGPU_BGZF_ST_DISTANCE     5  /* a match reaches before the block's own first byte */
+#define SNPGPU_BGZF_ST_INPUT_END    6  /* the bit stream ends before its end-of-block code */
+#define SNPGPU_BGZF_ST_OUTPUT_OVER  7  /* more text than ISIZE */
+#define SNPGPU_BGZF_ST_OUTPUT_SHORT 8  /* less text than ISIZE */
+#define SNPGPU_BGZF_ST_CRC          9  /* CRC32 of the text differs from the footer's */
+typedef struct snpgpu_bgzf_block {
+    uint64_t coff;       /* offset of the block (its gzip header) in the compressed data */
+    uint64_t poff;       /* offset of its text in the plain data */
+    uint32_t csize;      /* BSIZE + 1: the whole block */
+    uint32_t isize;      /* bytes of text, at most 65 536 */
+    uint32_t crc;        /* CRC32 of the text */
+    uint32_t data_off;   /* the deflate stream lies at [coff + data_off, coff + csize - 8) */
+} snpgpu_bgzf_block;
+typedef struct snpgpu_bgzf_info {
+    uint64_t n_blocks, plain_bytes, compressed_bytes;
+    uint64_t bad_block;      /* first block in error (index or inflate), UINT64_MAX: none */
+    uint64_t bad_offset;     /* its compressed offset */
+    int32_t  index_rc;       /* what the index said: 0 or SNPGPU_BGZF_E_* */
+    uint32_t bad_status;     /* SNPGPU_BGZF_ST_* of bad_block after inflate */
+    uint32_t n_bad;          /* blocks whose status is not OK */
+    uint32_t has_eof_marker; /* the file ends in the 28-byte empty block (its absence is accepted, as htslib accepts it) */
+    uint64_t reserved[2];
+} snpgpu_bgzf_info;
+/* 1: BGZF, 0: not gzip (plain text), SNPGPU_E_IO: cannot be read, SNPGPU_BGZF_E_NOT_BGZF / _TRUNCATED: gzip that is no BGZF.
+ * Reads the first block header only. */
+int  snpgpu_bgzf_probe(const char *path);
+const char *snpgpu_bgzf_strerror(int code);          /* the SNPGPU_BGZF_E_* codes in words */
+const char *snpgpu_bgzf_status_name(uint32_t status);
+/* The block table of data[0, nbytes) (host memory, no context).  *out_n: the number of blocks; at most `capacity` of them are
+ * written (capacity 0 only counts).  Returns 0 or the SNPGPU_BGZF_E_* of the first bad header (info->bad_offset says where;
+ * the blocks before it are valid and counted).  info is nullable. */
+int  snpgpu_bgzf_index(const uint8_t *data, uint64_t nbytes, snpgpu_bgzf_block *out_blocks, uint64_t capacity, uint64_t *out_n,
+                       snpgpu_bgzf_info *info);
+/* Device to device: the blocks h_blocks[0, n_blocks) (a HOST table) of d_compressed[0, compressed_bytes) inflated to
+ * d_out[poff, poff + isize).  Before any launch the table is checked on the host: a block that leaves the compressed data, or
+ * whose text would pass out_capacity, is SNPGPU_E_ARG.  h_block_status (nullable) receives one SNPGPU_BGZF_ST_* per block; a bad
+ * block leaves its text unwritten and every other block untouched.  Synchronous.  Returns 0 also when blocks are bad: see
+ * info->n_bad / bad_block / bad_status (info nullable). */
+int  snpgpu_bgzf_inflate_dev(snpgpu_ctx *ctx, const void *d_compressed, uint64_t compressed_bytes, const snpgpu_bgzf_block *h_blocks,
+                             uint64_t n_blocks, void *d_out, uint64_t out_capacity, uint32_t *h_block_status, snpgpu_bgzf_info *info);
+/* One block on the host with the decoder the kernel runs: block[0, b->csize) -> out[0, b->isize).  Returns its status. */
+uint32_t snpgpu_bgzf_inflate_block_host(const uint8_t *block, const snpgpu_bgzf_block *b, uint8_t *out);
+/* Host only: the plain bytes [plain_offset, plain_offset + nbytes) of a BGZF file (fewer at the end of the text: *out_n),
+ * from the index and the host inflater.  SNPGPU_E_IO, SNPGPU_E_PILEUP (bad block) or a SNPGPU_BGZF_E_* code on failure. */
+int  snpgpu_bgzf_read_range(const char *path, uint64_t plain_offset, uint64_t nbytes, uint8_t *out, uint64_t *out_n);
+/* snpgpu_call_consensus_files for BGZF files: arguments and outputs as there, plus out_info [n_files] (nullable).  Each
+ * file's compressed bytes go through the reader threads and the pinned ring to the device, are inflated there into a text
+ * buffer sized from the index, and scanned and called like a resident pileup.  out_line_off is 1 + the offset in the PLAIN
+ * text.  out_rc: SNPGPU_E_IO for a file that cannot be read or is truncated, SNPGPU_E_UNSUPPORTED for one that is no BGZF,
+ * SNPGPU_E_PILEUP for a bad block (CRC, ISIZE, deflate stream) — the block and the cause are in out_info and in
+ * snpgpu_last_error; the rows of such a file are '-' / 0 / no line.  SNPGPU_E_NOMEM when the text buffer cannot be had.
+ * Limitation: one file at a time.  There is one compressed slot and one text slot; the read, copy and inflate of file k+1 do
+ * NOT overlap the scan and call of file k (each file is loaded and inflated synchronously, then scanned as device text).
+ * stats: bytes (PLAIN text that was scanned), n_chunks (files that were inflated), seconds, seconds_waiting_for_device and
+ * seconds_enqueueing are filled; n_readers, n_staging, chunk_bytes and the reader seconds stay 0. */
+int  snpgpu_call_consensus_bgzf_files(snpgpu_ctx *ctx, const snpgpu_siteset *ss, const char *const *paths, uint32_t n_files,
+                                      const snpgpu_caller_params *params, const uint32_t *excl_off, const uint32_t *excl_slots,
+                                      uint8_t *out_base, uint8_t *out_filters,
+                                      snpgpu_site_counts *out_counts, uint64_t *out_line_off, uint64_t *out_status,
+                                      int32_t *out_rc, const snpgpu_stream_opts *opts, snpgpu_stream_stats *stats,
+                                      snpgpu_bgzf_info *out_info);
+
 #ifdef __cplusplus
 }
 #endif

@@ -102,13 +102,28 @@ class CpuBudget(C.Structure):
                 ("local_ranks", C.c_uint32), ("budget", C.c_uint32), ("readers", C.c_uint32), ("writers", C.c_uint32)]
 
 
+class BgzfBlock(C.Structure):
+    _fields_ = [("coff", C.c_uint64), ("poff", C.c_uint64), ("csize", C.c_uint32), ("isize", C.c_uint32), ("crc", C.c_uint32), ("data_off", C.c_uint32)]
+
+
+class BgzfInfo(C.Structure):
+    _fields_ = [("n_blocks", C.c_uint64), ("plain_bytes", C.c_uint64), ("compressed_bytes", C.c_uint64), ("bad_block", C.c_uint64),
+                ("bad_offset", C.c_uint64), ("index_rc", C.c_int32), ("bad_status", C.c_uint32), ("n_bad", C.c_uint32),
+                ("has_eof_marker", C.c_uint32), ("reserved", C.c_uint64 * 2)]
+
+
+BGZF_E_NOT_GZIP, BGZF_E_NOT_BGZF, BGZF_E_TRUNCATED, BGZF_E_ISIZE, BGZF_E_MAGIC = -101, -102, -103, -104, -105
+(BGZF_ST_OK, BGZF_ST_BTYPE, BGZF_ST_STORED_LEN, BGZF_ST_CODE_SET, BGZF_ST_SYMBOL, BGZF_ST_DISTANCE, BGZF_ST_INPUT_END, BGZF_ST_OUTPUT_OVER,
+ BGZF_ST_OUTPUT_SHORT, BGZF_ST_CRC) = range(10)
+
+
 class ConsensusJob(C.Structure):
     _fields_ = [("fasta_path", C.c_char_p), ("fasta_id", C.c_char_p), ("sequence", C.c_void_p), ("n_bases", C.c_uint64),
                 ("vcf_path", C.c_char_p), ("vcf_header", C.c_char_p), ("counts", C.c_void_p), ("line_off", C.c_void_p),
                 ("row_filters", C.c_void_p), ("site_in_flow", C.c_void_p), ("rc", C.c_int32), ("n_rows", C.c_uint32)]
 
 
-assert C.sizeof(SiteCounts) == 128 and C.sizeof(CallerParams) == 32 and C.sizeof(VarscanSite) == 48 and C.sizeof(VarscanParams) == 24
+assert C.sizeof(BgzfBlock) == 32 and C.sizeof(BgzfInfo) == 72 and C.sizeof(SiteCounts) == 128 and C.sizeof(CallerParams) == 32 and C.sizeof(VarscanSite) == 48 and C.sizeof(VarscanParams) == 24
 
 # name -> (restype, argtypes); every exported symbol of include/snpgpu.h
 _P = C.c_void_p
@@ -207,6 +222,15 @@ SIGNATURES = {
     "snpgpu_group_check_dev": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_uint32, C.c_uint32, _P]),
     "snpgpu_synth_reference_dev": (C.c_int, [_P, C.c_uint64, C.c_uint32, _P]),
     "snpgpu_synth_pileup_dev": (C.c_int, [_P, C.POINTER(SynthParams), _P, _P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "snpgpu_bgzf_probe": (C.c_int, [C.c_char_p]),
+    "snpgpu_bgzf_strerror": (C.c_char_p, [C.c_int]),
+    "snpgpu_bgzf_status_name": (C.c_char_p, [C.c_uint32]),
+    "snpgpu_bgzf_index": (C.c_int, [_P, C.c_uint64, _P, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(BgzfInfo)]),
+    "snpgpu_bgzf_inflate_dev": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint64, _P, C.c_uint64, _P, C.POINTER(BgzfInfo)]),
+    "snpgpu_bgzf_inflate_block_host": (C.c_uint32, [_P, C.POINTER(BgzfBlock), _P]),
+    "snpgpu_bgzf_read_range": (C.c_int, [C.c_char_p, C.c_uint64, C.c_uint64, _P, C.POINTER(C.c_uint64)]),
+    "snpgpu_call_consensus_bgzf_files": (C.c_int, [_P, _P, C.POINTER(C.c_char_p), C.c_uint32, C.POINTER(CallerParams), _P, _P, _P, _P,
+                                                   _P, _P, _P, _P, C.POINTER(StreamOpts), C.POINTER(StreamStats), _P]),
 }
 
 _lib = None

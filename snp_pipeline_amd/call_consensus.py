@@ -17,6 +17,7 @@ import numpy as np
 
 from . import _lib as L
 from . import device as devmod
+from . import pileup_text
 from . import timing
 from . import utils
 from . import vcf_writer
@@ -77,12 +78,15 @@ def _raise_as_reference(err, pileup_path=None, every_line_is_a_record=False):
         # A byte >= 0x80.  The reference reads the pileup as text (pileup.py:405, the locale's encoding: UTF-8 on the
         # pipeline's platforms), so a file that is not valid UTF-8 ends its run with UnicodeDecodeError: the same here.
         # (Valid multi-byte characters are the one input that is still refused: they would count as single symbols.)
-        with open(pileup_path, "rb") as f:
-            f.read().decode("utf-8")
+        pileup_text.read_all(pileup_path).decode("utf-8")      # (plain or BGZF: the text)
         raise _ValidUtf8(str(err))                   # (call_consensus tries the escaped-names bridge, utf8_names.py, before giving up)
     if exc is None:
         raise err
     raise exc(str(err))
+
+
+_ALL_POS_BGZF = ("Error: --vcfAllPos cannot be used with a BGZF-compressed pileup (%s): its rows are formatted from the pileup's text on the host.  "
+                 "Decompress the pileup, or write the VCF without --vcfAllPos.")
 
 
 class _Plan(object):
@@ -108,6 +112,9 @@ def _write_outputs(plan, dev, ss, snp_slots, res, file_flags=None):
     if file_flags is None:
         file_flags = ss.flags
     in_snplist = (file_flags & L.SITE_IN_SNPLIST) != 0
+    info = getattr(res, "bgzf_info", None)
+    if info is not None and not info["has_eof_marker"]:
+        utils.verbose_print("BGZF pileup %s has no end-of-file marker block (accepted; a file cut at a block boundary looks the same)." % plan.pileup_path)
     utils.verbose_print("called consensus positions = %i" % int(((res.counts["status"] != L.ST_NO_LINE) & in_snplist).sum()))
     if plan.vcf_path:
         dup = res.n_matched > int(np.count_nonzero(res.line_offsets))
@@ -119,8 +126,16 @@ def _write_outputs(plan, dev, ss, snp_slots, res, file_flags=None):
             params = devmod.make_params(args.minBaseQual, args.minConsFreq, args.minConsDpth, args.minConsStrdDpth, args.minConsStrdBias)
             own = ss if file_flags is ss.flags else devmod.SiteSet.from_arrays(dev, ss.contigs, ss.keys[file_flags != 0], file_flags[file_flags != 0])
             try:
-                vcf_writer.write_all_positions_vcf_from_pileup(dev, own, plan.vcf_path, plan.sample_name, args, plan.read_path, params,
-                                                               only_listed=not args.vcfAllPos, check=bool(args.vcfAllPos))
+                if not args.vcfAllPos and pileup_text.probe(plan.read_path) == 1:
+                    # a BGZF pileup that repeats a position: the file-to-file writer formats from the text on the host, which a
+                    # compressed file does not offer; the few rows come from the all-lines pass, their CHROM and POS from the blocks
+                    # that hold the lines
+                    off, line_flags, counts = dev.call_all_lines(own, plan.read_path, params, capacity=res.n_lines, check=False)
+                    keep = line_flags != 0
+                    vcf_writer.write_all_positions_vcf(plan.vcf_path, plan.sample_name, args, plan.read_path, off[keep], counts[keep], spill=dev.last_spill)
+                else:
+                    vcf_writer.write_all_positions_vcf_from_pileup(dev, own, plan.vcf_path, plan.sample_name, args, plan.read_path, params,
+                                                                   only_listed=not args.vcfAllPos, check=bool(args.vcfAllPos))
             except devmod.PileupFormatError as err:
                 _raise_as_reference(err, plan.read_path, bool(args.vcfAllPos))
             finally:
@@ -172,6 +187,8 @@ def call_consensus(args):
     if utils.verify_non_empty_input_files("Pileup file", [all_pileup_file_path]) > 0:
         utils.sample_error("Error: cannot call consensus without the pileup file.", continue_possible=False)
     source_files = [snp_list_file_path, all_pileup_file_path]
+    if args.vcfAllPos and plan.vcf_path and pileup_text.probe(all_pileup_file_path) == 1:
+        utils.global_error(_ALL_POS_BGZF % all_pileup_file_path)
 
     if plan.exclude_path:
         if utils.verify_existing_input_files("Exclude file", [plan.exclude_path]) > 0:
@@ -237,7 +254,7 @@ def _call_one(plan, dev, params, snp_arrays):
 def _call_one_on(plan, dev, params, ss, snp_slots):
     args = plan.args
     timing.mark("site set")
-    results, rcs, _ = dev.call_consensus_files(ss, [plan.read_path], params, want_counts=True, want_line_offsets=True,
+    results, rcs, _ = dev.call_consensus_files(ss, [plan.read_path], params, want_counts=True, want_line_offsets=True, bgzf=True,
                                                want_depth_sum=bool(getattr(args, "amdMetricsRefFasta", None)))
     timing.mark("streamed call")
     all_pos = bool(args.vcfAllPos and plan.vcf_path)
@@ -273,6 +290,11 @@ def call_consensus_batch(args):
     if utils.verify_existing_input_files("Snplist file", [snp_list_file_path]) > 0:
         utils.global_error("Error: cannot call consensus without the snplist file.")
 
+    if args.vcfAllPos and args.vcfFileName:           # before any output is touched
+        for d in sample_dirs:
+            path = os.path.join(d, args.pileupName)
+            if os.path.isfile(path) and pileup_text.probe(path) == 1:
+                utils.global_error(_ALL_POS_BGZF % path)
     plans, failed = [], 0
     for d in sample_dirs:
         plan = _Plan(args, os.path.join(d, args.pileupName), os.path.join(d, args.consensusFile),
@@ -343,7 +365,7 @@ def call_consensus_batch(args):
                 part = my_plans[k0:k0 + step]
                 exclude = [excl_slots.get(id(p), np.zeros(0, np.int64)) for p in part] if with_excl else None
                 results, rcs, _ = dev.call_consensus_files(ss, [p.pileup_path for p in part], params, want_counts=True,
-                                                           want_line_offsets=True, exclude=exclude,
+                                                           want_line_offsets=True, exclude=exclude, bgzf=True,
                                                            want_depth_sum=bool(getattr(args, "amdMetricsRefFasta", None)))
                 if writer is not None:
                     writer.join()             # one writer at a time: the device context below is this thread's again

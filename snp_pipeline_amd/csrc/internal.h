@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/snpgpu.h"
+#include "bgzf_host.h"
 
 struct snpgpu_stream_pool;          // stream.hip: pinned staging ring, device file slots, copy stream
 void snpgpu_stream_pool_destroy(struct snpgpu_ctx *ctx);
@@ -26,6 +27,7 @@ struct snpgpu_ctx {
     int n_cu = 256;
     bool scan_lds_attr = false;         // hipFuncSetAttribute is per device: done once per context
     bool varscan_lds_attr = false;
+    bool bgzf_lds_attr = false;
     void *comm = nullptr;               // comm.hip: the RCCL communicator of this rank (snpgpu_comm_init), or none
     // positions with more than SNPGPU_MAX_SYMS symbols: [SNPGPU_SPILL_CAP] records + one counter word (allocated on first use)
     snpgpu_symbol_spill *d_spill = nullptr;
@@ -50,6 +52,7 @@ struct snpgpu_ctx {
 #define SNPGPU_K_VARSCAN 3          // everything phase-1 site calling launches for one file (scan, walk, long walk)
 #define SNPGPU_K_VCF_COUNT 4        // the SNP count of a piece of a VCF file (vcf_count.hip)
 #define SNPGPU_K_VCF_MERGE 5        // the parse, rows and write kernels of merge_vcfs (vcf_merge.hip)
+#define SNPGPU_K_BGZF 6             // the inflate kernel of BGZF-compressed pileups (bgzf.hip)
 // RAII-less helpers: call begin before the launch and end right after it (no-ops unless timing is enabled)
 // Start of a public call that produces per-site records: the spill is there and empty (enqueued on the context's stream).
 int snpgpu_spill_begin(snpgpu_ctx *ctx);
@@ -203,6 +206,13 @@ int snpgpu_enqueue_merge_key_sites(snpgpu_ctx *ctx, const snpgpu_merge_key *d_re
 int snpgpu_enqueue_merge_key_rank(snpgpu_ctx *ctx, uint64_t *d_keys, uint32_t n, const uint32_t *d_rank, uint32_t *d_zeros);
 int snpgpu_enqueue_merge_place(snpgpu_ctx *ctx, const snpgpu_merge_cell *d_extra, uint32_t n, uint32_t lo, uint32_t n_col, snpgpu_merge_cell *d_cells, uint32_t *d_table,
                                uint64_t *d_ctl);
+// bgzf.hip: BGZF-compressed pileups (the index and the host inflater: bgzf_host.h).  The host-side check of a table against its buffers; the inflate kernel over a checked table (d_ws: snpgpu_bgzf_scratch_bytes,
+// *d_status: where the n_blocks status words are afterwards); first bad block and count into info
+size_t snpgpu_bgzf_scratch_bytes(uint64_t n_blocks);
+int snpgpu_bgzf_check_table(snpgpu_ctx *ctx, const snpgpu_bgzf_block *h_blocks, uint64_t n_blocks, uint64_t compressed_bytes, uint64_t out_capacity);
+int snpgpu_enqueue_bgzf_inflate(snpgpu_ctx *ctx, const uint8_t *d_comp, const snpgpu_bgzf_block *h_blocks, uint64_t n_blocks, uint8_t *d_out, void *d_ws,
+                                uint32_t **d_status);
+void snpgpu_bgzf_summarise(const snpgpu_bgzf_block *h_blocks, const uint32_t *h_status, uint64_t n_blocks, snpgpu_bgzf_info *info);
 // regions.hip: merge_sites in the caller's own workspace
 size_t snpgpu_merge_sites_ws_bytes(uint64_t n);
 int snpgpu_enqueue_merge_sites_ws(snpgpu_ctx *ctx, const uint64_t *d_keys, const uint32_t *d_sample_of_key, uint32_t n, uint64_t *d_out_unique, uint32_t *d_out_off,

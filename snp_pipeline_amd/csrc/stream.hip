@@ -49,6 +49,7 @@ inline double now_s() { return std::chrono::duration<double>(std::chrono::steady
 struct Source {
     const char *path = nullptr;     // a file ...
     const uint8_t *mem = nullptr;   // ... or host memory
+    const uint8_t *dev = nullptr;   // ... or text that is already in device memory (an inflated BGZF file): nothing to read or copy
     uint64_t size = 0;
     int fd = -1;
     int rc = SNPGPU_OK;
@@ -346,7 +347,7 @@ struct DevScratch {                 // one carve-up of the context's scratch, sh
 // called with the set's flags | SNPGPU_SITE_EXCLUDED on those slots.
 int run_stream(snpgpu_ctx *ctx, const snpgpu_siteset *ss, std::vector<Source> &src, const snpgpu_caller_params *prm,
                const Outputs &out, const snpgpu_stream_opts *opts, snpgpu_stream_stats *stats, uint64_t *d_site_line,
-               const uint32_t *excl_off = nullptr, const uint32_t *excl_slots = nullptr) {
+               const uint32_t *excl_off = nullptr, const uint32_t *excl_slots = nullptr, bool keep_spill = false) {
     const double t_start = now_s();
     const uint32_t n_files = (uint32_t)src.size();
     const uint32_t n_sites = ss->n_sites;
@@ -361,7 +362,7 @@ int run_stream(snpgpu_ctx *ctx, const snpgpu_siteset *ss, std::vector<Source> &s
         }
     }
     HIP_TRY(ctx, snpgpu_enter(ctx));
-    if (out.counts) { int rc0 = snpgpu_spill_begin(ctx); if (rc0) return rc0; }
+    if (out.counts && !keep_spill) { int rc0 = snpgpu_spill_begin(ctx); if (rc0) return rc0; }     // (keep_spill: one arena for several calls, begun by the caller)
     size_t chunk = opts && opts->chunk_bytes ? opts->chunk_bytes : (size_t)16 << 20;
     chunk = up(chunk < 65536 ? 65536 : chunk, SNPGPU_SCAN_TILE);
     const int want_depth = opts && opts->want_depth_sum ? 1 : 0;
@@ -378,7 +379,7 @@ int run_stream(snpgpu_ctx *ctx, const snpgpu_siteset *ss, std::vector<Source> &s
                 s.size = (uint64_t)stt.st_size;
             }
         }
-        if (s.size > max_size) max_size = s.size;
+        if (s.size > max_size && !s.dev) max_size = s.size;
         total_bytes += s.size;
     }
     Opener opener;
@@ -388,12 +389,12 @@ int run_stream(snpgpu_ctx *ctx, const snpgpu_siteset *ss, std::vector<Source> &s
     uint32_t max_chunks = 1;
     for (uint32_t f = 0; f < n_files; ++f) {
         const uint64_t n = src[f].size;
-        const uint32_t nc = n ? (uint32_t)((n + chunk - 1) / chunk) : 1;   // an empty file still takes one (empty) job
+        const uint32_t nc = n && !src[f].dev ? (uint32_t)((n + chunk - 1) / chunk) : 1;   // an empty file still takes one (empty) job, and so does device text
         chunks_of[f] = nc;
         if (nc > max_chunks) max_chunks = nc;
         for (uint32_t c = 0; c < nc; ++c) {
             const uint64_t off = (uint64_t)c * chunk;
-            jobs.push_back(Job{f, off, n - off < chunk ? n - off : chunk, c == 0, c + 1 == nc, c});
+            jobs.push_back(Job{f, off, src[f].dev ? 0 : (n - off < chunk ? n - off : chunk), c == 0, c + 1 == nc, c});
         }
     }
     const uint64_t J = jobs.size();
@@ -514,7 +515,7 @@ int run_stream(snpgpu_ctx *ctx, const snpgpu_siteset *ss, std::vector<Source> &s
             const Job &jb = jobs[j];
             const uint32_t f = jb.file, slot = f % (uint32_t)p->slot.size();
             Source &s = src[f];
-            uint8_t *d_file = (uint8_t *)p->slot[slot];
+            uint8_t *d_file = s.dev ? (uint8_t *)s.dev : (uint8_t *)p->slot[slot];
             SampleDev *h_tab = (SampleDev *)p->table_host[slot];
             SampleDev *d_tab = (SampleDev *)((char *)ds.tables + ds.table_stride * slot);
             const uint32_t nc = chunks_of[f];
@@ -650,7 +651,8 @@ done:
 // One file into device slot 0 through the same reader threads / staging ring / two copy streams as run_stream (the
 // all-lines passes: --vcfAllPos and phase-1 site calling index the whole file before they look at a line, so there is
 // nothing to overlap the copy with but the reads).  Synchronous.
-int load_file(snpgpu_ctx *ctx, const char *path, uint8_t **d_file, uint64_t *size) {
+// n_slots / min_slot_bytes: what the pool must hold besides (a BGZF file: a second slot, both large enough for the text).
+int load_raw(snpgpu_ctx *ctx, const char *path, uint32_t n_slots, size_t min_slot_bytes, uint8_t **d_file, uint64_t *size) {
     std::vector<Source> src(1);
     Source &s = src[0];
     s.path = path;
@@ -678,7 +680,9 @@ int load_file(snpgpu_ctx *ctx, const char *path, uint8_t **d_file, uint64_t *siz
     uint32_t n_staging = n_readers + 4;
     if (n_staging > J) n_staging = (uint32_t)J;
     if (n_staging < 1) n_staging = 1;
-    int rc = pool_ensure(ctx, chunk, n_staging, 1, up(n + SNPGPU_SCAN_TILE + 256, 4096), 256, 256);
+    size_t slot_bytes = up(n + SNPGPU_SCAN_TILE + 256, 4096);
+    if (slot_bytes < min_slot_bytes) slot_bytes = min_slot_bytes;
+    int rc = pool_ensure(ctx, chunk, n_staging, n_slots, slot_bytes, 256, 256);
     if (rc) { close(s.fd); return rc; }
     snpgpu_stream_pool *p = ctx->pool;
     const uint64_t R = p->staging.size() < n_staging ? p->staging.size() : n_staging;
@@ -730,6 +734,59 @@ int load_file(snpgpu_ctx *ctx, const char *path, uint8_t **d_file, uint64_t *siz
     return SNPGPU_OK;
 }
 
+// A BGZF file: its block table from a header-hopping pass over the mapped file, its compressed bytes into slot 0 the same way,
+// the inflate kernel from there into slot 1 (sized from the table, never from the compressed size).  Synchronous; the text stays
+// valid until the next call that loads a file.  info (nullable) says which block was bad and why.
+int load_bgzf(snpgpu_ctx *ctx, const char *path, uint8_t **d_file, uint64_t *size, snpgpu_bgzf_info *info) {
+    snpgpu_bgzf_info local;
+    if (!info) info = &local;
+    std::vector<snpgpu_bgzf_block> blocks;
+    const uint8_t *map = nullptr;
+    uint64_t map_bytes = 0;
+    int rc = snpgpu_bgzf_index_file(path, blocks, info, &map, &map_bytes);
+    if (map) munmap((void *)map, map_bytes);
+    if (rc == SNPGPU_E_IO) return snpgpu_set_error(ctx, SNPGPU_E_IO, "cannot open the pileup file %s", path);
+    if (rc != SNPGPU_OK)
+        return snpgpu_set_error(ctx, rc == SNPGPU_BGZF_E_TRUNCATED ? SNPGPU_E_IO : rc == SNPGPU_BGZF_E_NOT_BGZF || rc == SNPGPU_BGZF_E_NOT_GZIP ? SNPGPU_E_UNSUPPORTED : SNPGPU_E_PILEUP,
+                                "compressed pileup %s: %s (block %llu at byte offset %llu)", path, snpgpu_bgzf_strerror(rc), (unsigned long long)info->bad_block,
+                                (unsigned long long)info->bad_offset);
+    const uint64_t plain = info->plain_bytes;
+    uint8_t *d_comp = nullptr;
+    uint64_t n_comp = 0;
+    rc = load_raw(ctx, path, 2, up(plain + SNPGPU_SCAN_TILE + 256, 4096), &d_comp, &n_comp);
+    if (rc == SNPGPU_E_NOMEM) return snpgpu_set_error(ctx, SNPGPU_E_NOMEM, "no device memory for the %llu bytes of text of the compressed pileup %s", (unsigned long long)plain, path);
+    if (rc) return rc;
+    if (n_comp != info->compressed_bytes) return snpgpu_set_error(ctx, SNPGPU_E_IO, "the pileup file %s changed while it was read", path);
+    uint8_t *d_text = (uint8_t *)ctx->pool->slot[1];
+    rc = snpgpu_bgzf_check_table(ctx, blocks.data(), blocks.size(), n_comp, plain);
+    if (rc) return rc;
+    void *ws = nullptr;
+    rc = snpgpu_scratch(ctx, snpgpu_bgzf_scratch_bytes(blocks.size()), &ws);
+    if (rc) return rc;
+    uint32_t *d_status = nullptr;
+    rc = snpgpu_enqueue_bgzf_inflate(ctx, d_comp, blocks.data(), blocks.size(), d_text, ws, &d_status);
+    if (rc) return rc;
+    std::vector<uint32_t> st(blocks.size());
+    if (!st.empty()) HIP_TRY(ctx, hipMemcpyAsync(st.data(), d_status, 4 * st.size(), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    snpgpu_bgzf_summarise(blocks.data(), st.data(), blocks.size(), info);
+    if (info->n_bad)
+        return snpgpu_set_error(ctx, SNPGPU_E_PILEUP, "compressed pileup %s: block %llu at byte offset %llu: %s", path, (unsigned long long)info->bad_block,
+                                (unsigned long long)info->bad_offset, snpgpu_bgzf_status_name(info->bad_status));
+    *d_file = d_text;
+    *size = plain;
+    return SNPGPU_OK;
+}
+
+// The text of a pileup file in device memory, whether the file holds it plain or BGZF-compressed (decided by content).
+int load_file(snpgpu_ctx *ctx, const char *path, uint8_t **d_file, uint64_t *size) {
+    const int kind = snpgpu_bgzf_probe(path);
+    if (kind == 1) return load_bgzf(ctx, path, d_file, size, nullptr);
+    if (kind == SNPGPU_BGZF_E_NOT_BGZF || kind == SNPGPU_BGZF_E_TRUNCATED || kind == SNPGPU_BGZF_E_MAGIC)
+        return snpgpu_set_error(ctx, kind == SNPGPU_BGZF_E_TRUNCATED ? SNPGPU_E_IO : SNPGPU_E_UNSUPPORTED, "compressed pileup %s: %s", path, snpgpu_bgzf_strerror(kind));
+    return load_raw(ctx, path, 1, 0, d_file, size);         // (a file that cannot be opened fails there, in the words it always did)
+}
+
 int scan_status_error(snpgpu_ctx *ctx, const uint64_t *status, const char *what_file) {
     unsigned code = (unsigned)(status[0] & 0xFF);
     unsigned long long off = (unsigned long long)(status[0] >> 8) - 1;
@@ -778,6 +835,60 @@ int snpgpu_call_consensus_files_dev(snpgpu_ctx *ctx, const snpgpu_siteset *ss, c
     Outputs out{d_out_base, d_out_filters, d_out_counts, d_out_line_off, out_status, out_rc};
     out.on_device = true;
     return run_stream(ctx, ss, src, params, out, opts, stats, nullptr, excl_off, excl_slots);
+}
+
+// BGZF files: each one is loaded and inflated (load_bgzf), then takes the whole-file sequence of the stream above as text that is
+// already on the device.  One file at a time: the read, copy and inflate of a file do not yet overlap the scan and call of the one before.
+int snpgpu_call_consensus_bgzf_files(snpgpu_ctx *ctx, const snpgpu_siteset *ss, const char *const *paths, uint32_t n_files,
+                                     const snpgpu_caller_params *params, const uint32_t *excl_off, const uint32_t *excl_slots,
+                                     uint8_t *out_base, uint8_t *out_filters,
+                                     snpgpu_site_counts *out_counts, uint64_t *out_line_off, uint64_t *out_status,
+                                     int32_t *out_rc, const snpgpu_stream_opts *opts, snpgpu_stream_stats *stats, snpgpu_bgzf_info *out_info) {
+    if (!ctx || !ss || !params || !out_status || (n_files && !paths)) return snpgpu_set_error(ctx, SNPGPU_E_ARG, "null argument");
+    if (ss->n_sites && n_files && (!out_base || !out_filters)) return snpgpu_set_error(ctx, SNPGPU_E_ARG, "null output");
+    for (uint32_t f = 0; f < n_files; ++f) if (!paths[f]) return snpgpu_set_error(ctx, SNPGPU_E_ARG, "null path %u", f);
+    const double t_start = now_s();
+    if (stats) memset(stats, 0, sizeof *stats);
+    HIP_TRY(ctx, snpgpu_enter(ctx));
+    const size_t n_sites = ss->n_sites;
+    if (out_counts) { int rc0 = snpgpu_spill_begin(ctx); if (rc0) return rc0; }     // the spill records of all files of the call form one arena
+    std::string first_error;
+    uint64_t total = 0;
+    for (uint32_t f = 0; f < n_files; ++f) {
+        uint8_t *d_text = nullptr;
+        uint64_t nbytes = 0;
+        const size_t row = (size_t)f * n_sites;
+        int rc = load_bgzf(ctx, paths[f], &d_text, &nbytes, out_info ? out_info + f : nullptr);
+        if (rc == SNPGPU_E_HIP || rc == SNPGPU_E_NOMEM || rc == SNPGPU_E_ARG) return rc;
+        if (rc == SNPGPU_OK) {
+            std::vector<Source> src(1);
+            src[0].dev = d_text;
+            src[0].size = nbytes;
+            Outputs out{out_base + row, out_filters + row, out_counts ? out_counts + row : nullptr, out_line_off ? out_line_off + row : nullptr,
+                        out_status + (size_t)f * SNPGPU_SCAN_STATUS_WORDS, out_rc ? out_rc + f : nullptr};
+            snpgpu_stream_stats one;
+            rc = run_stream(ctx, ss, src, params, out, opts, &one, nullptr, excl_off ? excl_off + f : nullptr, excl_slots, true);
+            if (rc) return rc;
+            total += nbytes;
+            if (stats) { stats->n_chunks += 1; stats->seconds_waiting_for_device += one.seconds_waiting_for_device; stats->seconds_enqueueing += one.seconds_enqueueing; }
+            continue;
+        }
+        // this file has no text: its rows are void, the others go on
+        if (first_error.empty()) first_error = ctx->err;
+        if (n_sites) {
+            memset(out_base + row, '-', n_sites);
+            memset(out_filters + row, 0, n_sites);
+            if (out_counts) memset(out_counts + row, 0, sizeof(snpgpu_site_counts) * n_sites);
+            if (out_line_off) memset(out_line_off + row, 0, 8 * n_sites);
+        }
+        uint64_t *stw = out_status + (size_t)f * SNPGPU_SCAN_STATUS_WORDS;
+        memset(stw, 0, 8 * SNPGPU_SCAN_STATUS_WORDS);
+        stw[0] = ~0ull;
+        if (out_rc) out_rc[f] = rc;
+    }
+    if (!first_error.empty()) ctx->err = first_error;       // (snpgpu_last_error: the first file that failed, with its block and cause)
+    if (stats) { stats->bytes = total; stats->seconds = now_s() - t_start; }
+    return SNPGPU_OK;
 }
 
 // Host-buffer form for ONE pileup (an mmap, bytes read elsewhere): same pipeline, the readers memcpy instead of pread.
@@ -973,6 +1084,9 @@ int snpgpu_write_all_positions_vcf(snpgpu_ctx *ctx, const snpgpu_siteset *ss, co
     if (!ctx || !ss || !pileup_path || !params || !vcf_path || !header || !filter_names || !out_n_lines || !out_n_rows || !out_first_bad_line ||
         !out_first_bad_off || !out_first_bad || !out_status)
         return snpgpu_set_error(ctx, SNPGPU_E_ARG, "null argument");
+    // the rows are formatted from the pileup's text on the host: a compressed pileup is refused before anything is opened or truncated
+    if (snpgpu_bgzf_probe(pileup_path) == 1)
+        return snpgpu_set_error(ctx, SNPGPU_E_UNSUPPORTED, "every-position VCF output from a BGZF-compressed pileup is not supported: %s", pileup_path);
     HIP_TRY(ctx, snpgpu_enter(ctx));
     *out_n_lines = *out_n_rows = 0;
     *out_first_bad_line = ~0ull;
@@ -1765,7 +1879,7 @@ int snpgpu_varscan_file(snpgpu_ctx *ctx, const char *path, const snpgpu_varscan_
     HIP_TRY(ctx, snpgpu_enter(ctx));
     uint8_t *d_file = nullptr;
     uint64_t nbytes = 0;
-    int rc = load_file(ctx, path, &d_file, &nbytes);
+    int rc = load_raw(ctx, path, 1, 0, &d_file, &nbytes);     // (plain text only: the rows of var.flt.vcf are formatted from the file on the host)
     if (rc) return rc;
     return varscan_resident(ctx, d_file, nbytes, path, params, capacity, out_sites, out_n_sites, out_status);
 }

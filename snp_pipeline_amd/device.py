@@ -55,6 +55,18 @@ def _ptr(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
 
 
+def _bgzf_error_text(path, rc, info):
+    """None for a BGZF file that was inflated; else what failed, in words, for the exception of that file."""
+    if rc == 0 or (info.index_rc == 0 and info.n_bad == 0):
+        return None
+    lib = L.load()
+    if info.index_rc != 0:
+        return "compressed pileup %s: %s (block %d at byte offset %d)" % (path, lib.snpgpu_bgzf_strerror(info.index_rc).decode("ascii"),
+                                                                         info.bad_block, info.bad_offset)
+    return "compressed pileup %s: block %d at byte offset %d cannot be inflated: %s (%d bad block%s)" % (
+        path, info.bad_block, info.bad_offset, lib.snpgpu_bgzf_status_name(info.bad_status).decode("ascii"), info.n_bad, "" if info.n_bad == 1 else "s")
+
+
 def make_params(min_base_quality=0, min_cons_freq=0.6, min_cons_depth=1, min_cons_strand_depth=0,
                 min_cons_strand_bias=0.0):
     return CallerParams(int(min_base_quality), int(min_cons_depth), int(min_cons_strand_depth), 0,
@@ -283,13 +295,14 @@ def _exclude_csr(exclude, n_files):
 
 
 class ConsensusResult(object):
-    __slots__ = ("bases", "filters", "counts", "status", "n_lines", "n_matched", "depth_sum", "line_offsets", "spill")
+    __slots__ = ("bases", "filters", "counts", "status", "n_lines", "n_matched", "depth_sum", "line_offsets", "spill", "bgzf_info", "bgzf_error")
 
     def __init__(self, bases, filters, counts, status, spill=None):
         self.bases, self.filters, self.counts, self.status = bases, filters, counts, status
         self.n_lines, self.n_matched, self.depth_sum = int(status[1]), int(status[2]), int(status[3])
         self.line_offsets = None
         self.spill = spill                                   # SPILL_DTYPE records of the call, or None (no position has > 8 symbols)
+        self.bgzf_info = self.bgzf_error = None              # a file read as BGZF: its snpgpu_bgzf_info as a dict; what failed, in words, or None
 
 
 class Device(object):
@@ -461,13 +474,44 @@ class Device(object):
 
     @_again_on_spill_overflow
     def call_consensus_files(self, siteset, paths, params, want_counts=False, want_line_offsets=False,
-                             want_depth_sum=False, chunk_bytes=0, n_readers=0, n_staging=0, n_slots=0, exclude=None):
+                             want_depth_sum=False, chunk_bytes=0, n_readers=0, n_staging=0, n_slots=0, exclude=None, bgzf=False):
         """Streamed ingestion of pileup FILES (snpgpu_call_consensus_files): reader threads -> pinned staging -> copy
         stream -> scan of the tiles that have landed; no file is resident in host memory.
         Returns (results, rcs, stats): one ConsensusResult per path (``.line_offsets`` set when asked for), the per-file
         return codes (0, E_IO, E_PILEUP, E_UNSUPPORTED) and the StreamStats of the call.  Nothing is raised per file:
         use ``raise_file_status``.  exclude: per path, the site-set slots of that file's own exclude list (arrays; slots < 0
-        are ignored) — the file is called with SITE_EXCLUDED on them on top of the set's flags."""
+        are ignored) — the file is called with SITE_EXCLUDED on them on top of the set's flags.  bgzf: probe each path and send BGZF
+        files through snpgpu_call_consensus_bgzf_files (results in the caller's order, ``.bgzf_info`` / ``.bgzf_error`` set on them, line
+        offsets those of the PLAIN text); without it a BGZF file is read as the text it is not and refused as non-ASCII."""
+        compressed = [False] * len(paths)
+        if bgzf:                                  # (opt-in: call_consensus / call_consensus_batch; every other caller reads plain text only, as ever)
+            from . import pileup_text
+            compressed = [pileup_text.is_compressed(p) for p in paths]
+        if not any(compressed):
+            return self._call_consensus_files_of(False, siteset, paths, params, want_counts, want_line_offsets, want_depth_sum, chunk_bytes,
+                                                 n_readers, n_staging, n_slots, exclude)
+        # BGZF files go through the call that inflates them on the device, plain ones through the stream as ever; the results
+        # come back in the caller's order
+        results, rcs, stats = [None] * len(paths), np.zeros(len(paths), dtype=np.int32), None
+        for kind in (False, True):
+            idx = [i for i, c in enumerate(compressed) if c == kind]
+            if not idx:
+                continue
+            res, rc, st = self._call_consensus_files_of(kind, siteset, [paths[i] for i in idx], params, want_counts, want_line_offsets, want_depth_sum,
+                                                        chunk_bytes, n_readers, n_staging, n_slots, [exclude[i] for i in idx] if exclude is not None else None)
+            for k, i in enumerate(idx):
+                results[i], rcs[i] = res[k], rc[k]
+            if stats is None:
+                stats = st
+            else:
+                stats.bytes += st.bytes
+                stats.n_chunks += st.n_chunks
+                stats.seconds += st.seconds
+        return results, rcs, stats
+
+    def _call_consensus_files_of(self, compressed, siteset, paths, params, want_counts, want_line_offsets, want_depth_sum, chunk_bytes, n_readers,
+                                 n_staging, n_slots, exclude):
+        """One library call over files of one kind: snpgpu_call_consensus_files, or snpgpu_call_consensus_bgzf_files (compressed)."""
         n_files, n = len(paths), len(siteset)
         excl_off, excl_slots = _exclude_csr(exclude, n_files)
         enc = [os.fsencode(p) for p in paths]
@@ -480,16 +524,49 @@ class Device(object):
         rcs = np.zeros(max(n_files, 1), dtype=np.int32)
         opts = L.StreamOpts(int(chunk_bytes), int(n_staging), int(n_readers), int(n_slots), 1 if want_depth_sum else 0)
         stats = L.StreamStats()
-        self._check(self.lib.snpgpu_call_consensus_files(
-            self.ctx, siteset.handle, arr, n_files, C.byref(params), _ptr(excl_off), _ptr(excl_slots), _ptr(bases), _ptr(filters),
-            _ptr(counts), _ptr(line_off), _ptr(status), _ptr(rcs), C.byref(opts), C.byref(stats)))
+        infos = (L.BgzfInfo * max(n_files, 1))() if compressed else None
+        if compressed:
+            self._check(self.lib.snpgpu_call_consensus_bgzf_files(
+                self.ctx, siteset.handle, arr, n_files, C.byref(params), _ptr(excl_off), _ptr(excl_slots), _ptr(bases), _ptr(filters),
+                _ptr(counts), _ptr(line_off), _ptr(status), _ptr(rcs), C.byref(opts), C.byref(stats), infos))
+        else:
+            self._check(self.lib.snpgpu_call_consensus_files(
+                self.ctx, siteset.handle, arr, n_files, C.byref(params), _ptr(excl_off), _ptr(excl_slots), _ptr(bases), _ptr(filters),
+                _ptr(counts), _ptr(line_off), _ptr(status), _ptr(rcs), C.byref(opts), C.byref(stats)))
         results = []
         spill = self.read_symbol_spill(counts) if want_counts else None      # one spill per call: shared by its files
         for f in range(n_files):
             r = ConsensusResult(bases[f], filters[f], counts[f] if want_counts else None, status[f], spill)
             r.line_offsets = line_off[f] if want_line_offsets else None
+            if compressed:
+                r.bgzf_info = {name: getattr(infos[f], name) for name, _ in L.BgzfInfo._fields_ if name != "reserved"}
+                r.bgzf_error = _bgzf_error_text(paths[f], int(rcs[f]), infos[f])
             results.append(r)
         return results, rcs[:n_files], stats
+
+    @staticmethod
+    def bgzf_index(data):
+        """The block table of BGZF data in host memory (bytes / a uint8 array): (rc, BgzfBlock ctypes array of the valid blocks, info).
+        rc is 0 or the BGZF_E_* of the first bad header; no context is involved."""
+        lib = L.load()
+        a = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data
+        n, info = C.c_uint64(), L.BgzfInfo()
+        ptr = a.ctypes.data_as(C.c_void_p) if len(a) else None
+        lib.snpgpu_bgzf_index(ptr, len(a), None, 0, C.byref(n), C.byref(info))
+        blocks = (L.BgzfBlock * max(int(n.value), 1))()
+        rc = lib.snpgpu_bgzf_index(ptr, len(a), blocks, n.value, C.byref(n), C.byref(info))
+        return int(rc), (L.BgzfBlock * int(n.value)).from_buffer(blocks) if n.value else (L.BgzfBlock * 0)(), info
+
+    def bgzf_inflate_dev(self, d_compressed, compressed_bytes, blocks, d_out, out_capacity):
+        """snpgpu_bgzf_inflate_dev: the blocks of a HOST table (a BgzfBlock ctypes array) from device memory to device memory
+        (d_* are device pointers as ints).  Returns (status per block, info); raises SnpGpuError(E_ARG) before any launch when a block
+        leaves the compressed data or its text would pass out_capacity."""
+        n = len(blocks)
+        status = np.zeros(max(n, 1), dtype=np.uint32)
+        info = L.BgzfInfo()
+        self._check(self.lib.snpgpu_bgzf_inflate_dev(self.ctx, C.c_void_p(d_compressed) if d_compressed else None, int(compressed_bytes), blocks, n,
+                                                     C.c_void_p(d_out) if d_out else None, int(out_capacity), _ptr(status), C.byref(info)))
+        return status[:n], info
 
     def call_consensus_files_dev(self, siteset, paths, params, d_bases, d_filters, d_counts=0, d_line_off=0, want_depth_sum=False,
                                  chunk_bytes=0, n_readers=0, n_staging=0, n_slots=0, exclude=None):
@@ -733,6 +810,11 @@ class Device(object):
 
     def raise_file_status(self, path, rc, res, check=True, wanted=None):
         """Raise for one file of call_consensus_files the way call_consensus does for its single pileup (wanted: see site_error)."""
+        why = getattr(res, "bgzf_error", None)        # a compressed pileup that could not be inflated: the file, the block and the cause
+        if why and rc == L.E_IO:
+            raise PileupIOError(why)
+        if why:
+            raise PileupFormatError(why, None)
         if rc == L.E_IO:
             raise PileupIOError("cannot open or read the pileup file %s" % path)
         if rc in (L.E_PILEUP, L.E_UNSUPPORTED):

@@ -13,6 +13,7 @@ Still refused (what the characters would MEAN differs between text and bytes the
 (a multi-byte read base or quality is one symbol to the reference and several bytes to the kernels), and Unicode white space
 anywhere (str.split() breaks a field at U+00A0, U+2028 ...; the kernels split at ASCII white space).
 """
+import io
 import os
 import re
 import tempfile
@@ -115,7 +116,9 @@ def escaped_copy(pileup_path, directory=None):
     fd, tmp = tempfile.mkstemp(prefix=".snpgpu_names_", suffix=".pileup", dir=directory or _copy_directory(pileup_path))
     ok = False
     try:
-        with os.fdopen(fd, "wb") as out, open(pileup_path, "rb") as f:
+        from . import pileup_text
+        source = io.BytesIO(pileup_text.read_all(pileup_path)) if pileup_text.probe(pileup_path) == 1 else open(pileup_path, "rb")   # (a BGZF pileup: its text)
+        with os.fdopen(fd, "wb") as out, source as f:
             carry = b""
             while True:
                 block = f.read(CHUNK)

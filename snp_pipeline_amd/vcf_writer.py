@@ -187,23 +187,18 @@ def format_line_rows(pileup, line_offsets, recs, wide_index, wide, filter_names,
 def write_all_positions_vcf(path, sample_id, args, pileup_path, line_offsets, counts, spill=None):
     """The same file row by row in Python, from the per-line records of ``Device.call_all_lines``; CHROM and POS are the first two
     fields of the line itself.  The readable statement of the layout: the tests hold the library's rows against it."""
-    import mmap
+    from . import pileup_text
     filters = filter_descriptions(args.minConsFreq, args.minConsDpth, args.minConsStrdDpth, args.minConsStrdBias)
     names = [n for n, _ in filters]
     with open(path, "w") as f:
         f.write("\n".join(header_lines(sample_id, filters, args.vcfRefName)) + "\n")
         if len(line_offsets) == 0:
             return
-        with open(pileup_path, "rb") as pf:
-            mm = mmap.mmap(pf.fileno(), 0, access=mmap.ACCESS_READ)
-            try:
-                for i in range(len(line_offsets)):
-                    start = int(line_offsets[i]) - 1
-                    fields = mm[start:start + 256].split(None, 2)
-                    if len(fields) < 3:                          # a very long contig name: take the whole line
-                        end = mm.find(b"\n", start)
-                        fields = mm[start:end if end >= 0 else len(mm)].split(None, 2)
-                    f.write(row_from_counts(fields[0].decode("ascii"), int(fields[1]), counts[i], names,
-                                            args.vcfPreserveRefCase, args.vcfFailedSnpGt, spill=spill) + "\n")
-            finally:
-                mm.close()
+        with pileup_text.TextAt(pileup_path) as text:             # (plain or BGZF: offsets are those of the plain text)
+            for i in range(len(line_offsets)):
+                start = int(line_offsets[i]) - 1
+                fields = text.slice(start, 256).split(None, 2)
+                if len(fields) < 3:                              # a very long contig name: take the whole line
+                    fields = text.line(start).split(None, 2)
+                f.write(row_from_counts(fields[0].decode("ascii"), int(fields[1]), counts[i], names,
+                                        args.vcfPreserveRefCase, args.vcfFailedSnpGt, spill=spill) + "\n")
