@@ -117,21 +117,73 @@ def test_tile_kernels_against_numpy(d):
     d.tiles_gather_dev(dm.data_ptr(), n, rows.data_ptr(), cols.data_ptr(), 0, packed.data_ptr())      # no tiles: nothing happens
 
 
+def test_tile_kernels_second_turn_of_the_grid(d):
+    """More tiles than k_tiles_gather / k_tiles_scatter have workgroups (comm.hip: grid = min(n_tiles, 8 * n_cu)): the loops over
+    tiles turn twice.  Compared on the device; only the verdicts come back."""
+    import torch
+    n_cu = int(torch.cuda.get_device_properties(0).multi_processor_count)
+    cap = 8 * n_cu
+    n_tiles = cap + 1
+    assert n_tiles > cap
+    rng = np.random.default_rng(5)
+    # gather: from a 3 x 3-tile matrix, every source tile many times over
+    nt = 3
+    n = nt * 128
+    dm = torch.from_numpy(rng.integers(-1000, 1 << 30, size=(n, n), dtype=np.int32)).cuda()
+    tr, tc = rng.integers(0, nt, size=n_tiles), rng.integers(0, nt, size=n_tiles)
+    tr[[0, cap - 1, cap]], tc[[0, cap - 1, cap]] = [0, 1, 2], [2, 0, 1]                  # the turn's edge: three different tiles
+    rows, cols = torch.from_numpy(tr.astype(np.int32)).cuda(), torch.from_numpy(tc.astype(np.int32)).cuda()
+    packed = torch.full((n_tiles, 128, 128), -7, dtype=torch.int32, device="cuda")
+    d.tiles_gather_dev(dm.data_ptr(), n, rows.data_ptr(), cols.data_ptr(), n_tiles, packed.data_ptr())
+    torch.cuda.synchronize()
+    want = dm.view(nt, 128, nt, 128).permute(0, 2, 1, 3)[rows.long(), cols.long()]
+    assert want.shape == packed.shape and torch.equal(packed, want)
+    del want, packed
+    # scatter: tiles that all differ, to distinct places of a matrix just large enough; the background stays elsewhere
+    side = int(np.ceil(np.sqrt(n_tiles)))
+    assert side * side >= n_tiles > (side - 1) * (side - 1)
+    n2 = side * 128
+    tiles = torch.arange(n_tiles * 128 * 128, dtype=torch.int32, device="cuda").view(n_tiles, 128, 128)
+    places = rng.permutation(side * side)[:n_tiles]
+    r2, c2 = torch.from_numpy((places // side).astype(np.int32)).cuda(), torch.from_numpy((places % side).astype(np.int32)).cuda()
+    out = torch.full((n2, n2), -7, dtype=torch.int32, device="cuda")
+    d.tiles_scatter_dev(tiles.data_ptr(), r2.data_ptr(), c2.data_ptr(), n_tiles, out.data_ptr(), n2)
+    torch.cuda.synchronize()
+    want = torch.full((n2, n2), -7, dtype=torch.int32, device="cuda")
+    want.view(side, 128, side, 128).permute(0, 2, 1, 3)[r2.long(), c2.long()] = tiles
+    assert torch.equal(out, want)
+    assert int((out == -7).sum().item()) == (side * side - n_tiles) * 128 * 128          # (no tile holds a -7)
+
+
 @pytest.mark.parametrize("with_counts", [False, True])
 def test_group_check_equals_the_expressions_it_replaced(d, with_counts):
+    _group_check(d, with_counts, 9, 1237)
+
+
+@pytest.mark.parametrize("with_counts", [False, True])
+def test_group_check_second_turn_of_the_grid(d, with_counts):
+    """More samples than k_group_check has workgroups (comm.hip: grid = min(n_samples, 8 * n_cu)): the loop over samples turns twice."""
+    import torch
+    cap = 8 * int(torch.cuda.get_device_properties(0).multi_processor_count)
+    g = cap + 1
+    assert g > cap
+    _group_check(d, with_counts, g, 5)
+
+
+def _group_check(d, with_counts, g, S):
     import torch
     from snp_pipeline_amd import _lib as L
     rng = np.random.default_rng(11 + with_counts)
-    g, S = 9, 1237
+    rare = 1.0 if S > 100 else 30.0                               # (rows of a few sites: bad and spilled positions often enough to show)
     filt = rng.integers(0, 64, size=(g, S), dtype=np.uint8)
-    filt[rng.random((g, S)) < 0.002] |= 0x80
+    filt[rng.random((g, S)) < 0.002 * rare] |= 0x80
     line = (rng.random((g, S)) < 0.9) * rng.integers(1, 1 << 40, size=(g, S))
     counts = np.zeros((g, S, 128), dtype=np.uint8)
-    counts[:, :, 23] = np.where(rng.random((g, S)) < 0.003, L.ST_OK + 1 + rng.integers(0, 3, size=(g, S)), L.ST_OK)
-    spilled = rng.random((g, S)) < 0.01
+    counts[:, :, 23] = np.where(rng.random((g, S)) < 0.003 * rare, L.ST_OK + 1 + rng.integers(0, 3, size=(g, S)), L.ST_OK)
+    spilled = rng.random((g, S)) < 0.01 * rare
     counts[:, :, 17 + rng.integers(0, 3)][spilled] = 1
     wanted = (rng.random(S) < 0.6).astype(np.uint8)
-    excl = [np.sort(rng.choice(S, size=rng.integers(0, 40), replace=False)).astype(np.int32) for _ in range(g)]
+    excl = [np.sort(rng.choice(S, size=rng.integers(0, min(40, S + 1)), replace=False)).astype(np.int32) for _ in range(g)]
     eoff = np.zeros(g + 1, dtype=np.int32)
     np.cumsum([len(e) for e in excl], out=eoff[1:])
     d_filt, d_line, d_counts = torch.from_numpy(filt).cuda(), torch.from_numpy(line.astype(np.int64)).cuda(), torch.from_numpy(counts).cuda()

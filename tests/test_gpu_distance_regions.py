@@ -242,6 +242,63 @@ def test_small_steps_device_pointer_forms(d):
         d.dense_windows(np.array([5, -1, 7], dtype=np.int64), np.array([0, 3], dtype=np.uint32), [1], [15])
 
 
+def _in_regions_dev(d, q_g, q_p, reg_off, rs, re_):
+    """snpgpu_in_regions_dev on device copies of the host form's arguments; the flags, with guard bytes around them intact."""
+    import torch
+    d.use_torch_stream()
+    n, n_groups = len(q_p), len(reg_off) - 1
+    tg = torch.from_numpy(np.asarray(q_g, dtype=np.uint32).view(np.int32)).cuda()
+    tp = torch.from_numpy(np.asarray(q_p, dtype=np.int64)).cuda()
+    to = torch.from_numpy(np.asarray(reg_off, dtype=np.uint32).view(np.int32)).cuda()
+    ts = torch.from_numpy(np.concatenate([np.asarray(rs, dtype=np.int64), [0]])).cuda()     # (never empty: a group without regions reads nothing)
+    te = torch.from_numpy(np.concatenate([np.asarray(re_, dtype=np.int64), [0]])).cuda()
+    out = torch.full((n + 128,), 0xAB, dtype=torch.uint8, device="cuda")
+    d.in_regions_dev(tg.data_ptr(), tp.data_ptr(), n, to.data_ptr(), ts.data_ptr(), te.data_ptr(), n_groups, out.data_ptr() + 64)
+    torch.cuda.synchronize()
+    o = out.cpu().numpy()
+    assert (o[:64] == 0xAB).all() and (o[64 + n:] == 0xAB).all()
+    assert set(np.unique(o[64:64 + n]).tolist()) <= {0, 1}
+    return o[64:64 + n].astype(bool)
+
+
+@pytest.mark.parametrize("n_pos", [255, 256, 257])
+def test_in_regions_device_pointer_form(d, n_pos):
+    """snpgpu_in_regions_dev (one thread per position, workgroups of 256) against steps_oracle.in_region: positions at every
+    region's start and end and one on either side of each, a group without regions, group indices >= n_groups (flag 0)."""
+    rng = np.random.default_rng(n_pos)
+    regions = [[(10, 10), (12, 20), (1000, 1000), (1002, 5000)], [], [(0, 7)], [(5, 6), (8, 9), (3_000_000_000, np.iinfo(np.int64).max)]]
+    n_groups = len(regions)
+    reg_off = np.concatenate([[0], np.cumsum([len(r) for r in regions])]).astype(np.uint32)
+    rs = np.array([a for r in regions for a, _ in r], dtype=np.int64)
+    re_ = np.array([b for r in regions for _, b in r], dtype=np.int64)
+    q = []
+    for g, regs in enumerate(regions):
+        for a, b in regs:
+            for p in (a - 1, a, a + 1, b - 1, b, min(b, np.iinfo(np.int64).max - 1) + 1):
+                q += [(g, p), (1, p), (n_groups, p), (n_groups + 7, p), (0xFFFFFFFF, p)]     # ... the empty group, and groups that do not exist
+    assert len(q) == 240 < n_pos
+    q += [(int(rng.integers(0, n_groups + 2)), int(rng.integers(-5, 6000))) for _ in range(n_pos - len(q))]
+    q = [q[i] for i in rng.permutation(n_pos)]
+    q_g, q_p = np.array([g for g, _ in q], dtype=np.uint32), np.array([p for _, p in q], dtype=np.int64)
+    want = np.array([g < n_groups and so.in_region(p, regions[g]) for g, p in q])
+    assert want.any() and not want.all() and not want[q_g == 1].any() and not want[q_g >= n_groups].any()
+    got = _in_regions_dev(d, q_g, q_p, reg_off, rs, re_)
+    assert np.array_equal(got, want)
+    assert np.array_equal(d.in_regions(q_g, q_p, reg_off, rs, re_), want)                      # the host form, same inputs
+
+
+def test_in_regions_device_pointer_form_on_the_golden_vectors(d, steps_vectors):
+    """The in_region vectors of test_region_golden_vectors through the device-pointer form: one group per vector, one launch."""
+    vs = steps_vectors["in_region"]
+    reg_off = np.concatenate([[0], np.cumsum([len(v["regions"]) for v in vs])]).astype(np.uint32)
+    rs = np.array([r[0] for v in vs for r in v["regions"]], dtype=np.int64)
+    re_ = np.array([r[1] for v in vs for r in v["regions"]], dtype=np.int64)
+    got = _in_regions_dev(d, np.arange(len(vs)), [v["pos"] for v in vs], reg_off, rs, re_)
+    assert got.tolist() == [bool(v["out"]) for v in vs]
+    for v in vs:                                                                               # (the vectors say what the oracle says)
+        assert so.in_region(v["pos"], [tuple(r) for r in v["regions"]]) == v["out"]
+
+
 def test_distance_unequal_lengths_and_no_sites(d):
     """utils.calculate_sequence_distance walks range(len(seq1)) (utils.py:1156-1158): a longer second sequence is cut, a
     shorter one raises IndexError.  And a matrix without sites: all distances 0, nothing read."""
