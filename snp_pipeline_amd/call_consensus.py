@@ -68,12 +68,11 @@ class _ValidUtf8(devmod.PileupFormatError):
 def _raise_as_reference(err, pileup_path=None, every_line_is_a_record=False):
     """Re-raise a device-detected malformed pileup as the exception class the reference raises for it, so that the
     error log names the same exception type (utils.handle_sample_exception prints ``exc_type.__name__``).
-    every_line_is_a_record: the --vcfAllPos reader (pileup.py:418-421) builds a Record from every line, and a line with fewer
-    than two fields then ends with IndexError (pileup.py:223-224) where the reader with a position set fails to unpack two
-    values (ValueError, pileup.py:425)."""
+    every_line_is_a_record: the error comes from the --vcfAllPos reader, whose class for a line with fewer than two fields is
+    another one (Device.every_line_is_a_record holds the rule)."""
+    if every_line_is_a_record:
+        devmod.Device.every_line_is_a_record(err)
     exc = getattr(err, "reference_exception", None)
-    if every_line_is_a_record and getattr(err, "scan_code", 0) == 1:
-        exc = IndexError
     if getattr(err, "scan_code", 0) == 3 and pileup_path:
         # A byte >= 0x80.  The reference reads the pileup as text (pileup.py:405, the locale's encoding: UTF-8 on the
         # pipeline's platforms), so a file that is not valid UTF-8 ends its run with UnicodeDecodeError: the same here.

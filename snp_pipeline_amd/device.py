@@ -396,6 +396,15 @@ class Device(object):
         return err, off
 
     @staticmethod
+    def every_line_is_a_record(err):
+        """The reader without a position set (--vcfAllPos, pileup.py:418-421) builds a Record from EVERY line: a line with fewer than
+        two fields ends it with IndexError (pileup.py:223-224), where the reader with a position set fails to unpack two values
+        (ValueError, pileup.py:425).  The all-lines calls that check every line say so in the error they raise."""
+        if getattr(err, "scan_code", 0) == 1:
+            err.reference_exception = IndexError
+        return err
+
+    @staticmethod
     def raise_scan_status(status):
         err, _ = Device.scan_error(status)
         if err is not None:
@@ -607,12 +616,15 @@ class Device(object):
             if rc == L.E_IO:
                 raise PileupIOError("cannot open or read the pileup file %s" % path)
             if rc in (L.E_PILEUP, L.E_UNSUPPORTED) and int(status[0]) != 0xFFFFFFFFFFFFFFFF:
-                if check and 0 < n_lines.value <= cap:          # the records are there: a Record-level failure earlier in the file goes first
-                    keep = np.nonzero(flags[:n_lines.value])[0] if listed_only else slice(0, n_lines.value)
-                    res = ConsensusResult(None, None, counts[:n_lines.value][keep], status)
-                    res.line_offsets = off[:n_lines.value][keep]
-                    self.raise_first_error(status, res, True)
-                self.raise_scan_status(status)
+                try:
+                    if check and 0 < n_lines.value <= cap:      # the records are there: a Record-level failure earlier in the file goes first
+                        keep = np.nonzero(flags[:n_lines.value])[0] if listed_only else slice(0, n_lines.value)
+                        res = ConsensusResult(None, None, counts[:n_lines.value][keep], status)
+                        res.line_offsets = off[:n_lines.value][keep]
+                        self.raise_first_error(status, res, True)
+                    self.raise_scan_status(status)
+                except PileupFormatError as err:
+                    raise self.every_line_is_a_record(err) if check and not listed_only else err
             self._check(rc)
             if n_lines.value <= cap:
                 break
@@ -679,11 +691,14 @@ class Device(object):
             raise IOError("cannot write %s" % vcf_path)
         has_bad = bad_line.value != 0xFFFFFFFFFFFFFFFF
         if rc in (L.E_PILEUP, L.E_UNSUPPORTED) and int(status[0]) != 0xFFFFFFFFFFFFFFFF:
-            if check and has_bad:                                 # a Record-level failure earlier in the file goes first
-                res = ConsensusResult(None, None, bad, status)
-                res.line_offsets = np.array([bad_off.value], dtype=np.uint64)
-                self.raise_first_error(status, res, True)
-            self.raise_scan_status(status)
+            try:
+                if check and has_bad:                             # a Record-level failure earlier in the file goes first
+                    res = ConsensusResult(None, None, bad, status)
+                    res.line_offsets = np.array([bad_off.value], dtype=np.uint64)
+                    self.raise_first_error(status, res, True)
+                self.raise_scan_status(status)
+            except PileupFormatError as err:
+                raise self.every_line_is_a_record(err) if check and not only_listed else err
         self._check(rc)
         if has_bad:
             res = ConsensusResult(None, None, bad, status)

@@ -13,6 +13,7 @@ from snp_pipeline_amd import _lib as L
 from snp_pipeline_amd import device as dev
 from snp_pipeline_amd import vcf_writer
 from tests.gpu_util import get_device
+from tests.lines_cases import line_starts
 
 pytestmark = pytest.mark.gpu
 
@@ -109,6 +110,7 @@ def test_line_records_of_32_bytes_equal_the_full_ones(d, tmp_path, seed, genome_
     off2, recs, widx, wide = d.call_all_lines_compact(ss, path, prm, capacity=len(off) // 2, wide_capacity=1)      # (both arrays too small at first)
     spill2 = d.last_spill
     assert len(off) == data.count(b"\n") and np.array_equal(off, off2)
+    assert np.array_equal(off.astype(np.int64), line_starts(data) + 1)      # the offsets against the statement, not only against themselves
     flags2, counts2 = dev.expand_line_records(recs, widx, wide)
     assert np.array_equal(flags, flags2)
     _same_records(counts, spill, counts2, spill2)

@@ -10,6 +10,7 @@ from oracle import pileup_oracle as po
 from oracle import threshold_cases as tc
 from snp_pipeline_amd import _lib as L
 from snp_pipeline_amd import device as dev
+from tests.gpu_util import check_record as _check_record
 
 pytestmark = pytest.mark.gpu
 
@@ -41,22 +42,6 @@ def _is_wide(rec):
     ranked = rec.most_common_good_bases or []
     big = any(max(rec.base_good_depth[s], rec.forward_base_good_depth.get(s, 0), rec.reverse_base_good_depth.get(s, 0)) > 65535 for s in ranked)
     return big or len(ranked) > dev.LINE_SYMS
-
-
-def _check_record(c, rec, p, where):
-    """A full record of the device against the oracle's Record of the line: depths, ranking, per-symbol counts, the caller's output."""
-    assert c["status"] == L.ST_OK, where
-    assert (int(c["raw_depth"]), int(c["good_depth"]), int(c["fwd_good_depth"]), int(c["rev_good_depth"])) == \
-        (rec.raw_depth, rec.good_depth, rec.forward_good_depth, rec.reverse_good_depth), where
-    ranked = rec.most_common_good_bases or []
-    assert int(c["n_symbols"]) == len(ranked) <= L.MAX_SYMS, where
-    for r, sym in enumerate(ranked):
-        assert (int(c["sym"][r]), int(c["total"][r]), int(c["fwd"][r]), int(c["rev"][r])) == \
-            (sym, rec.base_good_depth[sym], rec.forward_base_good_depth.get(sym, 0), rec.reverse_base_good_depth.get(sym, 0)), (where, r)
-    for r in range(len(ranked), L.MAX_SYMS):
-        assert (int(c["sym"][r]), int(c["total"][r]), int(c["fwd"][r]), int(c["rev"][r])) == (0, 0, 0, 0), (where, r)
-    base, mask = po.call_record(rec, p)
-    assert (int(c["cons_base"]), int(c["filters"])) == (base, mask), where
 
 
 @pytest.fixture(scope="module")
