@@ -1,5 +1,6 @@
 """The scan's tile stream at its seams: a site line starts a few bytes before every 4 KiB tile end, so that its name and position
-are read from the halo the tile's last DMA instruction fetches (the bytes the next tile's first instruction reads again)."""
+are read from the halo the tile's last DMA instruction fetches (the bytes the next tile's first instruction reads again).  The
+distances here are drawn at random; tests/test_gpu_scan_parse.py (case F) sweeps every distance from 0 to 72 bytes deterministically."""
 import random
 
 import pytest
