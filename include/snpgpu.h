@@ -687,6 +687,49 @@ int  snpgpu_fasta_load(const char *path, uint64_t n_records, uint64_t row_stride
 int  snpgpu_write_distance_tsv(const char *path, int layout, const char *ids, const uint64_t *id_off, uint32_t n,
                                const int32_t *matrix, uint64_t row_stride);
 
+/* ---- close pairs and SNP-threshold clusters (csrc/clusters.hip) -------------------------------------------------------
+ * Additive entries of ABI 7: they extend what distance.py:93-106 hands the user and change nothing it writes.  The reference
+ * prints every ordered pair (distance.py:100-106); these keep the rows with Distance <= T and group the samples that a chain
+ * of such pairs joins, on the device, from the matrix snpgpu_distance_packed_dev leaves there.
+ *
+ * snpgpu_close_pairs_dev: rows [row_lo, row_hi) of the device int32 matrix (row i at d_matrix + i * row_stride elements,
+ * row_stride >= n; rows outside the range are never read, so d_matrix may be where row 0 WOULD lie in front of a band of
+ * rows; 4-byte aligned) as a CSR of their entries <= threshold over the columns j < n — ascending j, the diagonal included,
+ * whatever lies between n and row_stride ignored: d_row_off[row_hi - row_lo + 1], d_col[], d_dist[].  No atomics place the
+ * entries: the same matrix gives the same bytes.  *out_n (host) is always set to the number of entries; when it exceeds
+ * `capacity` nothing else is written, and capacity 0 only counts.  The call waits for the stream once (the count). */
+int  snpgpu_close_pairs_dev(snpgpu_ctx *ctx, const int32_t *d_matrix, uint32_t n, uint64_t row_stride, uint32_t row_lo,
+                            uint32_t row_hi, int32_t threshold, uint64_t capacity, uint64_t *d_row_off, uint32_t *d_col,
+                            int32_t *d_dist, uint64_t *out_n);
+/* Host form (as snpgpu_distance, distance.py:93-98): packs the symbols, computes the matrix on the device, thresholds it there
+ * and copies only the CSR back — with out_matrix null the n x n matrix never crosses the host link.  out_matrix not null (a
+ * caller that writes the reference's two tables as well): the n x n int32 matrix of snpgpu_distance is copied there too, from
+ * the same computation, whatever the capacity.  Same capacity protocol for the CSR: a call whose count exceeds `capacity`
+ * has computed the matrix for the count alone, and the caller's second call computes it again. */
+int  snpgpu_close_pairs(snpgpu_ctx *ctx, const uint8_t *symbols, uint32_t n_rows, uint32_t n_sites, int32_t threshold,
+                        uint64_t capacity, uint64_t *out_row_off, uint32_t *out_col, int32_t *out_dist, uint64_t *out_n,
+                        int32_t *out_matrix);
+/* Connected components of the graph of such a CSR over n nodes (d_row_off[n + 1], n_edges entries; one or both directions of
+ * an edge, diagonal entries allowed) at every one of n_thresholds thresholds (HOST array) in one call: an entry takes part at
+ * threshold t when its distance is <= t.  d_out_numbers[t * n + i] = the cluster number of node i at thresholds[t]: clusters
+ * are numbered 1, 2, ... in the order of their smallest node; out_n_clusters[t] (host) = how many.  Min-label hooking and
+ * pointer jumping until a round changes nothing (the round count is not bounded in advance; each round waits for the stream). */
+int  snpgpu_clusters_dev(snpgpu_ctx *ctx, uint32_t n, const uint64_t *d_row_off, const uint32_t *d_col, const int32_t *d_dist,
+                         uint64_t n_edges, const int32_t *thresholds, uint32_t n_thresholds, uint32_t *d_out_numbers,
+                         uint32_t *out_n_clusters);
+/* Host-array form of snpgpu_clusters_dev; SNPGPU_E_ARG when the offsets do not rise from 0 to n_edges. */
+int  snpgpu_clusters(snpgpu_ctx *ctx, uint32_t n, const uint64_t *row_off, const uint32_t *col, const int32_t *dist,
+                     uint64_t n_edges, const int32_t *thresholds, uint32_t n_thresholds, uint32_t *out_numbers,
+                     uint32_t *out_n_clusters);
+/* The two texts (host code, the thread scheme and CPU budget of snpgpu_write_distance_tsv): the close-pairs file is the
+ * header and the rows of the pairwise file of distance.py:100-106 that the HOST CSR holds ("id_i\tid_col\tdist\n", row by
+ * row); the clusters file is "Id\t" + the thresholds joined by TAB, then one row per id: the id and numbers[t * n + i] for
+ * every t.  SNPGPU_E_IO when the file cannot be created or written. */
+int  snpgpu_write_close_pairs_tsv(const char *path, const char *ids, const uint64_t *id_off, uint32_t n,
+                                  const uint64_t *row_off, const uint32_t *col, const int32_t *dist);
+int  snpgpu_write_clusters_tsv(const char *path, const char *ids, const uint64_t *id_off, uint32_t n,
+                               const int32_t *thresholds, uint32_t n_thresholds, const uint32_t *numbers);
+
 /* ---- the exchange steps of the sharded path: RCCL over xGMI, one process per GPU ------------------------
  * The reference fans out one process per sample (run.py:704-718, `run_array` with `max_processes`) over a shared file system
  * and has no exchange step; sharded over GPUs the hot path has three: C1, the all-gather of the per-rank SNP site keys

@@ -207,6 +207,10 @@ def parse_argument_list(argv):
     sub.add_argument("-f", "--force", dest="forceFlag", action="store_true", help="Force processing even when result file already exists and is newer than inputs")
     sub.add_argument("-p", "--pairs", dest="pairwiseFile", type=str, default=None, metavar="FILE", help="Relative or absolute path to the pairwise distance output file.")
     sub.add_argument("-m", "--matrix", dest="matrixFile", type=str, default=None, metavar="FILE", help="Relative or absolute path to the distance matrix output file.")
+    sub.add_argument("--amdClosePairs", dest="amdClosePairsFile", type=str, default=None, metavar="FILE", help="Extension of this build: output file with the rows of the pairwise file whose distance is at most --amdMaxPairDistance, in the pairwise file's order; computed on the device, the full matrix is not written.")
+    sub.add_argument("--amdMaxPairDistance", dest="amdMaxPairDistance", type=int, default=None, metavar="INT", help="Extension of this build: the largest distance of a row of the --amdClosePairs file.")
+    sub.add_argument("--amdClusters", dest="amdClustersFile", type=str, default=None, metavar="FILE", help="Extension of this build: output file with every sample's single-linkage cluster number at each threshold of --amdClusterThresholds (samples joined by a chain of pairs within the threshold; clusters numbered from 1 in order of their first sample).")
+    sub.add_argument("--amdClusterThresholds", dest="amdClusterThresholds", type=int, nargs="+", default=None, metavar="INT", help="Extension of this build: the SNP thresholds of the --amdClusters file; sorted and made unique.")
     _common(sub)
     sub.set_defaults(func=distance.calculate_snp_distances, excepthook=utils.handle_global_exception)
 

@@ -8,6 +8,7 @@
 #include <string.h>
 #include <unistd.h>
 
+#include <algorithm>
 #include <thread>
 #include <vector>
 
@@ -205,4 +206,130 @@ extern "C" int snpgpu_write_distance_tsv(const char *path, int layout, const cha
     }
     if (close(fd) != 0) failed = true;
     return failed ? SNPGPU_E_IO : SNPGPU_OK;
+}
+
+// ---- close pairs and clusters (additive: the rows of distance.py:93-106 under a threshold, and their single-linkage groups) ----
+namespace {
+
+// The thread scheme of snpgpu_write_distance_tsv for any text of n independent row blocks: header(sink) writes header_bytes
+// bytes, size_rows(r0, r1) is the byte length of the rows [r0, r1), format_rows_of(sink, r0, r1) writes them.  `work`: the
+// number of values the file holds (below 2^22 one thread writes it with plain write() calls).  `values_before`: null when every
+// row holds the same number of values, else n + 1 rising counts (a CSR's row offsets): the blocks then hold equal shares of the
+// values, not of the rows, so that a few dense rows do not leave one thread with the whole file (a single row is never split).
+template <typename Head, typename Size, typename Format>
+int write_row_blocks(const char *path, uint32_t n, uint64_t work, const uint64_t *values_before, uint64_t header_bytes, Head header, Size size_rows,
+                     Format format_rows_of) {
+    unsigned T = snpgpu_writer_threads(0);
+    if (work < ((uint64_t)1 << 22)) T = 1;
+    if (T > n) T = n ? n : 1;
+    if (T <= 1) {
+        FileOut o(path);
+        if (o.failed) return SNPGPU_E_IO;
+        header(o);
+        format_rows_of(o, 0u, n);
+        return o.finish();
+    }
+    std::vector<uint64_t> block_bytes(T, 0);
+    auto first_row = [&](unsigned t) -> uint32_t {
+        if (t >= T) return n;
+        if (!values_before) return (uint32_t)((uint64_t)n * t / T);
+        const uint64_t want = (uint64_t)((unsigned __int128)work * t / T);          // the first row that starts at or behind this share
+        return (uint32_t)(std::lower_bound(values_before, values_before + n, want) - values_before);
+    };
+    auto block = [&](unsigned t, uint32_t &r0, uint32_t &r1) { r0 = first_row(t); r1 = first_row(t + 1); };
+    auto size_block = [&](unsigned t) { uint32_t r0, r1; block(t, r0, r1); block_bytes[t] = size_rows(r0, r1); };
+    {
+        std::vector<std::thread> th;
+        for (unsigned t = 1; t < T; ++t) th.emplace_back(size_block, t);
+        size_block(0);
+        for (auto &x : th) x.join();
+    }
+    std::vector<uint64_t> at(T + 1, header_bytes);
+    for (unsigned t = 0; t < T; ++t) at[t + 1] = at[t] + block_bytes[t];
+    const int fd = open(path, O_WRONLY | O_CREAT | O_TRUNC | O_CLOEXEC, 0666);
+    if (fd < 0) return SNPGPU_E_IO;
+    bool failed = ftruncate(fd, (off_t)at[T]) != 0;
+    {
+        RangeOut h(fd, 0);
+        header(h);
+        h.flush();
+        failed = failed || h.failed || h.at != header_bytes;
+    }
+    std::vector<uint8_t> bad(T, 0);
+    auto write_block = [&](unsigned t) {
+        uint32_t r0, r1;
+        block(t, r0, r1);
+        RangeOut o(fd, at[t]);
+        format_rows_of(o, r0, r1);
+        o.flush();
+        bad[t] = o.failed || o.at != at[t + 1];
+    };
+    if (!failed) {
+        std::vector<std::thread> th;
+        for (unsigned t = 1; t < T; ++t) th.emplace_back(write_block, t);
+        write_block(0);
+        for (auto &x : th) x.join();
+        for (unsigned t = 0; t < T; ++t) failed = failed || bad[t];
+    }
+    if (close(fd) != 0) failed = true;
+    return failed ? SNPGPU_E_IO : SNPGPU_OK;
+}
+
+}  // namespace
+
+extern "C" int snpgpu_write_close_pairs_tsv(const char *path, const char *ids, const uint64_t *id_off, uint32_t n, const uint64_t *row_off,
+                                            const uint32_t *col, const int32_t *dist) {
+    if (!path || (n && (!ids || !id_off || !row_off))) return SNPGPU_E_ARG;
+    const uint64_t n_edges = n ? row_off[n] : 0;
+    if (n && (row_off[0] != 0 || (n_edges && (!col || !dist)))) return SNPGPU_E_ARG;
+    for (uint32_t i = 0; i < n; ++i)
+        if (row_off[i] > row_off[i + 1]) return SNPGPU_E_ARG;
+    for (uint64_t e = 0; e < n_edges; ++e)
+        if (col[e] >= n) return SNPGPU_E_ARG;
+    auto len = [&](uint32_t i) { return id_off[i + 1] - id_off[i]; };
+    auto header = [&](auto &o) { o.put("Seq1\tSeq2\tDistance\n", 19); };                          // distance.py:100
+    auto size_rows = [&](uint32_t r0, uint32_t r1) {
+        uint64_t total = 0;
+        for (uint32_t i = r0; i < r1; ++i)
+            for (uint64_t e = row_off[i]; e < row_off[i + 1]; ++e) total += len(i) + len(col[e]) + digits_i32(dist[e]) + 3;
+        return total;
+    };
+    auto format = [&](auto &o, uint32_t r0, uint32_t r1) {
+        for (uint32_t i = r0; i < r1 && !o.failed; ++i)
+            for (uint64_t e = row_off[i]; e < row_off[i + 1]; ++e) {                             // "%s\t%s\t%i\n" of distance.py:105-106
+                o.put(ids + id_off[i], (size_t)len(i)); o.put('\t');
+                o.put(ids + id_off[col[e]], (size_t)len(col[e])); o.put('\t');
+                o.put_i32(dist[e]); o.put('\n');
+            }
+    };
+    return write_row_blocks(path, n, n_edges, row_off, 19, header, size_rows, format);
+}
+
+extern "C" int snpgpu_write_clusters_tsv(const char *path, const char *ids, const uint64_t *id_off, uint32_t n, const int32_t *thresholds,
+                                         uint32_t n_thresholds, const uint32_t *numbers) {
+    const uint32_t k = n_thresholds;
+    if (!path || (k && !thresholds) || (n && (!ids || !id_off || (k && !numbers)))) return SNPGPU_E_ARG;
+    uint64_t header_bytes = 3 + (k ? k : 1);                        // "Id\t", k - 1 separators, "\n"
+    for (uint32_t t = 0; t < k; ++t) header_bytes += digits_i32(thresholds[t]);
+    auto header = [&](auto &o) {
+        o.put("Id\t", 3);
+        for (uint32_t t = 0; t < k; ++t) { if (t) o.put('\t'); o.put_i32(thresholds[t]); }
+        o.put('\n');
+    };
+    auto size_rows = [&](uint32_t r0, uint32_t r1) {
+        uint64_t total = 0;
+        for (uint32_t i = r0; i < r1; ++i) {
+            total += id_off[i + 1] - id_off[i] + k + 1;
+            for (uint32_t t = 0; t < k; ++t) total += digits_i32((int32_t)numbers[(size_t)t * n + i]);
+        }
+        return total;
+    };
+    auto format = [&](auto &o, uint32_t r0, uint32_t r1) {
+        for (uint32_t i = r0; i < r1 && !o.failed; ++i) {
+            o.put(ids + id_off[i], (size_t)(id_off[i + 1] - id_off[i]));
+            for (uint32_t t = 0; t < k; ++t) { o.put('\t'); o.put_i32((int32_t)numbers[(size_t)t * n + i]); }
+            o.put('\n');
+        }
+    };
+    return write_row_blocks(path, n, (uint64_t)n * k, nullptr, header_bytes, header, size_rows, format);
 }

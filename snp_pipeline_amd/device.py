@@ -1069,6 +1069,68 @@ class Device(object):
         self._check(self.lib.snpgpu_distance_packed_dev(self.ctx, C.c_void_p(d_packed), n_rows, n_sites, tile_rank,
                                                         tile_nranks, C.c_void_p(d_out)))
 
+    # ---- close pairs and clusters (additive to distance.py:93-106) ------------------------------
+    def close_pairs_dev(self, d_matrix, n, row_stride, row_lo, row_hi, threshold, capacity=0, d_row_off=0, d_col=0, d_dist=0):
+        """Rows [row_lo, row_hi) of a device int32 matrix as a CSR of the entries <= threshold (columns < n, ascending).  Returns
+        the number of entries; the three device arrays are written only when 0 < capacity and the number fits."""
+        opt = lambda v: C.c_void_p(int(v)) if v else None     # noqa: E731
+        out_n = C.c_uint64(0)
+        self._check(self.lib.snpgpu_close_pairs_dev(self.ctx, C.c_void_p(int(d_matrix)), int(n), int(row_stride), int(row_lo), int(row_hi), int(threshold),
+                                                    int(capacity), opt(d_row_off), opt(d_col), opt(d_dist), C.byref(out_n)))
+        return int(out_n.value)
+
+    def close_pairs(self, symbols, threshold, capacity=None, want_matrix=False):
+        """symbols: (n, s) uint8 array of sequence bytes.  Returns (row_off uint64 [n + 1], col uint32, dist int32): per row of the
+        distance matrix its entries <= threshold, columns ascending.  The matrix itself stays on the device — unless want_matrix,
+        which adds the (n, n) int32 matrix of ``distance`` from the same computation as a fourth value.
+
+        The first call has room for every entry up to 2^26 of them (untouched pages of the two arrays cost nothing), so below
+        8 192 samples there is never a second; beyond, an answer of more than max(64 n, 2^26) entries costs a second call, which
+        uploads, packs and computes the matrix again."""
+        sym = np.ascontiguousarray(symbols, dtype=np.uint8)
+        n, s = sym.shape
+        row_off = np.zeros(n + 1, dtype=np.uint64)
+        mat = np.zeros((n, n), dtype=np.int32) if want_matrix else None
+        if n == 0:
+            empty = (row_off, np.zeros(0, np.uint32), np.zeros(0, np.int32))
+            return empty + (mat,) if want_matrix else empty
+        cap = int(capacity) if capacity else min(n * n, max(64 * n, 1 << 26))
+        have_matrix = False
+        while True:
+            col, dist = np.zeros(cap, dtype=np.uint32), np.zeros(cap, dtype=np.int32)
+            out_n = C.c_uint64(0)
+            self._check(self.lib.snpgpu_close_pairs(self.ctx, _ptr(sym) if sym.size else None, n, s, int(threshold), cap, _ptr(row_off), _ptr(col), _ptr(dist),
+                                                    C.byref(out_n), _ptr(mat) if want_matrix and not have_matrix else None))
+            have_matrix = True
+            if out_n.value <= cap:
+                csr = (row_off, col[:out_n.value], dist[:out_n.value])
+                return csr + (mat,) if want_matrix else csr
+            cap = int(out_n.value)
+
+    def clusters_dev(self, n, d_row_off, d_col, d_dist, n_edges, thresholds, d_out_numbers):
+        """Single-linkage cluster numbers of a device CSR at every threshold into d_out_numbers[len(thresholds)][n] (uint32);
+        returns the number of clusters per threshold."""
+        opt = lambda v: C.c_void_p(int(v)) if v else None     # noqa: E731
+        thr = np.ascontiguousarray(thresholds, dtype=np.int32)
+        counts = np.zeros(len(thr), dtype=np.uint32)
+        self._check(self.lib.snpgpu_clusters_dev(self.ctx, int(n), opt(d_row_off), opt(d_col), opt(d_dist), int(n_edges), _ptr(thr) if len(thr) else None,
+                                                 len(thr), opt(d_out_numbers), _ptr(counts) if len(thr) else None))
+        return counts
+
+    def clusters(self, n, row_off, col, dist, thresholds):
+        """Host-array form: returns (numbers uint32 [len(thresholds)][n], number of clusters per threshold)."""
+        off = np.ascontiguousarray(row_off, dtype=np.uint64)
+        c = np.ascontiguousarray(col, dtype=np.uint32)
+        d = np.ascontiguousarray(dist, dtype=np.int32)
+        thr = np.ascontiguousarray(thresholds, dtype=np.int32)
+        if len(off) != n + 1 or len(c) != len(d):
+            raise ValueError("row_off holds n + 1 offsets, col and dist one entry per edge")
+        numbers = np.zeros((len(thr), n), dtype=np.uint32)
+        counts = np.zeros(len(thr), dtype=np.uint32)
+        self._check(self.lib.snpgpu_clusters(self.ctx, int(n), _ptr(off), _ptr(c) if len(c) else None, _ptr(d) if len(d) else None, len(c),
+                                             _ptr(thr) if len(thr) else None, len(thr), _ptr(numbers) if numbers.size else None, _ptr(counts) if len(thr) else None))
+        return numbers, counts
+
     # ---- filter_regions ------------------------------------------------------------------------
     def dense_windows(self, positions, seg_off, max_snps, windows):
         pos = np.ascontiguousarray(positions, dtype=np.int64)

@@ -36,9 +36,10 @@ def distance_matrix(dev, seqs):
     return ids, dev.distance(sym)
 
 
-def distance_of_matrix(dev, file_ids, sym, lens):
-    """distance_matrix for the arrays of snp_matrix.load_matrix (no Python strings in between): equal ids keep their last
-    record (the reference's dict, distance.py:80-84), rows go into sorted-id order, lengths follow the same rule."""
+def _sorted_rows(file_ids, sym, lens):
+    """The arrays of snp_matrix.load_matrix in the order the distance step works in: equal ids keep their last record (the
+    reference's dict, distance.py:80-84), rows go into sorted-id order, lengths follow the rule of distance_matrix.  Returns
+    (ids, rows): rows is None without records, else the (n, s) byte matrix (s may be 0)."""
     last = {}
     for r, i in enumerate(file_ids):
         last[i] = r
@@ -46,15 +47,94 @@ def distance_of_matrix(dev, file_ids, sym, lens):
     rows = np.asarray([last[i] for i in ids], dtype=np.int64)
     n = len(ids)
     if n == 0:
-        return ids, np.zeros((0, 0), dtype=np.int32)
+        return ids, None
     ordered = lens[rows]
     if (ordered[1:] < ordered[:-1]).any():
         raise IndexError("string index out of range")                         # what seq2[pos] raises in utils.py:1158
     if sym.shape[1] == 0:
-        return ids, np.zeros((n, n), dtype=np.int32)
+        return ids, np.zeros((n, 0), dtype=np.uint8)
     if not np.array_equal(rows, np.arange(len(file_ids))):
         sym = sym[rows]                                                         # (snp_matrix writes sorted sample order: usually a no-op)
-    return ids, dev.distance(np.ascontiguousarray(sym))
+    return ids, np.ascontiguousarray(sym)
+
+
+def distance_of_matrix(dev, file_ids, sym, lens):
+    """distance_matrix for the arrays of snp_matrix.load_matrix (no Python strings in between)."""
+    ids, rows = _sorted_rows(file_ids, sym, lens)
+    n = len(ids)
+    if rows is None:
+        return ids, np.zeros((0, 0), dtype=np.int32)
+    if rows.shape[1] == 0:
+        return ids, np.zeros((n, n), dtype=np.int32)
+    return ids, dev.distance(rows)
+
+
+def close_pairs_of_matrix(dev, file_ids, sym, lens, threshold, want_matrix=False):
+    """As distance_of_matrix, but only what lies within `threshold` SNPs comes back: (ids, row_off, col, dist), per id the
+    entries d <= threshold of its row of the matrix in ascending column order, the diagonal included — the rows of the pairwise
+    file (distance.py:100-106) under the threshold.  The matrix is computed and thresholded on the device and stays there;
+    want_matrix (the two tables are wanted as well) adds it as a fifth value, from the same computation."""
+    ids, rows = _sorted_rows(file_ids, sym, lens)
+    if rows is None:
+        empty = (ids, np.zeros(1, dtype=np.uint64), np.zeros(0, dtype=np.uint32), np.zeros(0, dtype=np.int32))
+        return empty + (np.zeros((0, 0), dtype=np.int32),) if want_matrix else empty
+    return (ids,) + tuple(dev.close_pairs(rows, threshold, want_matrix=want_matrix))
+
+
+def filter_pairs(row_off, col, dist, threshold):
+    """The entries d <= threshold of a CSR, in place and order."""
+    keep = np.asarray(dist) <= threshold
+    kept_before = np.concatenate((np.zeros(1, dtype=np.uint64), np.cumsum(keep, dtype=np.uint64)))
+    return kept_before[np.asarray(row_off, dtype=np.int64)], np.asarray(col)[keep], np.asarray(dist)[keep]
+
+
+def cluster_thresholds(values):
+    """Thresholds as the clusters file lists them: ascending, each once."""
+    return sorted(set(int(v) for v in values))
+
+
+def _id_table(ids):
+    names = [i.encode("utf-8") for i in ids]
+    off = np.zeros(len(names) + 1, dtype=np.uint64)
+    np.cumsum([len(b) for b in names], out=off[1:])
+    return b"".join(names), off
+
+
+def write_close_pairs(path, ids, row_off, col, dist):
+    """Header and "id\tid\tdistance" rows of a CSR over ids, row by row, through the library's host formatter (csrc/tsv_out.hip)."""
+    from . import _lib as L
+    blob, off = _id_table(ids)
+    ro = np.ascontiguousarray(row_off, dtype=np.uint64)
+    c = np.ascontiguousarray(col, dtype=np.uint32)
+    d = np.ascontiguousarray(dist, dtype=np.int32)
+    rc = L.load().snpgpu_write_close_pairs_tsv(path.encode(), blob, off.ctypes.data, len(ids), ro.ctypes.data, c.ctypes.data, d.ctypes.data)
+    if rc == L.E_IO:
+        raise IOError("cannot write %s" % path)
+    if rc != 0:
+        raise RuntimeError("snpgpu_write_close_pairs_tsv failed (%d)" % rc)
+
+
+def write_clusters(path, ids, thresholds, numbers):
+    """"Id" and the thresholds, then per id its cluster number at each threshold; numbers: (len(thresholds), len(ids)) uint32."""
+    from . import _lib as L
+    blob, off = _id_table(ids)
+    thr = np.ascontiguousarray(thresholds, dtype=np.int32)
+    num = np.ascontiguousarray(numbers, dtype=np.uint32).reshape(len(thr), len(ids))
+    rc = L.load().snpgpu_write_clusters_tsv(path.encode(), blob, off.ctypes.data, len(ids), thr.ctypes.data, len(thr), num.ctypes.data)
+    if rc == L.E_IO:
+        raise IOError("cannot write %s" % path)
+    if rc != 0:
+        raise RuntimeError("snpgpu_write_clusters_tsv failed (%d)" % rc)
+
+
+def write_pairs_and_clusters(dev, ids, row_off, col, dist, pairs_file, max_pair_distance, clusters_file, thresholds):
+    """The two additive outputs from one CSR that holds at least every entry within the largest threshold asked for."""
+    if pairs_file:
+        write_close_pairs(pairs_file, ids, *filter_pairs(row_off, col, dist, max_pair_distance))
+    if clusters_file:
+        thresholds = cluster_thresholds(thresholds)
+        numbers, _ = dev.clusters(len(ids), row_off, col, dist, thresholds)
+        write_clusters(clusters_file, ids, thresholds, numbers)
 
 
 def _write_tsv(path, layout, ids, mat):
@@ -89,22 +169,44 @@ def calculate_snp_distances(args):
     input_file = args.inputFile
     pairwise_file = args.pairwiseFile
     matrix_file = args.matrixFile
+    # extensions of this build (absent when the Namespace comes from the reference's own parser)
+    close_file = getattr(args, "amdClosePairsFile", None)
+    max_pair_distance = getattr(args, "amdMaxPairDistance", None)
+    clusters_file = getattr(args, "amdClustersFile", None)
+    thresholds = list(getattr(args, "amdClusterThresholds", None) or [])
     if utils.verify_existing_input_files("SNP matrix file", [input_file]) > 0:
         utils.global_error("Error: cannot calculate sequence distances without the snp matrix file.")
-    if not pairwise_file and not matrix_file:
+    if close_file and max_pair_distance is None:
+        utils.global_error("Error: --amdClosePairs needs --amdMaxPairDistance.")
+    if clusters_file and not thresholds:
+        utils.global_error("Error: --amdClusters needs at least one threshold in --amdClusterThresholds.")
+    if (max_pair_distance is not None and max_pair_distance < 0) or any(t < 0 for t in thresholds):
+        utils.global_error("Error: a distance threshold cannot be negative.")
+    if not pairwise_file and not matrix_file and not close_file and not clusters_file:
         utils.global_error("Error: no output file specified.")
 
-    rebuild_pairwise = pairwise_file and utils.target_needs_rebuild([input_file], pairwise_file)
-    rebuild_matrix = matrix_file and utils.target_needs_rebuild([input_file], matrix_file)
-    if not (args.forceFlag or rebuild_pairwise or rebuild_matrix):
+    outputs = [f for f in (pairwise_file, matrix_file, close_file, clusters_file) if f]
+    if not (args.forceFlag or any(utils.target_needs_rebuild([input_file], f) for f in outputs)):
         utils.verbose_print("Distance files have already been freshly built.  Use the -f option to force a rebuild.")
         return
 
     file_ids, sym, lens = snp_matrix.load_matrix(input_file)
     utils.verbose_print("# %s %s" % (utils.timestamp(), "Calculating all pairwise distances"))
     from .device import default_device
-    ids, mat = distance_of_matrix(default_device(), file_ids, sym, lens)
+    dev = default_device()
+    mat = None
+    if close_file or clusters_file:
+        # the matrix is thresholded where it is computed: only the pairs within the largest threshold come to the host — and the
+        # matrix of that same computation when the two tables are asked for too
+        widest = max(([max_pair_distance] if close_file else []) + (thresholds if clusters_file else []))
+        got = close_pairs_of_matrix(dev, file_ids, sym, lens, widest, want_matrix=bool(pairwise_file or matrix_file))
+        ids, row_off, col, dist = got[:4]
+        mat = got[4] if len(got) > 4 else None
+    elif pairwise_file or matrix_file:
+        ids, mat = distance_of_matrix(dev, file_ids, sym, lens)
     if pairwise_file:
         write_pairwise(pairwise_file, ids, mat)
     if matrix_file:
         write_matrix(matrix_file, ids, mat)
+    if close_file or clusters_file:
+        write_pairs_and_clusters(dev, ids, row_off, col, dist, close_file, max_pair_distance, clusters_file, thresholds)

@@ -63,6 +63,7 @@ import numpy as np
 from . import _lib as L
 from . import call_sites as cs
 from . import device as devmod
+from . import distance as dmod
 from . import filter_regions as fr
 from . import merge_sites as ms
 from . import snp_reference
@@ -223,6 +224,15 @@ class _Job(object):
             ("snplist", "snplist.txt"), ("snplist_p", "snplist_preserved.txt"), ("snpma", "snpma.fasta"), ("snpma_p", "snpma_preserved.fasta"),
             ("pairs", "snp_distance_pairwise.tsv"), ("matrix", "snp_distance_matrix.tsv"), ("pairs_p", "snp_distance_pairwise_preserved.tsv"),
             ("matrix_p", "snp_distance_matrix_preserved.tsv"), ("refsnp", "referenceSNP.fasta"), ("refsnp_p", "referenceSNP_preserved.fasta"))}
+        # --closePairs / --clusters (additive to the distance step): the pairwise rows within a distance, single-linkage groups
+        self.close_pairs = getattr(args, "closePairs", None)
+        self.cluster_thresholds = dmod.cluster_thresholds(getattr(args, "clusters", None) or [])
+        if (self.close_pairs is not None and self.close_pairs < 0) or any(t < 0 for t in self.cluster_thresholds):
+            utils.global_error("Error: a distance threshold cannot be negative.")
+        if self.close_pairs is not None:
+            self.outputs.update(close=os.path.join(work_dir, "snp_distance_close_pairs.tsv"), close_p=os.path.join(work_dir, "snp_distance_close_pairs_preserved.tsv"))
+        if self.cluster_thresholds:
+            self.outputs.update(clusters=os.path.join(work_dir, "snp_clusters.tsv"), clusters_p=os.path.join(work_dir, "snp_clusters_preserved.tsv"))
         self.filtered1, self.filtered2 = dirs_file + ".OrigVCF.filtered", dirs_file + ".PresVCF.filtered"
 
         self.samples = [_Sample(i, d, args.pileupName) for i, d in enumerate(self.sorted_dirs)]
@@ -1142,6 +1152,40 @@ def stage_consensus(job):
 
 
 # ==================================== stage 4: matrices, distances, top-level files ===========================================
+def _close_rows(torch, dev, d_matrix, n, row_stride, row_lo, row_hi, threshold):
+    """Rows [row_lo, row_hi) of a device distance matrix (row i at d_matrix + 4 * i * row_stride) thresholded there: (entries per
+    row, columns, distances) as host arrays.  The first call has room for 32 entries per row (an outbreak threshold keeps a few):
+    only a denser answer costs a second call with the room the first one asked for."""
+    rows = row_hi - row_lo
+    row_off = torch.zeros(rows + 1, dtype=torch.int64, device="cuda")
+    capacity = max(32 * rows, 1 << 16)
+    while True:
+        col = torch.zeros(capacity, dtype=torch.int32, device="cuda")
+        dist = torch.zeros(capacity, dtype=torch.int32, device="cuda")
+        total = dev.close_pairs_dev(d_matrix, n, row_stride, row_lo, row_hi, threshold, capacity, row_off.data_ptr(), col.data_ptr(), dist.data_ptr())
+        if total <= capacity:
+            break
+        capacity = total
+    return np.diff(row_off.cpu().numpy()).astype(np.uint64), col[:total].cpu().numpy().view(np.uint32), dist[:total].cpu().numpy()
+
+
+def close_rows_over_ranks(torch, dev, comm, bands, dmat, band, n, threshold):
+    """The entries <= threshold of the whole n x n distance matrix as a CSR (row_off, col, dist) on rank 0, None on the others.
+    With one rank: from `dmat` (pitch bands.n_padded).  With several: `band` holds the complete rows of this rank's band after
+    bands.exchange (the same pitch); each rank thresholds those on the device — the kernel is given where row 0 WOULD lie in front of
+    the band, and the band's own row range — and the pieces are gathered in rank order, which is row order."""
+    if band is not None:
+        blo, bhi = bands.band_rows(comm.rank)
+        parts = comm.gather_objects(_close_rows(torch, dev, band.data_ptr() - blo * bands.n_padded * 4, n, bands.n_padded, blo, bhi, threshold))
+    else:
+        parts = [_close_rows(torch, dev, dmat.data_ptr(), n, max(bands.n_padded, 1), 0, n, threshold)]
+    if comm.rank != 0:
+        return None
+    row_off = np.zeros(n + 1, dtype=np.uint64)
+    np.cumsum(np.concatenate([p[0] for p in parts]), out=row_off[1:])
+    return row_off, np.concatenate([p[1] for p in parts]), np.concatenate([p[2] for p in parts])
+
+
 def stage_matrices_and_distances(job):
     """Collectives interleaved with file output; the output runs under ``job.guard`` so that a rank whose disk is full still takes
     part in every collective and the failure surfaces at the agreement after the stage."""
@@ -1215,9 +1259,18 @@ def stage_matrices_and_distances(job):
             full = np.concatenate(pieces, axis=0) if rank == 0 else None
         else:
             full = dmat[:n, :n].cpu().numpy()
+        csr = None
+        if job.close_pairs is not None or job.cluster_thresholds:
+            # every rank thresholds the complete rows it holds on the device; the pieces that travel are the pairs within the widest threshold
+            widest = max(([job.close_pairs] if job.close_pairs is not None else []) + job.cluster_thresholds)
+            csr = close_rows_over_ranks(torch, dev, comm, bands, dmat, band if (comm.dist and n) else None, n, widest)
+        with job.guard() as go:
+            if go and rank == 0 and csr is not None:
+                sfx = "" if flow == 1 else "_p"
+                dmod.write_pairs_and_clusters(dev, ids, csr[0], csr[1], csr[2], outputs["close" + sfx] if job.close_pairs is not None else None, job.close_pairs,
+                                              outputs["clusters" + sfx] if job.cluster_thresholds else None, job.cluster_thresholds)
         with job.guard() as go:
             if go and rank == 0:
-                from . import distance as dmod
                 dmod.write_pairwise(outputs[pairs], ids, full)
                 dmod.write_matrix(outputs[matrix], ids, full)
                 if ref_seqs[0] is None:
@@ -1433,6 +1486,8 @@ def add_arguments(sub):
     sub.add_argument("--mergeVcfs", dest="mergeVcfs", action="store_true", help="At the end of the job write snpma.vcf and snpma_preserved.vcf (merge_vcfs) into the work directory, from the consensus.vcf / consensus_preserved.vcf files the job has just written; not with --noConsensusVcf")
     sub.add_argument("--vcfMerger", dest="vcfMerger", type=str, default=None, choices=("bcftools", "device", "auto"), metavar="MODE", help="With --mergeVcfs: who merges, as merge_vcfs --vcfMerger (default: $SNPGPU_VCF_MERGER, else auto)")
     sub.add_argument("--mergeDeviceBytes", dest="mergeDeviceBytes", type=str, default=argparse.SUPPRESS, metavar="INT", help="With --mergeVcfs: the device memory the device route may allocate, as merge_vcfs --mergeDeviceBytes (default: $SNPGPU_MERGE_DEVICE_BYTES, else 0 = what is free, less a reserve)")
+    sub.add_argument("--closePairs", dest="closePairs", type=int, default=None, metavar="INT", help="Also write snp_distance_close_pairs.tsv and snp_distance_close_pairs_preserved.tsv into the work directory: the rows of the pairwise files whose distance is at most INT, thresholded on the device (as distance --amdClosePairs --amdMaxPairDistance)")
+    sub.add_argument("--clusters", dest="clusters", type=int, nargs="+", default=None, metavar="INT", help="Also write snp_clusters.tsv and snp_clusters_preserved.tsv into the work directory: every sample's single-linkage cluster number at each of the SNP thresholds (as distance --amdClusters --amdClusterThresholds)")
     sub.add_argument("--noConsensusVcf", dest="noConsensusVcf", action="store_true", help="Do not write consensus.vcf / consensus_preserved.vcf")
     sub.add_argument("--residentBytes", dest="residentBytes", type=int, default=0, metavar="INT", help="Device memory for resident pileups (0 = what is free, less 24 GiB); files past it are streamed twice in site calling mode device only: in modes existing and varscan --pileupRoute auto streams every pileup once instead")
     sub.add_argument("--pileupRoute", dest="pileupRoute", type=str, default=None, choices=PILEUP_ROUTES, metavar="ROUTE",
