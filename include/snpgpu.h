@@ -730,6 +730,45 @@ int  snpgpu_write_close_pairs_tsv(const char *path, const char *ids, const uint6
 int  snpgpu_write_clusters_tsv(const char *path, const char *ids, const uint64_t *id_off, uint32_t n,
                                const int32_t *thresholds, uint32_t n_thresholds, const uint32_t *numbers);
 
+/* ---- minimum spanning tree and single-linkage dendrogram (csrc/mst.hip) ------------------------------------------------
+ * Additive entries of ABI 7, like the ones above.  Samples are 0 ... n-1; edge {i, j}, i < j, weighs matrix[i][j] (signed
+ * int32); the edges are totally ordered by (d, i, j) and THE tree is the one Kruskal's algorithm builds in that order, so it
+ * is unique: the same matrix gives the same bytes.  For any T its edges with d <= T have the components snpgpu_clusters
+ * reports at T.
+ *
+ * snpgpu_mst_dev: the minimum spanning forest of the entries of rows [row_lo, row_hi) of the device matrix, addressed as for
+ * snpgpu_close_pairs_dev (row i at d_matrix + i * row_stride, rows outside the range never read, columns >= n and the diagonal
+ * never taken as edges, whatever they hold).  d_u[], d_v[], d_dist[] (room for n - 1 each) receive the edges in ascending
+ * (d, u, v), u < v; *out_n_edges and *out_rounds (host) how many there are and how many Boruvka rounds picked them, at most
+ * ceil(log2 n).  An empty range or n <= 1: 0 edges, 0 rounds.  The call waits for the stream once per round. */
+int  snpgpu_mst_dev(snpgpu_ctx *ctx, const int32_t *d_matrix, uint32_t n, uint64_t row_stride, uint32_t row_lo, uint32_t row_hi,
+                    uint32_t *d_u, uint32_t *d_v, int32_t *d_dist, uint32_t *out_n_edges, uint32_t *out_rounds);
+/* Host form (as snpgpu_close_pairs): packs the symbols, computes the matrix and builds the tree on the device; out_u, out_v,
+ * out_dist hold n_rows - 1 edges.  With out_matrix null the n x n matrix never crosses the host link; not null: it is copied
+ * there too, from the same computation. */
+int  snpgpu_mst(snpgpu_ctx *ctx, const uint8_t *symbols, uint32_t n_rows, uint32_t n_sites, uint32_t *out_u, uint32_t *out_v,
+                int32_t *out_dist, int32_t *out_matrix);
+/* snpgpu_mst and, with want_pairs not 0, snpgpu_close_pairs (same threshold / capacity protocol, same outputs) from ONE
+ * computation of the matrix: for a caller that writes the tree next to the close pairs or the clusters. */
+int  snpgpu_mst_close_pairs(snpgpu_ctx *ctx, const uint8_t *symbols, uint32_t n_rows, uint32_t n_sites, uint32_t *out_u,
+                            uint32_t *out_v, int32_t *out_dist, int32_t *out_matrix, int want_pairs, int32_t threshold,
+                            uint64_t capacity, uint64_t *out_row_off, uint32_t *out_col, int32_t *out_pair_dist, uint64_t *out_n);
+/* Host code: Kruskal in the order (d, min(u,v), max(u,v)) over an edge list on n nodes — duplicates and either orientation of
+ * an edge allowed —, which merges the forests that several ranks found in their bands.  out_u / out_v / out_dist: room for
+ * min(n_edges, n - 1); a disconnected list gives a forest.  SNPGPU_E_ARG for an index >= n or u == v. */
+int  snpgpu_mst_of_edges(uint32_t n, const uint32_t *u, const uint32_t *v, const int32_t *dist, uint64_t n_edges,
+                         uint32_t *out_u, uint32_t *out_v, int32_t *out_dist, uint32_t *out_n);
+/* The two texts (host code).  MST file: "Seq1\tSeq2\tDistance\n", then "id_u\tid_v\td\n" per edge as given.  Dendrogram: one
+ * Newick line.  The edges, which must be a spanning tree of the n samples in ascending (d, i, j) with d >= 0 (else
+ * SNPGPU_E_ARG), are taken in order; each joins the groups of its ends under a node of height d / 2 (leaves: 0), the child
+ * with the smaller sample first; a branch length is (d_parent - d_child) / 2 written from the integer ("7" or "7.5"), the root
+ * has none; an id that is not [A-Za-z0-9.|-]+ is put in single quotes with every ' doubled.  n = 0: ";\n", n = 1: "id;\n".
+ * No recursion.  SNPGPU_E_IO when the file cannot be created or written. */
+int  snpgpu_write_mst_tsv(const char *path, const char *ids, const uint64_t *id_off, uint32_t n, const uint32_t *u,
+                          const uint32_t *v, const int32_t *dist, uint32_t n_edges);
+int  snpgpu_write_dendrogram_newick(const char *path, const char *ids, const uint64_t *id_off, uint32_t n, const uint32_t *u,
+                                    const uint32_t *v, const int32_t *dist, uint32_t n_edges);
+
 /* ---- the exchange steps of the sharded path: RCCL over xGMI, one process per GPU ------------------------
  * The reference fans out one process per sample (run.py:704-718, `run_array` with `max_processes`) over a shared file system
  * and has no exchange step; sharded over GPUs the hot path has three: C1, the all-gather of the per-rank SNP site keys

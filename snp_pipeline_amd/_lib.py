@@ -201,6 +201,12 @@ SIGNATURES = {
     "snpgpu_clusters": (C.c_int, [_P, C.c_uint32, _P, _P, _P, C.c_uint64, _P, C.c_uint32, _P, _P]),
     "snpgpu_write_close_pairs_tsv": (C.c_int, [C.c_char_p, _P, _P, C.c_uint32, _P, _P, _P]),
     "snpgpu_write_clusters_tsv": (C.c_int, [C.c_char_p, _P, _P, C.c_uint32, _P, C.c_uint32, _P]),
+    "snpgpu_mst_dev": (C.c_int, [_P, _P, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, _P, _P, _P, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "snpgpu_mst": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, _P, _P, _P, _P]),
+    "snpgpu_mst_close_pairs": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, _P, _P, _P, _P, C.c_int, C.c_int32, C.c_uint64, _P, _P, _P, C.POINTER(C.c_uint64)]),
+    "snpgpu_mst_of_edges": (C.c_int, [C.c_uint32, _P, _P, _P, C.c_uint64, _P, _P, _P, C.POINTER(C.c_uint32)]),
+    "snpgpu_write_mst_tsv": (C.c_int, [C.c_char_p, _P, _P, C.c_uint32, _P, _P, _P, C.c_uint32]),
+    "snpgpu_write_dendrogram_newick": (C.c_int, [C.c_char_p, _P, _P, C.c_uint32, _P, _P, _P, C.c_uint32]),
     "snpgpu_dense_windows": (C.c_int, [_P, _P, _P, C.c_uint32, _P, _P, C.c_uint32, _P, _P, _P, C.POINTER(C.c_uint32)]),
     "snpgpu_merge_regions": (C.c_int, [_P, _P, _P, _P, C.c_uint32, _P, _P, _P, C.POINTER(C.c_uint32)]),
     "snpgpu_in_regions": (C.c_int, [_P, _P, _P, C.c_uint32, _P, _P, _P, C.c_uint32, _P]),

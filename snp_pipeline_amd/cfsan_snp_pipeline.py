@@ -211,6 +211,8 @@ def parse_argument_list(argv):
     sub.add_argument("--amdMaxPairDistance", dest="amdMaxPairDistance", type=int, default=None, metavar="INT", help="Extension of this build: the largest distance of a row of the --amdClosePairs file.")
     sub.add_argument("--amdClusters", dest="amdClustersFile", type=str, default=None, metavar="FILE", help="Extension of this build: output file with every sample's single-linkage cluster number at each threshold of --amdClusterThresholds (samples joined by a chain of pairs within the threshold; clusters numbered from 1 in order of their first sample).")
     sub.add_argument("--amdClusterThresholds", dest="amdClusterThresholds", type=int, nargs="+", default=None, metavar="INT", help="Extension of this build: the SNP thresholds of the --amdClusters file; sorted and made unique.")
+    sub.add_argument("--amdMst", dest="amdMstFile", type=str, default=None, metavar="FILE", help="Extension of this build: output file with the n - 1 edges of the minimum spanning tree of the samples (the tree Kruskal's algorithm builds under the edge order distance, first sample, second sample), one Seq1 / Seq2 / Distance row per edge in that order; built on the device, the full matrix is not written.")
+    sub.add_argument("--amdDendrogram", dest="amdDendrogramFile", type=str, default=None, metavar="FILE", help="Extension of this build: output file with the single-linkage dendrogram of the samples as one Newick line: groups join at height distance / 2, so the path between two leaves through their join is their single-linkage distance.")
     _common(sub)
     sub.set_defaults(func=distance.calculate_snp_distances, excepthook=utils.handle_global_exception)
 

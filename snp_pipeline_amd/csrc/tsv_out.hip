@@ -333,3 +333,92 @@ extern "C" int snpgpu_write_clusters_tsv(const char *path, const char *ids, cons
     };
     return write_row_blocks(path, n, (uint64_t)n * k, nullptr, header_bytes, header, size_rows, format);
 }
+
+// ---- minimum spanning tree and dendrogram (additive: the tree of csrc/mst.hip as text) ----
+extern "C" int snpgpu_write_mst_tsv(const char *path, const char *ids, const uint64_t *id_off, uint32_t n, const uint32_t *u, const uint32_t *v,
+                                    const int32_t *dist, uint32_t n_edges) {
+    if (!path || (n && (!ids || !id_off)) || (n_edges && (!u || !v || !dist))) return SNPGPU_E_ARG;
+    for (uint32_t e = 0; e < n_edges; ++e)
+        if (u[e] >= n || v[e] >= n) return SNPGPU_E_ARG;
+    FileOut o(path);
+    if (o.failed) return SNPGPU_E_IO;
+    o.put("Seq1\tSeq2\tDistance\n", 19);
+    for (uint32_t e = 0; e < n_edges && !o.failed; ++e) {
+        o.put(ids + id_off[u[e]], (size_t)(id_off[u[e] + 1] - id_off[u[e]])); o.put('\t');
+        o.put(ids + id_off[v[e]], (size_t)(id_off[v[e] + 1] - id_off[v[e]])); o.put('\t');
+        o.put_i32(dist[e]); o.put('\n');
+    }
+    return o.finish();
+}
+
+// Newick, one line: the edges in their order join the groups of their ends under a node of height d / 2.  Node k < n is leaf k,
+// node n + e the join of edge e.  Written with an explicit stack: a chain of 10 000 nested joins is an ordinary tree here.
+extern "C" int snpgpu_write_dendrogram_newick(const char *path, const char *ids, const uint64_t *id_off, uint32_t n, const uint32_t *u, const uint32_t *v,
+                                              const int32_t *dist, uint32_t n_edges) {
+    if (!path || (n && (!ids || !id_off)) || (n_edges && (!u || !v || !dist))) return SNPGPU_E_ARG;
+    if (n_edges != (n ? n - 1 : 0)) return SNPGPU_E_ARG;
+    std::vector<uint32_t> parent(n), top(n), least(n), child((size_t)n_edges * 2);   // union-find; per set root: its node and its smallest sample
+    for (uint32_t i = 0; i < n; ++i) parent[i] = top[i] = least[i] = i;
+    auto find = [&](uint32_t x) {
+        while (parent[x] != x) { parent[x] = parent[parent[x]]; x = parent[x]; }
+        return x;
+    };
+    for (uint32_t e = 0; e < n_edges; ++e) {
+        if (u[e] >= n || v[e] >= n || u[e] == v[e] || dist[e] < 0) return SNPGPU_E_ARG;
+        if (e) {                                                     // ascending (d, i, j)
+            const uint32_t lo0 = std::min(u[e - 1], v[e - 1]), hi0 = std::max(u[e - 1], v[e - 1]), lo1 = std::min(u[e], v[e]), hi1 = std::max(u[e], v[e]);
+            if (dist[e - 1] > dist[e] || (dist[e - 1] == dist[e] && (lo0 > lo1 || (lo0 == lo1 && hi0 >= hi1)))) return SNPGPU_E_ARG;
+        }
+        uint32_t a = find(u[e]), b = find(v[e]);
+        if (a == b) return SNPGPU_E_ARG;                             // a cycle: not a tree
+        if (least[b] < least[a]) std::swap(a, b);                    // the child with the smaller sample is written first
+        child[2 * (size_t)e] = top[a];
+        child[2 * (size_t)e + 1] = top[b];
+        parent[b] = a;
+        top[a] = n + e;
+    }
+    FileOut o(path);
+    if (o.failed) return SNPGPU_E_IO;
+    auto d_of = [&](uint32_t node) -> int64_t { return node < n ? 0 : (int64_t)dist[node - n]; };
+    auto label = [&](uint32_t i) {
+        const char *s = ids + id_off[i];
+        const size_t len = (size_t)(id_off[i + 1] - id_off[i]);
+        bool bare = len > 0;
+        for (size_t k = 0; k < len && bare; ++k) {
+            const unsigned char c = (unsigned char)s[k];
+            bare = (c >= 'A' && c <= 'Z') || (c >= 'a' && c <= 'z') || (c >= '0' && c <= '9') || c == '.' || c == '|' || c == '-';
+        }
+        if (bare) { o.put(s, len); return; }
+        o.put('\'');
+        for (size_t k = 0; k < len; ++k) { if (s[k] == '\'') o.put('\''); o.put(s[k]); }
+        o.put('\'');
+    };
+    auto length = [&](int64_t twice) {                               // ":" and half of d_parent - d_child, never through a float
+        o.put(':');
+        o.put_i32((int32_t)(twice / 2));
+        if (twice & 1) o.put(".5", 2);
+    };
+    if (n) {
+        struct Frame { uint32_t node, up, state; };                  // up: the parent node (or itself at the root); state: children written
+        std::vector<Frame> stack;
+        const uint32_t root = n + n_edges - 1;                       // (n == 1: leaf 0)
+        stack.push_back({n_edges ? root : 0u, n_edges ? root : 0u, 0u});
+        while (!stack.empty() && !o.failed) {
+            Frame &f = stack.back();
+            if (f.node < n) {
+                label(f.node);
+                if (f.up != f.node) length(d_of(f.up));
+                stack.pop_back();
+                continue;
+            }
+            const uint32_t e = f.node - n;
+            if (f.state == 0) { o.put('('); f.state = 1; const uint32_t c = child[2 * (size_t)e]; const uint32_t me = f.node; stack.push_back({c, me, 0u}); continue; }
+            if (f.state == 1) { o.put(','); f.state = 2; const uint32_t c = child[2 * (size_t)e + 1]; const uint32_t me = f.node; stack.push_back({c, me, 0u}); continue; }
+            o.put(')');
+            if (f.up != f.node) length(d_of(f.up) - d_of(f.node));
+            stack.pop_back();
+        }
+    }
+    o.put(";\n", 2);
+    return o.finish();
+}

@@ -1131,6 +1131,45 @@ class Device(object):
                                              _ptr(thr) if len(thr) else None, len(thr), _ptr(numbers) if numbers.size else None, _ptr(counts) if len(thr) else None))
         return numbers, counts
 
+    # ---- minimum spanning tree (additive to distance.py:93-106) --------------------------------
+    def mst_dev(self, d_matrix, n, row_stride, row_lo, row_hi, d_u=0, d_v=0, d_dist=0):
+        """The minimum spanning forest of the entries of rows [row_lo, row_hi) of a device int32 matrix (columns < n, the diagonal
+        left out) under the edge order (d, i, j) into d_u / d_v / d_dist (room for n - 1 each), ascending, u < v.  Returns
+        (number of edges, Boruvka rounds)."""
+        opt = lambda v: C.c_void_p(int(v)) if v else None     # noqa: E731
+        n_edges, rounds = C.c_uint32(0), C.c_uint32(0)
+        self._check(self.lib.snpgpu_mst_dev(self.ctx, opt(d_matrix), int(n), int(row_stride), int(row_lo), int(row_hi), opt(d_u), opt(d_v), opt(d_dist),
+                                            C.byref(n_edges), C.byref(rounds)))
+        return int(n_edges.value), int(rounds.value)
+
+    def mst(self, symbols, want_matrix=False, pairs_within=None):
+        """symbols: (n, s) uint8 array of sequence bytes.  Returns (u uint32, v uint32, dist int32): the n - 1 edges of the minimum
+        spanning tree of the distance matrix in ascending (d, u, v), u < v.  The matrix itself stays on the device — unless
+        want_matrix, which adds the (n, n) int32 matrix of ``distance`` from the same computation.  pairs_within = T adds, from that
+        computation too, the CSR of ``close_pairs(symbols, T)``: the result is then (u, v, dist, (row_off, col, dist)[, matrix])."""
+        sym = np.ascontiguousarray(symbols, dtype=np.uint8)
+        n, s = sym.shape
+        m = max(n - 1, 0)
+        u, v, dist = np.zeros(m, dtype=np.uint32), np.zeros(m, dtype=np.uint32), np.zeros(m, dtype=np.int32)
+        mat = np.zeros((n, n), dtype=np.int32) if want_matrix else None
+        opt = lambda a: _ptr(a) if a is not None and a.size else None     # noqa: E731
+        if pairs_within is None:
+            self._check(self.lib.snpgpu_mst(self.ctx, opt(sym), n, s, opt(u), opt(v), opt(dist), opt(mat)))
+            return (u, v, dist, mat) if want_matrix else (u, v, dist)
+        row_off = np.zeros(n + 1, dtype=np.uint64)
+        cap = max(min(n * n, max(64 * n, 1 << 26)), 1)
+        have_matrix = False
+        while True:                                           # (the capacity protocol of close_pairs: a second call only past max(64 n, 2^26) entries)
+            col, pd = np.zeros(cap, dtype=np.uint32), np.zeros(cap, dtype=np.int32)
+            out_n = C.c_uint64(0)
+            self._check(self.lib.snpgpu_mst_close_pairs(self.ctx, opt(sym), n, s, opt(u), opt(v), opt(dist), opt(mat) if not have_matrix else None, 1,
+                                                        int(pairs_within), cap, _ptr(row_off), _ptr(col), _ptr(pd), C.byref(out_n)))
+            have_matrix = True
+            if out_n.value <= cap:
+                csr = (row_off, col[:out_n.value], pd[:out_n.value])
+                return (u, v, dist, csr, mat) if want_matrix else (u, v, dist, csr)
+            cap = int(out_n.value)
+
     # ---- filter_regions ------------------------------------------------------------------------
     def dense_windows(self, positions, seg_off, max_snps, windows):
         pos = np.ascontiguousarray(positions, dtype=np.int64)

@@ -137,6 +137,64 @@ def write_pairs_and_clusters(dev, ids, row_off, col, dist, pairs_file, max_pair_
         write_clusters(clusters_file, ids, thresholds, numbers)
 
 
+def mst_of_matrix(dev, file_ids, sym, lens, want_matrix=False, pairs_within=None):
+    """As close_pairs_of_matrix, but what comes back is the minimum spanning tree of the samples: (ids, u, v, dist), the n - 1
+    edges {u, v}, u < v, of the tree Kruskal builds under the edge order (d, u, v), in that order; built on the device, where the
+    matrix stays.  pairs_within = T adds the CSR (row_off, col, dist) of close_pairs_of_matrix at T, want_matrix the matrix, each
+    from the same computation: (ids, u, v, dist[, csr][, matrix])."""
+    ids, rows = _sorted_rows(file_ids, sym, lens)
+    if rows is None:
+        rows = np.zeros((0, 0), dtype=np.uint8)
+    return (ids,) + tuple(dev.mst(rows, want_matrix=want_matrix, pairs_within=pairs_within))
+
+
+def mst_of_edges(n, u, v, dist):
+    """Kruskal under the edge order (d, min, max) over an edge list on n nodes (duplicates and both orientations allowed): the
+    minimum spanning forest (u, v, dist), u < v, in that order.  Merges the forests the ranks found in their bands."""
+    from . import _lib as L
+    u = np.ascontiguousarray(u, dtype=np.uint32)
+    v = np.ascontiguousarray(v, dtype=np.uint32)
+    d = np.ascontiguousarray(dist, dtype=np.int32)
+    if not len(u) == len(v) == len(d):
+        raise ValueError("u, v and dist hold one entry per edge")
+    room = max(min(len(u), max(int(n) - 1, 0)), 1)
+    ou, ov, od = np.zeros(room, dtype=np.uint32), np.zeros(room, dtype=np.uint32), np.zeros(room, dtype=np.int32)
+    out_n = L.C.c_uint32(0)
+    rc = L.load().snpgpu_mst_of_edges(int(n), u.ctypes.data, v.ctypes.data, d.ctypes.data, len(u), ou.ctypes.data, ov.ctypes.data, od.ctypes.data, L.C.byref(out_n))
+    if rc == L.E_ARG:
+        raise ValueError("an edge names a node outside 0 ... %d or joins a node to itself" % (int(n) - 1))
+    if rc != 0:
+        raise RuntimeError("snpgpu_mst_of_edges failed (%d)" % rc)
+    k = int(out_n.value)
+    return ou[:k], ov[:k], od[:k]
+
+
+def _write_tree(entry, path, ids, u, v, dist):
+    from . import _lib as L
+    blob, off = _id_table(ids)
+    u = np.ascontiguousarray(u, dtype=np.uint32)
+    v = np.ascontiguousarray(v, dtype=np.uint32)
+    d = np.ascontiguousarray(dist, dtype=np.int32)
+    rc = getattr(L.load(), entry)(path.encode(), blob, off.ctypes.data, len(ids), u.ctypes.data, v.ctypes.data, d.ctypes.data, len(u))
+    if rc == L.E_IO:
+        raise IOError("cannot write %s" % path)
+    if rc == L.E_ARG:
+        raise ValueError("the edges are not a spanning tree of the %d ids in ascending order" % len(ids))
+    if rc != 0:
+        raise RuntimeError("%s failed (%d)" % (entry, rc))
+
+
+def write_mst(path, ids, u, v, dist):
+    """Header and one "id\tid\tdistance" row per tree edge, in the order given."""
+    _write_tree("snpgpu_write_mst_tsv", path, ids, u, v, dist)
+
+
+def write_dendrogram(path, ids, u, v, dist):
+    """The single-linkage dendrogram of a spanning tree whose edges come in ascending order, as one Newick line: each edge joins
+    the groups of its ends at height d / 2 (csrc/tsv_out.hip)."""
+    _write_tree("snpgpu_write_dendrogram_newick", path, ids, u, v, dist)
+
+
 def _write_tsv(path, layout, ids, mat):
     """distance.py:100-114 through the library's host formatter (csrc/tsv_out.hip): at 10 000 samples the pairwise file has
     10^8 lines, ~35 s of Python string formatting for 38 ms of kernel."""
@@ -174,6 +232,8 @@ def calculate_snp_distances(args):
     max_pair_distance = getattr(args, "amdMaxPairDistance", None)
     clusters_file = getattr(args, "amdClustersFile", None)
     thresholds = list(getattr(args, "amdClusterThresholds", None) or [])
+    mst_file = getattr(args, "amdMstFile", None)
+    dendrogram_file = getattr(args, "amdDendrogramFile", None)
     if utils.verify_existing_input_files("SNP matrix file", [input_file]) > 0:
         utils.global_error("Error: cannot calculate sequence distances without the snp matrix file.")
     if close_file and max_pair_distance is None:
@@ -182,10 +242,10 @@ def calculate_snp_distances(args):
         utils.global_error("Error: --amdClusters needs at least one threshold in --amdClusterThresholds.")
     if (max_pair_distance is not None and max_pair_distance < 0) or any(t < 0 for t in thresholds):
         utils.global_error("Error: a distance threshold cannot be negative.")
-    if not pairwise_file and not matrix_file and not close_file and not clusters_file:
+    if not pairwise_file and not matrix_file and not close_file and not clusters_file and not mst_file and not dendrogram_file:
         utils.global_error("Error: no output file specified.")
 
-    outputs = [f for f in (pairwise_file, matrix_file, close_file, clusters_file) if f]
+    outputs = [f for f in (pairwise_file, matrix_file, close_file, clusters_file, mst_file, dendrogram_file) if f]
     if not (args.forceFlag or any(utils.target_needs_rebuild([input_file], f) for f in outputs)):
         utils.verbose_print("Distance files have already been freshly built.  Use the -f option to force a rebuild.")
         return
@@ -195,7 +255,18 @@ def calculate_snp_distances(args):
     from .device import default_device
     dev = default_device()
     mat = None
-    if close_file or clusters_file:
+    tree = None
+    if mst_file or dendrogram_file:
+        # the tree is built where the matrix is computed: n - 1 edges come to the host — with them, from that one computation, the
+        # pairs within the widest threshold and the matrix itself when those outputs are asked for too
+        widest = max(([max_pair_distance] if close_file else []) + (thresholds if clusters_file else [])) if (close_file or clusters_file) else None
+        got = mst_of_matrix(dev, file_ids, sym, lens, want_matrix=bool(pairwise_file or matrix_file), pairs_within=widest)
+        ids, tree = got[0], got[1:4]
+        got = got[4:]
+        if widest is not None:
+            (row_off, col, dist), got = got[0], got[1:]
+        mat = got[0] if got else None
+    elif close_file or clusters_file:
         # the matrix is thresholded where it is computed: only the pairs within the largest threshold come to the host — and the
         # matrix of that same computation when the two tables are asked for too
         widest = max(([max_pair_distance] if close_file else []) + (thresholds if clusters_file else []))
@@ -210,3 +281,7 @@ def calculate_snp_distances(args):
         write_matrix(matrix_file, ids, mat)
     if close_file or clusters_file:
         write_pairs_and_clusters(dev, ids, row_off, col, dist, close_file, max_pair_distance, clusters_file, thresholds)
+    if mst_file:
+        write_mst(mst_file, ids, *tree)
+    if dendrogram_file:
+        write_dendrogram(dendrogram_file, ids, *tree)

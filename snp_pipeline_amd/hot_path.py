@@ -233,6 +233,11 @@ class _Job(object):
             self.outputs.update(close=os.path.join(work_dir, "snp_distance_close_pairs.tsv"), close_p=os.path.join(work_dir, "snp_distance_close_pairs_preserved.tsv"))
         if self.cluster_thresholds:
             self.outputs.update(clusters=os.path.join(work_dir, "snp_clusters.tsv"), clusters_p=os.path.join(work_dir, "snp_clusters_preserved.tsv"))
+        # --mst (additive to the distance step): the minimum spanning tree of the samples and their single-linkage dendrogram
+        self.mst = bool(getattr(args, "mst", False))
+        if self.mst:
+            self.outputs.update(mst=os.path.join(work_dir, "snp_mst.tsv"), mst_p=os.path.join(work_dir, "snp_mst_preserved.tsv"),
+                                dendrogram=os.path.join(work_dir, "snp_dendrogram.nwk"), dendrogram_p=os.path.join(work_dir, "snp_dendrogram_preserved.nwk"))
         self.filtered1, self.filtered2 = dirs_file + ".OrigVCF.filtered", dirs_file + ".PresVCF.filtered"
 
         self.samples = [_Sample(i, d, args.pileupName) for i, d in enumerate(self.sorted_dirs)]
@@ -1186,6 +1191,35 @@ def close_rows_over_ranks(torch, dev, comm, bands, dmat, band, n, threshold):
     return row_off, np.concatenate([p[1] for p in parts]), np.concatenate([p[2] for p in parts])
 
 
+def _mst_rows(torch, dev, d_matrix, n, row_stride, row_lo, row_hi):
+    """The minimum spanning forest of the entries of rows [row_lo, row_hi) of a device distance matrix, built there: (u, v, dist)
+    as host arrays, ascending (d, u, v)."""
+    room = max(n - 1, 1)
+    u = torch.zeros(room, dtype=torch.int32, device="cuda")
+    v = torch.zeros(room, dtype=torch.int32, device="cuda")
+    dist = torch.zeros(room, dtype=torch.int32, device="cuda")
+    k, _ = dev.mst_dev(d_matrix, n, row_stride, row_lo, row_hi, u.data_ptr(), v.data_ptr(), dist.data_ptr())
+    return u[:k].cpu().numpy().view(np.uint32), v[:k].cpu().numpy().view(np.uint32), dist[:k].cpu().numpy()
+
+
+def mst_over_ranks(torch, dev, comm, bands, dmat, band, n):
+    """The minimum spanning tree of the whole n x n distance matrix as (u, v, dist) on rank 0, None on the others.  With one rank:
+    from `dmat` (pitch bands.n_padded, n columns: the zero padding is never an edge).  With several: each rank builds the forest of
+    the complete rows of its band (as close_rows_over_ranks addresses them; an empty band gives no edges), the forests are
+    gathered, and rank 0 merges them with Kruskal in the same edge order.  The merge is exact: an edge outside the forest of its
+    own band is the largest edge of a cycle of that band, hence of a cycle of the whole graph."""
+    if band is not None:
+        blo, bhi = bands.band_rows(comm.rank)
+        parts = comm.gather_objects(_mst_rows(torch, dev, band.data_ptr() - blo * bands.n_padded * 4, n, bands.n_padded, blo, bhi))
+    else:
+        parts = [_mst_rows(torch, dev, dmat.data_ptr(), n, max(bands.n_padded, 1), 0, n)]
+    if comm.rank != 0:
+        return None
+    if len(parts) == 1:
+        return parts[0]
+    return dmod.mst_of_edges(n, *(np.concatenate([p[k] for p in parts]) for k in range(3)))
+
+
 def stage_matrices_and_distances(job):
     """Collectives interleaved with file output; the output runs under ``job.guard`` so that a rank whose disk is full still takes
     part in every collective and the failure surfaces at the agreement after the stage."""
@@ -1269,6 +1303,12 @@ def stage_matrices_and_distances(job):
                 sfx = "" if flow == 1 else "_p"
                 dmod.write_pairs_and_clusters(dev, ids, csr[0], csr[1], csr[2], outputs["close" + sfx] if job.close_pairs is not None else None, job.close_pairs,
                                               outputs["clusters" + sfx] if job.cluster_thresholds else None, job.cluster_thresholds)
+        tree = mst_over_ranks(torch, dev, comm, bands, dmat, band if (comm.dist and n) else None, n) if job.mst else None
+        with job.guard() as go:
+            if go and rank == 0 and tree is not None:
+                sfx = "" if flow == 1 else "_p"
+                dmod.write_mst(outputs["mst" + sfx], ids, *tree)
+                dmod.write_dendrogram(outputs["dendrogram" + sfx], ids, *tree)
         with job.guard() as go:
             if go and rank == 0:
                 dmod.write_pairwise(outputs[pairs], ids, full)
@@ -1488,6 +1528,7 @@ def add_arguments(sub):
     sub.add_argument("--mergeDeviceBytes", dest="mergeDeviceBytes", type=str, default=argparse.SUPPRESS, metavar="INT", help="With --mergeVcfs: the device memory the device route may allocate, as merge_vcfs --mergeDeviceBytes (default: $SNPGPU_MERGE_DEVICE_BYTES, else 0 = what is free, less a reserve)")
     sub.add_argument("--closePairs", dest="closePairs", type=int, default=None, metavar="INT", help="Also write snp_distance_close_pairs.tsv and snp_distance_close_pairs_preserved.tsv into the work directory: the rows of the pairwise files whose distance is at most INT, thresholded on the device (as distance --amdClosePairs --amdMaxPairDistance)")
     sub.add_argument("--clusters", dest="clusters", type=int, nargs="+", default=None, metavar="INT", help="Also write snp_clusters.tsv and snp_clusters_preserved.tsv into the work directory: every sample's single-linkage cluster number at each of the SNP thresholds (as distance --amdClusters --amdClusterThresholds)")
+    sub.add_argument("--mst", dest="mst", action="store_true", help="Also write snp_mst.tsv, snp_mst_preserved.tsv, snp_dendrogram.nwk and snp_dendrogram_preserved.nwk into the work directory: the minimum spanning tree of the samples and their single-linkage dendrogram, built on the device (as distance --amdMst --amdDendrogram)")
     sub.add_argument("--noConsensusVcf", dest="noConsensusVcf", action="store_true", help="Do not write consensus.vcf / consensus_preserved.vcf")
     sub.add_argument("--residentBytes", dest="residentBytes", type=int, default=0, metavar="INT", help="Device memory for resident pileups (0 = what is free, less 24 GiB); files past it are streamed twice in site calling mode device only: in modes existing and varscan --pileupRoute auto streams every pileup once instead")
     sub.add_argument("--pileupRoute", dest="pileupRoute", type=str, default=None, choices=PILEUP_ROUTES, metavar="ROUTE",
