@@ -1,22 +1,39 @@
-// Streamed ingestion for call_consensus: pileup files (or host buffers) -> consensus bytes, without ever waiting for a
-// whole file to be resident.
+// Everything this project moves from disk to the device: pileup files (or host buffers) and VCF files, streamed through
+// pinned memory without ever waiting for a whole file to be read.
 //
 // Replaces the way the reference feeds pileup.Reader (snppipeline/pileup.py:408-429: a text-mode line iterator over the
 // open file, driven from call_consensus.py:161) and the one-process-per-sample job array around it (run.py:704-718).
 // A pileup is 0.4 GB of text per 5 Mbp x 30x sample: the 10 000-sample target is 4 TB that can only pass through HBM,
 // so the rate that matters end to end is the host link's, and the job of this file is to keep that link busy:
 //
-//   reader threads   pread() the file (page cache) in chunks of whole 4 KiB scan tiles into a ring of PINNED staging
-//                    buffers — a kernel-side memcpy of ~5 GB/s per thread, hence several threads
-//   copy stream      one hipMemcpyAsync per chunk, staging -> the file's device buffer ("slot"), event per chunk
-//   compute stream   waits for the chunk's event and scans the tiles that are now complete (tile + 128-byte halo inside
-//                    the landed bytes) with the batch scan kernel restricted to that tile range (scan.hip:
-//                    snpgpu_scan_range); lines the fast parser leaves to the exact parser are queued with their file
+//   reader threads   pread() the files (page cache) piece by piece into a ring of PINNED staging buffers — a kernel-side
+//                    memcpy of ~5 GB/s per thread, hence several threads.  They never call HIP.
+//   issuing thread   waits for piece j, retires finished copies by polling their events (a staging buffer is refilled only
+//                    after the copy out of it has completed), copies the piece on one of two copy streams and records the
+//                    buffer's event.  Nobody waits after an abort.
+// That mechanism is Ring; what a consumer does between Ring::wait(j) and the recording of the copy event is its own.
+//
+// In file order:
+//   pool             the pinned staging buffers, copy streams and events, device slots and result blocks a context keeps
+//   Opener           opens the files of a batch a few ahead of the readers
+//   Ring             the in-order staging ring and its readers (read_piece, start_readers / stop_readers)
+//   run_stream       call_consensus over files or host buffers, in chunks of whole 4 KiB scan tiles.  On top of the ring:
+//                    times the wait; a read error marks the file SNPGPU_E_IO; the compute stream waits on the copy event
+//                    and scans the tiles that are now complete (tile + 128-byte halo inside the landed bytes; scan.hip:
+//                    snpgpu_scan_range).  Lines the fast parser leaves to the exact parser are queued with their file
 //                    offsets and finished when the file is complete, as is the call step (snpgpu_enqueue_call), which
-//                    reads the lines the scan selected straight from the slot
-//   results          base / filter bytes (+ optional per-site counts and line offsets) come back through pinned buffers
-// Files alternate between n_slots device buffers, so file k+1 streams in while file k's tail (last tiles, queue, call,
-// results) runs.  Everything on the compute stream is in order, so all device scratch is shared between files.
+//                    reads the lines the scan selected straight from the file's device buffer ("slot"); results come
+//                    back through pinned blocks.  Files alternate between n_slots slots, so file k+1 streams in while
+//                    file k's tail runs; the compute stream is in order, so all device scratch is shared between files.
+//   one-file loads   load_raw (and load_bgzf / load_file on it).  No opener thread; a read error fails the whole call; the
+//                    compute stream waits on nothing, both copy streams are synchronised at the end.
+//   all lines        --vcfAllPos: a record, or a VCF row, for every line of one loaded file
+//   site calling     varscan_resident(_batch) over text in device memory; varscan_stream over files, and the resident
+//                    store behind it.  Pass A copies the pieces of resident files in ANY order (its own retire loop);
+//                    pass B is the ring over jobs [JA, J), with opportunistic() before each wait.
+//   VCF streams      vcf_stream: pieces into a few device buffers, counted or parsed by a launch each.  The host may
+//                    append '\n' to the staged piece before the copy, and the copy also waits on ev_counted[b].
+//   merge_vcfs       the multi-sample VCF from the parsed pieces (vcf_merge.hip)
 #include <errno.h>
 #include <fcntl.h>
 #include <sched.h>
@@ -61,6 +78,36 @@ struct Job {
     bool first, last;
     uint32_t chunk;                 // index of the chunk inside its file
 };
+
+// In a function with `int rc` and a `done:` label behind which everything is undone (#undef'd where the last namespace ends).
+#define STREAM_TRY(expr)                                                                                            \
+    do {                                                                                                            \
+        hipError_t e_ = (expr);                                                                                     \
+        if (e_ != hipSuccess) { rc = snpgpu_set_error(ctx, SNPGPU_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); goto done; } \
+    } while (0)
+
+// The size of a file source.  What is no regular file is an I/O error of that file, with nothing to read.
+void size_source(Source &s) {
+    struct stat stt;
+    if (!s.path || stat(s.path, &stt) != 0 || !S_ISREG(stt.st_mode)) {
+        s.rc = SNPGPU_E_IO;
+        s.size = 0;
+    } else {
+        s.size = (uint64_t)stt.st_size;
+    }
+}
+
+// Readers and staging buffers for J jobs: no more readers than jobs, extra_staging buffers beyond one per reader, at least one.
+void ring_sizes(uint64_t J, uint32_t n_readers_wanted, uint32_t extra_staging, uint32_t *n_readers, uint32_t *n_staging) {
+    *n_readers = n_readers_wanted > J ? (uint32_t)J : n_readers_wanted;
+    *n_staging = *n_readers + extra_staging;
+    if (*n_staging > J) *n_staging = (uint32_t)J;
+    if (*n_staging < 1) *n_staging = 1;
+}
+
+// The first pieces of a load are small — 1, 1, 2, 4, 8 MiB, then `chunk` — so that the first copy starts after ~1 MiB has been
+// read instead of after a whole chunk (all readers start at once and each takes a few milliseconds per 16 MiB).
+inline uint64_t ramp_piece(uint64_t c, uint64_t chunk) { return c < 2 ? (uint64_t)1 << 20 : (c < 5 ? (uint64_t)1 << (18 + c) : chunk); }
 
 // The files of a batch are opened by a thread of their own, a few files ahead of the readers, and each is closed by the reader
 // that reads its last piece: at most OPEN_WINDOW of them are open at a time.  Opening all of them up front is what costs: a
@@ -234,29 +281,22 @@ int pool_ensure(snpgpu_ctx *ctx, size_t chunk_bytes, uint32_t n_staging, uint32_
         HIP_TRY(ctx, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
         p->ev_done.push_back(ev);
     }
-    if (p->result_bytes < result_bytes || p->result.size() < n_blocks) {
-        pool_free_host(p->result);
-        if (result_bytes < p->result_bytes) result_bytes = p->result_bytes;
-        for (size_t i = 0; i < n_blocks; ++i) {
+    // n pinned blocks of at least bytes_want each: all of them anew when there are too few or they are too small, never smaller
+    auto grow_pinned = [&](std::vector<void *> &vec, size_t n, size_t &bytes_have, size_t bytes_want) -> int {
+        if (bytes_have >= bytes_want && vec.size() >= n) return SNPGPU_OK;
+        pool_free_host(vec);
+        if (bytes_want < bytes_have) bytes_want = bytes_have;
+        for (size_t i = 0; i < n; ++i) {
             void *h = nullptr;
-            hipError_t e = hipHostMalloc(&h, result_bytes, hipHostMallocDefault);
-            if (e != hipSuccess) return snpgpu_set_error(ctx, SNPGPU_E_NOMEM, "hipHostMalloc(%zu) failed: %s", result_bytes, hipGetErrorString(e));
-            p->result.push_back(h);
+            hipError_t e = hipHostMalloc(&h, bytes_want, hipHostMallocDefault);
+            if (e != hipSuccess) return snpgpu_set_error(ctx, SNPGPU_E_NOMEM, "hipHostMalloc(%zu) failed: %s", bytes_want, hipGetErrorString(e));
+            vec.push_back(h);
         }
-        p->result_bytes = result_bytes;
-    }
-    if (p->table_bytes < table_bytes || p->table_host.size() < n_blocks) {
-        pool_free_host(p->table_host);
-        if (table_bytes < p->table_bytes) table_bytes = p->table_bytes;
-        for (size_t i = 0; i < n_blocks; ++i) {
-            void *h = nullptr;
-            hipError_t e = hipHostMalloc(&h, table_bytes, hipHostMallocDefault);
-            if (e != hipSuccess) return snpgpu_set_error(ctx, SNPGPU_E_NOMEM, "hipHostMalloc(%zu) failed: %s", table_bytes, hipGetErrorString(e));
-            p->table_host.push_back(h);
-        }
-        p->table_bytes = table_bytes;
-    }
-    return SNPGPU_OK;
+        bytes_have = bytes_want;
+        return SNPGPU_OK;
+    };
+    if (int rc = grow_pinned(p->result, n_blocks, p->result_bytes, result_bytes)) return rc;
+    return grow_pinned(p->table_host, n_blocks, p->table_bytes, table_bytes);
 }
 
 struct Outputs {
@@ -269,19 +309,71 @@ struct Outputs {
                                     // themselves, only the status words pass through the pinned result block
 };
 
-// What the readers and the orchestrator share.
+// One piece of a source into staging memory.  Returns the errno of a failed read (0: fine); whatever could not be read is
+// filled with newlines, so that the piece is blank lines to the kernels.
+int read_piece(Source &s, const Job &jb, uint8_t *dst) {
+    if (s.mem) {
+        memcpy(dst, s.mem + jb.off, jb.len);
+        return 0;
+    }
+    int err = 0;
+    uint64_t got = 0;
+    while (s.fd >= 0 && got < jb.len) {                     // (no descriptor: could not be opened, its result is void and rc says so)
+        ssize_t r = pread(s.fd, dst + got, jb.len - got, (off_t)(jb.off + got));
+        if (r < 0) { if (errno == EINTR) continue; err = errno ? errno : EIO; break; }
+        if (r == 0) { err = EIO; break; }                    // the file shrank under us
+        got += (uint64_t)r;
+    }
+    if (got < jb.len) memset(dst + got, '\n', jb.len - got);
+    return err;
+}
+
+// The reader threads of a Shared or an AnyOrder (below) take jobs [sh.next, n_jobs) off a counter.  stop_readers ends them:
+// after a failure they are told to give up — the opener first, so that none of them waits for a file, then `abort` for those that
+// wait on cv — otherwise they run out of jobs by themselves.  Safe to call again.
+template <class S>
+void stop_readers(S &sh, std::condition_variable &cv, uint64_t n_jobs, bool failed) {
+    if (sh.readers.empty()) return;
+    if (failed && sh.opener) sh.opener->cancel();
+    {
+        std::lock_guard<std::mutex> lk(sh.mu);
+        if (failed) { sh.abort = true; sh.next.store(n_jobs); }
+    }
+    cv.notify_all();
+    for (auto &t : sh.readers) t.join();
+    sh.readers.clear();
+}
+
+// size(): sizes what the readers share; then n threads that run main_fn(ctx, &sh, jobs, src).  No memory for the one or no thread for
+// the other is an error code, never an exception through the C ABI, and the threads that did start are stopped again.
+template <class S, class Size>
+int start_readers(snpgpu_ctx *ctx, S &sh, std::condition_variable &cv, uint64_t n_jobs, uint32_t n, Size size,
+                  void (*main_fn)(snpgpu_ctx *, S *, const std::vector<Job> *, std::vector<Source> *), const std::vector<Job> *jobs,
+                  std::vector<Source> *src) {
+    try {
+        size();
+        for (uint32_t i = 0; i < n; ++i) sh.readers.emplace_back(main_fn, ctx, &sh, jobs, src);
+    } catch (const std::exception &e) {                     // nothing has been enqueued yet
+        stop_readers(sh, cv, n_jobs, true);
+        return snpgpu_set_error(ctx, SNPGPU_E_NOMEM, "cannot start the reader threads: %s", e.what());
+    }
+    return SNPGPU_OK;
+}
+
+// What the readers and the issuing thread of the in-order ring share.
 struct Shared {
     std::mutex mu;
     std::condition_variable cv;
-    std::vector<uint8_t> filled;    // job j has been read into staging[j % R]
-    std::vector<int> job_err;       // errno of a failed read (0: fine)
-    int64_t freed = 0;              // jobs whose H2D copy has completed: their staging buffers can be refilled
+    std::vector<uint8_t> filled;    // [job - base] the job has been read into its staging buffer
+    std::vector<int> job_err;       // [job - base] errno of a failed read (0: fine)
+    int64_t freed = 0;              // places of the ring whose H2D copy has completed: their staging buffers can be refilled
     uint64_t R = 1;                 // staging buffers in the ring
     std::atomic<uint64_t> ns_reading{0}, ns_waiting{0};   // summed over the readers
     bool abort = false;
     std::atomic<uint64_t> next{0};
-    uint64_t base = 0;              // the ring serves jobs [base, ...): job j uses staging[(j - base) % R]
+    uint64_t base = 0, end = 0;     // the ring serves jobs [base, end): job j has place j - base and uses staging[(j - base) % R]
     Opener *opener = nullptr;       // (optional) the files are opened by another thread and closed by the last reader
+    std::vector<std::thread> readers;
 };
 
 void reader_main(snpgpu_ctx *ctx, Shared *sh, const std::vector<Job> *jobs, std::vector<Source> *src) {
@@ -290,7 +382,7 @@ void reader_main(snpgpu_ctx *ctx, Shared *sh, const std::vector<Job> *jobs, std:
     const uint64_t R = sh->R;
     for (;;) {
         const uint64_t j = sh->next.fetch_add(1);
-        if (j >= jobs->size()) return;
+        if (j >= sh->end) return;
         const Job &jb = (*jobs)[j];
         const double t_w = now_s();
         const uint64_t k = j - sh->base;                    // place in the ring
@@ -300,35 +392,61 @@ void reader_main(snpgpu_ctx *ctx, Shared *sh, const std::vector<Job> *jobs, std:
             if (sh->abort) return;
         }
         const double t_r = now_s();
-        uint8_t *dst = (uint8_t *)p->staging[k % R];
-        Source &s = (*src)[jb.file];
         if (sh->opener) sh->opener->wait(jb.file);
-        int err = 0;
-        if (s.mem) {
-            memcpy(dst, s.mem + jb.off, jb.len);
-        } else if (s.fd >= 0) {
-            uint64_t got = 0;
-            while (got < jb.len) {
-                ssize_t r = pread(s.fd, dst + got, jb.len - got, (off_t)(jb.off + got));
-                if (r < 0) { if (errno == EINTR) continue; err = errno ? errno : EIO; break; }
-                if (r == 0) { err = EIO; break; }            // the file shrank under us
-                got += (uint64_t)r;
-            }
-            if (err) memset(dst + got, '\n', jb.len - got);
-        } else {
-            memset(dst, '\n', jb.len);                       // could not be opened: its result is void (rc says so)
-        }
+        const int err = read_piece((*src)[jb.file], jb, (uint8_t *)p->staging[k % R]);
         if (sh->opener) sh->opener->done_reading(jb.file);
         sh->ns_waiting.fetch_add((uint64_t)((t_r - t_w) * 1e9));
         sh->ns_reading.fetch_add((uint64_t)((now_s() - t_r) * 1e9));
         {
             std::lock_guard<std::mutex> lk(sh->mu);
-            sh->filled[j] = 1;
-            sh->job_err[j] = err;
+            sh->filled[k] = 1;
+            sh->job_err[k] = err;
         }
         sh->cv.notify_all();
     }
 }
+
+// The in-order staging ring: reader threads fill staging[(j - base) % R] with job j; the issuing thread — the only one that calls
+// HIP — takes the jobs in order: wait(j), then the copy out of staging(j) on copy_stream(j), then copy_event(j) recorded behind
+// it.  A staging buffer goes back to the readers only when the copy out of it has completed, which wait() learns by polling the
+// events in order.
+struct Ring : Shared {
+    snpgpu_stream_pool *p = nullptr;
+    int64_t copies_done = 0;        // the copies of places [0, copies_done) have completed
+
+    // Readers for jobs [first_job, first_job + n_jobs) over the first R staging buffers of the pool.  opener: nullptr when the
+    // sources are open already.  On failure nothing is left running.
+    int start(snpgpu_ctx *ctx, const std::vector<Job> *jobs, std::vector<Source> *src, uint64_t first_job, uint64_t n_jobs, uint64_t n_ring,
+              uint32_t n_readers, Opener *opener_or_null) {
+        p = ctx->pool;
+        R = n_ring ? n_ring : 1;
+        base = first_job;
+        end = first_job + n_jobs;
+        next.store(first_job);
+        opener = opener_or_null;
+        return start_readers<Shared>(ctx, *this, cv, end, n_readers, [&] { filled.assign(n_jobs, 0); job_err.assign(n_jobs, 0); }, reader_main, jobs, src);
+    }
+    // Waits until job j has been read; meanwhile retires finished copies so that their buffers go back to the readers.  Returns
+    // the errno of the job's read (0: fine).
+    int wait(uint64_t j) {
+        const int64_t k = (int64_t)(j - base);
+        for (;;) {
+            bool progress = false;
+            while (copies_done < k && hipEventQuery(p->ev_copy[copies_done % R]) != hipErrorNotReady) { ++copies_done; progress = true; }   // (an error counts as done: the next HIP call reports it, nobody waits forever)
+            std::unique_lock<std::mutex> lk(mu);
+            if (progress) { freed = copies_done; lk.unlock(); cv.notify_all(); lk.lock(); }
+            if (filled[k]) return job_err[k];
+            cv.wait_for(lk, std::chrono::microseconds(copies_done < k ? 20 : 2000), [&] { return filled[k] != 0; });
+            if (filled[k]) return job_err[k];
+        }
+    }
+    void *staging(uint64_t j) const { return p->staging[(j - base) % R]; }
+    hipEvent_t copy_event(uint64_t j) const { return p->ev_copy[(j - base) % R]; }
+    hipStream_t copy_stream(uint64_t j) const { return (j & 1) ? p->copy_stream2 : p->copy_stream; }    // chunks alternate by job index
+    // failed: the readers give up; otherwise they have read every job by now, or will.  Joins them either way.
+    void stop(bool failed) { stop_readers<Shared>(*this, cv, end, failed); }
+    ~Ring() { stop(true); }
+};
 
 struct DevScratch {                 // one carve-up of the context's scratch, shared by all files (the compute stream is in order)
     SampleDev *tables;              // [n_slots][table entries]
@@ -370,15 +488,7 @@ int run_stream(snpgpu_ctx *ctx, const snpgpu_siteset *ss, std::vector<Source> &s
     // ---- sources and jobs -------------------------------------------------------------------------------------
     uint64_t max_size = 0, total_bytes = 0;
     for (auto &s : src) {
-        if (s.path) {                                           // (sized here, opened by the opener thread as the readers get to it)
-            struct stat stt;
-            if (stat(s.path, &stt) != 0 || !S_ISREG(stt.st_mode)) {
-                s.rc = SNPGPU_E_IO;
-                s.size = 0;
-            } else {
-                s.size = (uint64_t)stt.st_size;
-            }
-        }
+        if (s.path) size_source(s);                             // (sized here, opened by the opener thread as the readers get to it)
         if (s.size > max_size && !s.dev) max_size = s.size;
         total_bytes += s.size;
     }
@@ -401,14 +511,9 @@ int run_stream(snpgpu_ctx *ctx, const snpgpu_siteset *ss, std::vector<Source> &s
     opener.start(&src, chunks_of);                          // (the first files open while the staging memory is being pinned)
 
     // ---- resources ----------------------------------------------------------------------------------------------
-    uint32_t n_readers = opts && opts->n_readers ? opts->n_readers : 0;
-    if (!n_readers) {
-        n_readers = snpgpu_reader_threads();                     // the CPU budget of this process, not the box's CPU count
-    }
-    if (n_readers > J) n_readers = (uint32_t)J;
-    uint32_t n_staging = opts && opts->n_staging ? opts->n_staging : n_readers + 4;
-    if (n_staging > J) n_staging = (uint32_t)J;
-    if (n_staging < 1) n_staging = 1;
+    uint32_t n_readers, n_staging;                              // (the CPU budget of this process, not the box's CPU count)
+    ring_sizes(J, opts && opts->n_readers ? opts->n_readers : snpgpu_reader_threads(), 4, &n_readers, &n_staging);
+    if (opts && opts->n_staging) n_staging = (uint32_t)std::min<uint64_t>(opts->n_staging, J);
     uint32_t n_slots = opts && opts->n_slots ? opts->n_slots : 2;
     if (n_slots > n_files) n_slots = n_files;
     const size_t slot_bytes = up(max_size + SNPGPU_SCAN_TILE + 256, 4096);
@@ -422,8 +527,7 @@ int run_stream(snpgpu_ctx *ctx, const snpgpu_siteset *ss, std::vector<Source> &s
         int rc = pool_ensure(ctx, chunk, n_staging, n_slots, slot_bytes, result_bytes, table_bytes);
         if (rc) { close_all(); return rc; }
     }
-    snpgpu_stream_pool *p = ctx->pool;
-    const uint64_t R = p->staging.size() < n_staging ? p->staging.size() : n_staging;   // ring actually used
+    snpgpu_stream_pool *p = ctx->pool;                          // (it holds n_staging buffers or more: the ring uses n_staging)
     DevScratch ds;
     {
         const size_t list_bytes = up(8ull * n_sites, 256);
@@ -462,24 +566,10 @@ int run_stream(snpgpu_ctx *ctx, const snpgpu_siteset *ss, std::vector<Source> &s
         }
     }
 
-    Shared sh;
-    sh.R = R;
-    sh.filled.assign(J, 0);
-    sh.job_err.assign(J, 0);
-    sh.opener = &opener;
-    std::vector<std::thread> readers;
-    try {
-        for (uint32_t i = 0; i < n_readers; ++i) readers.emplace_back(reader_main, ctx, &sh, &jobs, &src);
-    } catch (const std::exception &e) {                      // no thread to be had: nothing has been enqueued yet
-        opener.cancel();
-        { std::lock_guard<std::mutex> lk(sh.mu); sh.abort = true; sh.next.store(J); }
-        sh.cv.notify_all();
-        for (auto &t : readers) t.join();
-        close_all();
-        return snpgpu_set_error(ctx, SNPGPU_E_NOMEM, "cannot start the reader threads: %s", e.what());
-    }
+    Ring ring;
+    int rc = ring.start(ctx, &jobs, &src, 0, J, n_staging, n_readers, &opener);
+    if (rc) { close_all(); return rc; }
 
-    int rc = SNPGPU_OK;
     double t_wait_read = 0, t_wait_gpu = 0, t_enqueue = 0;
     auto harvest = [&](uint32_t f) -> int {                  // results of file f: pinned block -> the caller's arrays
         const uint32_t slot = f % (uint32_t)p->slot.size();
@@ -500,17 +590,10 @@ int run_stream(snpgpu_ctx *ctx, const snpgpu_siteset *ss, std::vector<Source> &s
             src[f].rc = (stw[0] & 0xFF) == SCAN_ERR_NON_ASCII ? SNPGPU_E_UNSUPPORTED : SNPGPU_E_PILEUP;
         return SNPGPU_OK;
     };
-#define ST_TRY(expr)                                                                                                \
-    do {                                                                                                            \
-        hipError_t e_ = (expr);                                                                                     \
-        if (e_ != hipSuccess) { rc = snpgpu_set_error(ctx, SNPGPU_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); goto done; } \
-    } while (0)
-
     {
         uint32_t harvested = 0;                              // files [0, harvested) have been copied out
         uint32_t cur_waves = 0;                              // waves of the final (whole-file) table entry of the current file
         uint32_t tiles_done = 0;
-        int64_t copies_done = 0;                             // copies [0, copies_done) have completed (events polled in order)
         for (uint64_t j = 0; j < J; ++j) {
             const Job &jb = jobs[j];
             const uint32_t f = jb.file, slot = f % (uint32_t)p->slot.size();
@@ -549,30 +632,20 @@ int run_stream(snpgpu_ctx *ctx, const snpgpu_siteset *ss, std::vector<Source> &s
                 }
                 cur_waves = h_tab[2 * nc + 1].wave0;
                 tiles_done = 0;
-                ST_TRY(hipMemcpyAsync(d_tab, h_tab, (size_t)(nc + 1) * 2 * sizeof(SampleDev), hipMemcpyHostToDevice, st));
+                STREAM_TRY(hipMemcpyAsync(d_tab, h_tab, (size_t)(nc + 1) * 2 * sizeof(SampleDev), hipMemcpyHostToDevice, st));
                 rc = snpgpu_scan_begin(ctx, ss, d_tab + 2 * nc, 1, f_line, ds.todo_n, SNPGPU_CALL_PASSES - 1);
                 if (rc) goto done;
             }
             {
-                // wait for the chunk to be read; meanwhile retire finished copies so that their buffers go back to the readers
                 const double t0 = now_s();
-                for (;;) {
-                    bool progress = false;
-                    while (copies_done < (int64_t)j && hipEventQuery(p->ev_copy[copies_done % R]) != hipErrorNotReady) { ++copies_done; progress = true; }   // (an error counts as done: the next HIP call reports it, nobody waits forever)
-                    std::unique_lock<std::mutex> lk(sh.mu);
-                    if (progress) { sh.freed = copies_done; lk.unlock(); sh.cv.notify_all(); lk.lock(); }
-                    if (sh.filled[j]) break;
-                    sh.cv.wait_for(lk, std::chrono::microseconds(copies_done < (int64_t)j ? 20 : 2000), [&] { return sh.filled[j] != 0; });
-                    if (sh.filled[j]) break;
-                }
-                if (sh.job_err[j] && s.rc == SNPGPU_OK) s.rc = SNPGPU_E_IO;
+                if (ring.wait(j) && s.rc == SNPGPU_OK) s.rc = SNPGPU_E_IO;
                 t_wait_read += now_s() - t0;
             }
             const double t_e = now_s();
-            hipStream_t cs = (j & 1) ? p->copy_stream2 : p->copy_stream;
-            if (jb.len) ST_TRY(hipMemcpyAsync(d_file + jb.off, p->staging[j % R], jb.len, hipMemcpyHostToDevice, cs));
-            ST_TRY(hipEventRecord(p->ev_copy[j % R], cs));
-            ST_TRY(hipStreamWaitEvent(st, p->ev_copy[j % R], 0));
+            hipStream_t cs = ring.copy_stream(j);
+            if (jb.len) STREAM_TRY(hipMemcpyAsync(d_file + jb.off, ring.staging(j), jb.len, hipMemcpyHostToDevice, cs));
+            STREAM_TRY(hipEventRecord(ring.copy_event(j), cs));
+            STREAM_TRY(hipStreamWaitEvent(st, ring.copy_event(j), 0));
             const SampleDev &e = h_tab[2 * jb.chunk];
             if (e.tile_hi > tiles_done) {
                 rc = snpgpu_scan_range(ctx, ss, d_tab + 2 * jb.chunk, 1, h_tab[2 * jb.chunk + 1].wave0, ds.totals, f_line, want_depth);
@@ -591,7 +664,7 @@ int run_stream(snpgpu_ctx *ctx, const snpgpu_siteset *ss, std::vector<Source> &s
                     memcpy(hf, ss->h_flags.data(), n_sites);
                     for (uint32_t k = excl_off[f]; k < excl_off[f + 1]; ++k) hf[excl_slots[k]] |= SNPGPU_SITE_EXCLUDED;
                     uint8_t *d_row = ds.flag_rows + ds.flag_row_stride * slot;
-                    ST_TRY(hipMemcpyAsync(d_row, hf, n_sites, hipMemcpyHostToDevice, st));
+                    STREAM_TRY(hipMemcpyAsync(d_row, hf, n_sites, hipMemcpyHostToDevice, st));
                     d_flags = d_row;
                 }
                 if (rc == SNPGPU_OK)
@@ -601,34 +674,27 @@ int run_stream(snpgpu_ctx *ctx, const snpgpu_siteset *ss, std::vector<Source> &s
                 if (to_dev && n_sites && s.rc == SNPGPU_E_IO) {
                     // could not be opened or read (known by now: the last piece has been waited for): its rows are void, and in the
                     // caller's arrays that is '-' / 0 / no line / zeroed records rather than whatever the pieces that did arrive gave
-                    ST_TRY(hipMemsetAsync(f_base, '-', n_sites, st));
-                    ST_TRY(hipMemsetAsync(f_filt, 0, n_sites, st));
-                    if (out.line_off) ST_TRY(hipMemsetAsync(f_line, 0, 8ull * n_sites, st));
-                    if (out.counts) ST_TRY(hipMemsetAsync(f_counts, 0, sizeof(snpgpu_site_counts) * (size_t)n_sites, st));
+                    STREAM_TRY(hipMemsetAsync(f_base, '-', n_sites, st));
+                    STREAM_TRY(hipMemsetAsync(f_filt, 0, n_sites, st));
+                    if (out.line_off) STREAM_TRY(hipMemsetAsync(f_line, 0, 8ull * n_sites, st));
+                    if (out.counts) STREAM_TRY(hipMemsetAsync(f_counts, 0, sizeof(snpgpu_site_counts) * (size_t)n_sites, st));
                 }
                 if (n_sites && !to_dev) {
-                    ST_TRY(hipMemcpyAsync(r + r_base, ds.base, n_sites, hipMemcpyDeviceToHost, st));
-                    ST_TRY(hipMemcpyAsync(r + r_filt, ds.filters, n_sites, hipMemcpyDeviceToHost, st));
-                    if (out.line_off) ST_TRY(hipMemcpyAsync(r + r_line, ds.site_line, 8ull * n_sites, hipMemcpyDeviceToHost, st));
-                    if (out.counts) ST_TRY(hipMemcpyAsync(r + r_cnt, ds.counts, sizeof(snpgpu_site_counts) * (size_t)n_sites, hipMemcpyDeviceToHost, st));
+                    STREAM_TRY(hipMemcpyAsync(r + r_base, ds.base, n_sites, hipMemcpyDeviceToHost, st));
+                    STREAM_TRY(hipMemcpyAsync(r + r_filt, ds.filters, n_sites, hipMemcpyDeviceToHost, st));
+                    if (out.line_off) STREAM_TRY(hipMemcpyAsync(r + r_line, ds.site_line, 8ull * n_sites, hipMemcpyDeviceToHost, st));
+                    if (out.counts) STREAM_TRY(hipMemcpyAsync(r + r_cnt, ds.counts, sizeof(snpgpu_site_counts) * (size_t)n_sites, hipMemcpyDeviceToHost, st));
                 }
-                ST_TRY(hipMemcpyAsync(r + r_stat, ds.status, 8 * SNPGPU_SCAN_STATUS_WORDS, hipMemcpyDeviceToHost, st));
+                STREAM_TRY(hipMemcpyAsync(r + r_stat, ds.status, 8 * SNPGPU_SCAN_STATUS_WORDS, hipMemcpyDeviceToHost, st));
                 // (the next file that uses this slot is not started before this event has been waited for in harvest())
-                ST_TRY(hipEventRecord(p->ev_done[slot], st));
+                STREAM_TRY(hipEventRecord(p->ev_done[slot], st));
             }
             t_enqueue += now_s() - t_e;
         }
         while (harvested < n_files) { rc = harvest(harvested); if (rc) goto done; ++harvested; }
     }
 done:
-#undef ST_TRY
-    if (rc) opener.cancel();
-    {
-        std::lock_guard<std::mutex> lk(sh.mu);
-        if (rc) { sh.abort = true; sh.next.store(J); }
-    }
-    sh.cv.notify_all();
-    for (auto &t : readers) t.join();
+    ring.stop(rc != SNPGPU_OK);
     if (rc) { (void)hipStreamSynchronize(p->copy_stream); (void)hipStreamSynchronize(p->copy_stream2); (void)hipStreamSynchronize(st); }
     close_all();
     if (out.rc) for (uint32_t f = 0; f < n_files; ++f) out.rc[f] = src[f].rc;
@@ -639,10 +705,10 @@ done:
         stats->seconds_waiting_for_device = t_wait_gpu;
         stats->n_chunks = J;
         stats->n_readers = n_readers;
-        stats->n_staging = (uint32_t)R;
+        stats->n_staging = n_staging;
         stats->chunk_bytes = (uint32_t)chunk;
-        stats->reader_seconds_reading = sh.ns_reading.load() * 1e-9;
-        stats->reader_seconds_waiting = sh.ns_waiting.load() * 1e-9;
+        stats->reader_seconds_reading = ring.ns_reading.load() * 1e-9;
+        stats->reader_seconds_waiting = ring.ns_waiting.load() * 1e-9;
         stats->seconds_enqueueing = t_enqueue;
     }
     return rc;
@@ -666,63 +732,33 @@ int load_raw(snpgpu_ctx *ctx, const char *path, uint32_t n_slots, size_t min_slo
     (void)posix_fadvise(s.fd, 0, 0, POSIX_FADV_SEQUENTIAL);
     const size_t chunk = (size_t)16 << 20;
     std::vector<Job> jobs;
-    // the first pieces are small, so that the first copy starts after ~1 MiB has been read instead of after 16 (all readers
-    // start at once and each takes a few milliseconds per 16 MiB)
-    for (uint64_t off = 0, c = 0; off < n; ++c) {
-        const uint64_t want = c < 2 ? (uint64_t)1 << 20 : (c < 5 ? (uint64_t)1 << (18 + c) : chunk);      // 1, 1, 2, 4, 8, 16, 16, ... MiB
-        const uint64_t len = n - off < want ? n - off : want;
+    for (uint64_t off = 0, c = 0; off < n; ++c) {                // 1, 1, 2, 4, 8, 16, 16, ... MiB
+        const uint64_t want = ramp_piece(c, chunk), len = n - off < want ? n - off : want;
         jobs.push_back(Job{0, off, len, c == 0, off + len >= n, (uint32_t)c});
         off += len;
     }
     const uint64_t J = jobs.size();
-    uint32_t n_readers = snpgpu_reader_threads();
-    if (n_readers > J) n_readers = (uint32_t)J;
-    uint32_t n_staging = n_readers + 4;
-    if (n_staging > J) n_staging = (uint32_t)J;
-    if (n_staging < 1) n_staging = 1;
+    uint32_t n_readers, n_staging;
+    ring_sizes(J, snpgpu_reader_threads(), 4, &n_readers, &n_staging);
     size_t slot_bytes = up(n + SNPGPU_SCAN_TILE + 256, 4096);
     if (slot_bytes < min_slot_bytes) slot_bytes = min_slot_bytes;
     int rc = pool_ensure(ctx, chunk, n_staging, n_slots, slot_bytes, 256, 256);
     if (rc) { close(s.fd); return rc; }
     snpgpu_stream_pool *p = ctx->pool;
-    const uint64_t R = p->staging.size() < n_staging ? p->staging.size() : n_staging;
     uint8_t *d = (uint8_t *)p->slot[0];
     hipError_t he = hipStreamSynchronize(ctx->stream);          // earlier work on the slot is done
-    Shared sh;
-    sh.R = R ? R : 1;
-    sh.filled.assign(J, 0);
-    sh.job_err.assign(J, 0);
-    std::vector<std::thread> readers;
+    Ring ring;
     bool io_failed = false;
     if (he == hipSuccess && J) {
-        try {
-            for (uint32_t i = 0; i < n_readers; ++i) readers.emplace_back(reader_main, ctx, &sh, &jobs, &src);
-        } catch (const std::exception &e) {
-            { std::lock_guard<std::mutex> lk(sh.mu); sh.abort = true; sh.next.store(J); }
-            sh.cv.notify_all();
-            for (auto &t : readers) t.join();
-            close(s.fd);
-            return snpgpu_set_error(ctx, SNPGPU_E_NOMEM, "cannot start the reader threads: %s", e.what());
-        }
-        int64_t copies_done = 0;
+        rc = ring.start(ctx, &jobs, &src, 0, J, n_staging, n_readers, nullptr);
+        if (rc) { close(s.fd); return rc; }
         for (uint64_t j = 0; j < J && he == hipSuccess; ++j) {
-            for (;;) {                                          // wait for chunk j; retire finished copies meanwhile
-                bool progress = false;
-                while (copies_done < (int64_t)j && hipEventQuery(p->ev_copy[copies_done % R]) != hipErrorNotReady) { ++copies_done; progress = true; }   // (an error counts as done: the next HIP call reports it, nobody waits forever)
-                std::unique_lock<std::mutex> lk(sh.mu);
-                if (progress) { sh.freed = copies_done; lk.unlock(); sh.cv.notify_all(); lk.lock(); }
-                if (sh.filled[j]) break;
-                sh.cv.wait_for(lk, std::chrono::microseconds(copies_done < (int64_t)j ? 20 : 2000), [&] { return sh.filled[j] != 0; });
-                if (sh.filled[j]) break;
-            }
-            if (sh.job_err[j]) io_failed = true;
-            hipStream_t cs = (j & 1) ? p->copy_stream2 : p->copy_stream;
-            he = hipMemcpyAsync(d + jobs[j].off, p->staging[j % R], jobs[j].len, hipMemcpyHostToDevice, cs);
-            if (he == hipSuccess) he = hipEventRecord(p->ev_copy[j % R], cs);
+            if (ring.wait(j)) io_failed = true;
+            hipStream_t cs = ring.copy_stream(j);
+            he = hipMemcpyAsync(d + jobs[j].off, ring.staging(j), jobs[j].len, hipMemcpyHostToDevice, cs);
+            if (he == hipSuccess) he = hipEventRecord(ring.copy_event(j), cs);
         }
-        { std::lock_guard<std::mutex> lk(sh.mu); if (he != hipSuccess) { sh.abort = true; sh.next.store(J); } }
-        sh.cv.notify_all();
-        for (auto &t : readers) t.join();
+        ring.stop(he != hipSuccess);
         hipError_t e1 = hipStreamSynchronize(p->copy_stream), e2 = hipStreamSynchronize(p->copy_stream2);
         if (he == hipSuccess) he = e1 != hipSuccess ? e1 : e2;
     }
@@ -1377,6 +1413,7 @@ struct AnyOrder {
     uint64_t n_jobs = 0;
     std::atomic<uint64_t> ns_reading{0}, ns_waiting{0};
     Opener *opener = nullptr;
+    std::vector<std::thread> readers;
 };
 
 void reader_any_order(snpgpu_ctx *ctx, AnyOrder *sh, const std::vector<Job> *jobs, std::vector<Source> *src) {
@@ -1386,7 +1423,6 @@ void reader_any_order(snpgpu_ctx *ctx, AnyOrder *sh, const std::vector<Job> *job
         const uint64_t j = sh->next.fetch_add(1);
         if (j >= sh->n_jobs) return;
         const Job &jb = (*jobs)[j];
-        Source &s = (*src)[jb.file];
         int32_t buf = -1;
         int err = 0;
         if (jb.len) {
@@ -1400,19 +1436,7 @@ void reader_any_order(snpgpu_ctx *ctx, AnyOrder *sh, const std::vector<Job> *job
                 sh->free_bufs.pop_back();
             }
             const double t_r = now_s();
-            uint8_t *dst = (uint8_t *)p->staging[buf];
-            if (s.fd >= 0) {
-                uint64_t got = 0;
-                while (got < jb.len) {
-                    ssize_t r = pread(s.fd, dst + got, jb.len - got, (off_t)(jb.off + got));
-                    if (r < 0) { if (errno == EINTR) continue; err = errno ? errno : EIO; break; }
-                    if (r == 0) { err = EIO; break; }
-                    got += (uint64_t)r;
-                }
-                if (err) memset(dst + got, '\n', jb.len - got);
-            } else {
-                memset(dst, '\n', jb.len);
-            }
+            err = read_piece((*src)[jb.file], jb, (uint8_t *)p->staging[buf]);
             sh->ns_waiting.fetch_add((uint64_t)((t_r - t_w) * 1e9));
             sh->ns_reading.fetch_add((uint64_t)((now_s() - t_r) * 1e9));
         }
@@ -1453,13 +1477,7 @@ int varscan_stream(snpgpu_ctx *ctx, const char *const *paths, uint32_t n_files, 
     for (uint32_t f = 0; f < n_files; ++f) {
         Source &s = src[f];
         s.path = paths[f];
-        struct stat stt;                                        // (the file itself is opened later, by the opener thread)
-        if (stat(s.path, &stt) != 0 || !S_ISREG(stt.st_mode)) {
-            s.rc = SNPGPU_E_IO;
-            s.size = 0;
-        } else {
-            s.size = (uint64_t)stt.st_size;
-        }
+        size_source(s);                                         // (the file itself is opened later, by the opener thread)
         bool resident = false;
         if (budget_left && s.rc == SNPGPU_OK) {
             const uint64_t need = up(s.size + 1, 256);
@@ -1498,9 +1516,7 @@ int varscan_stream(snpgpu_ctx *ctx, const char *const *paths, uint32_t n_files, 
         if (f == n_prefix) JA = jobs.size();
         if (n == 0) { jobs.push_back(Job{f, 0, 0, true, true, 0}); chunks_left[f] = 1; continue; }
         for (uint64_t off = 0, c = 0; off < n; ++c) {
-            // the very first pieces are small, so that the first copy starts after ~1 MiB has been read
-            const uint64_t want = f == 0 && c < 5 ? (c < 2 ? (uint64_t)1 << 20 : (uint64_t)1 << (18 + c)) : chunk;
-            const uint64_t len = n - off < want ? n - off : want;
+            const uint64_t want = f == 0 ? ramp_piece(c, chunk) : chunk, len = n - off < want ? n - off : want;
             jobs.push_back(Job{f, off, len, c == 0, off + len >= n, (uint32_t)c});
             ++chunks_left[f];
             off += len;
@@ -1514,11 +1530,9 @@ int varscan_stream(snpgpu_ctx *ctx, const char *const *paths, uint32_t n_files, 
     if (const char *e = getenv("SNPGPU_INGEST_READERS")) if (atoi(e) > 0) n_readers = (uint32_t)atoi(e);
     if (const char *e = getenv("SNPGPU_INGEST_EXTRA_STAGING")) if (atoi(e) >= 0) extra_staging = (uint32_t)atoi(e);
 #endif
-    if (n_readers > J) n_readers = (uint32_t)J;
+    uint32_t n_staging;
+    ring_sizes(J, n_readers, extra_staging, &n_readers, &n_staging);
     if (store) store->n_readers = n_readers;
-    uint32_t n_staging = n_readers + extra_staging;
-    if (n_staging > J) n_staging = (uint32_t)J;
-    if (n_staging < 1) n_staging = 1;
     const size_t r_rec = 256;                                  // result block: [0] u64 status, [8] u32 records found, [48] u32 lines; records at 256
     const size_t result_bytes = r_rec + sizeof(snpgpu_varscan_site) * (size_t)capacity + 256;
     Opener opener;
@@ -1529,8 +1543,7 @@ int varscan_stream(snpgpu_ctx *ctx, const char *const *paths, uint32_t n_files, 
     int rc = pool_ensure(ctx, chunk, n_staging, any_slot ? n_slots : 0, any_slot ? up(max_slot_size + SNPGPU_SCAN_TILE + 256, 4096) : 0,
                          result_bytes, 256, n_slots);
     if (rc) { close_all(); return rc; }
-    snpgpu_stream_pool *p = ctx->pool;
-    const uint64_t R = p->staging.size() < n_staging ? p->staging.size() : n_staging;
+    snpgpu_stream_pool *p = ctx->pool;                          // (both passes use its first n_staging staging buffers)
     hipStream_t st = ctx->stream;
     [[maybe_unused]] const double t_pool = now_s();
     {
@@ -1638,30 +1651,15 @@ int varscan_stream(snpgpu_ctx *ctx, const char *const *paths, uint32_t n_files, 
             r = harvest(harvested++);
         return r;
     };
-#define VS_TRY(expr)                                                                                                \
-    do {                                                                                                            \
-        hipError_t e_ = (expr);                                                                                     \
-        if (e_ != hipSuccess) { rc = snpgpu_set_error(ctx, SNPGPU_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); goto done; } \
-    } while (0)
     {
         // ---- pass A: the resident prefix, pieces copied in the order in which their reads finish -----------------------------
         if (JA) {
             AnyOrder sh;
             sh.n_jobs = JA;
             sh.opener = &opener;
-            for (uint32_t i = 0; i < R; ++i) sh.free_bufs.push_back(i);
-            std::vector<std::thread> readers;
-            const uint32_t nr = n_readers < JA ? n_readers : (uint32_t)JA;
-            try {
-                for (uint32_t i = 0; i < nr; ++i) readers.emplace_back(reader_any_order, ctx, &sh, &jobs, &src);
-            } catch (const std::exception &e) {
-                opener.cancel();
-                { std::lock_guard<std::mutex> lk(sh.mu); sh.abort = true; sh.next.store(JA); }
-                sh.cv_free.notify_all();
-                for (auto &t : readers) t.join();
-                rc = snpgpu_set_error(ctx, SNPGPU_E_NOMEM, "cannot start the reader threads: %s", e.what());
-                goto done;
-            }
+            rc = start_readers(ctx, sh, sh.cv_free, JA, n_readers < JA ? n_readers : (uint32_t)JA,
+                               [&] { for (uint32_t i = 0; i < n_staging; ++i) sh.free_bufs.push_back(i); }, reader_any_order, &jobs, &src);
+            if (rc) goto done;
             // The blocks are allocated by a helper thread, in the order in which they will be needed, while this thread copies
             // into the ones that exist: an allocation from the driver costs ~15 ms per GiB (and many times that for memory that
             // was freed a moment ago), about as long as the copy into it, but it does not hold up copies issued by another thread
@@ -1753,13 +1751,7 @@ int varscan_stream(snpgpu_ctx *ctx, const char *const *paths, uint32_t n_files, 
                 ++issued;
                 if (--chunks_left[f] == 0) rcA = file_complete(f);
             }
-            if (rcA) opener.cancel();
-            {
-                std::lock_guard<std::mutex> lk(sh.mu);
-                if (rcA) { sh.abort = true; sh.next.store(JA); }
-            }
-            sh.cv_free.notify_all();
-            for (auto &t : readers) t.join();
+            stop_readers(sh, sh.cv_free, JA, rcA != SNPGPU_OK);
             if (rcA) alloc_stop.store(true);
             if (allocator.joinable()) allocator.join();
 #ifdef SNPGPU_TUNING
@@ -1770,30 +1762,14 @@ int varscan_stream(snpgpu_ctx *ctx, const char *const *paths, uint32_t n_files, 
             ns_waiting += sh.ns_waiting.load();
             if (rcA) { rc = rcA; goto done; }
             // every staging buffer is free again before the in-order ring of pass B uses them
-            if (JA < J) { VS_TRY(hipStreamSynchronize(p->copy_stream)); VS_TRY(hipStreamSynchronize(p->copy_stream2)); }
+            if (JA < J) { STREAM_TRY(hipStreamSynchronize(p->copy_stream)); STREAM_TRY(hipStreamSynchronize(p->copy_stream2)); }
         }
         // ---- pass B: files that go through the device slots, pieces in file order -------------------------------------------
         if (JA < J) {
-            Shared sh;
-            sh.R = R ? R : 1;
-            sh.filled.assign(J, 0);
-            sh.job_err.assign(J, 0);
-            sh.next.store(JA);
-            sh.base = JA;
-            sh.opener = &opener;
-            std::vector<std::thread> readers;
-            try {
-                for (uint32_t i = 0; i < n_readers; ++i) readers.emplace_back(reader_main, ctx, &sh, &jobs, &src);
-            } catch (const std::exception &e) {
-                opener.cancel();
-                { std::lock_guard<std::mutex> lk(sh.mu); sh.abort = true; sh.next.store(J); }
-                sh.cv.notify_all();
-                for (auto &t : readers) t.join();
-                rc = snpgpu_set_error(ctx, SNPGPU_E_NOMEM, "cannot start the reader threads: %s", e.what());
-                goto done;
-            }
+            Ring ring;
+            rc = ring.start(ctx, &jobs, &src, JA, J - JA, n_staging, n_readers, &opener);
+            if (rc) goto done;
             int rcB = SNPGPU_OK;
-            int64_t copies_done = (int64_t)JA;
             for (uint64_t j = JA; j < J && !rcB; ++j) {
                 const Job &jb = jobs[j];
                 const uint32_t f = jb.file;
@@ -1809,41 +1785,25 @@ int varscan_stream(snpgpu_ctx *ctx, const char *const *paths, uint32_t n_files, 
                 }
                 uint8_t *d_file = dest(f);
                 const double tr = now_s();
-                for (;;) {                                      // wait for the piece to be read; retire finished copies meanwhile
-                    bool progress = false;
-                    while (copies_done < (int64_t)j && hipEventQuery(p->ev_copy[(copies_done - JA) % R]) != hipErrorNotReady) { ++copies_done; progress = true; }
-                    std::unique_lock<std::mutex> lk(sh.mu);
-                    if (progress) { sh.freed = copies_done - (int64_t)JA; lk.unlock(); sh.cv.notify_all(); lk.lock(); }
-                    if (sh.filled[j]) break;
-                    sh.cv.wait_for(lk, std::chrono::microseconds(copies_done < (int64_t)j ? 20 : 2000), [&] { return sh.filled[j] != 0; });
-                    if (sh.filled[j]) break;
-                }
+                if (ring.wait(j) && s.rc == SNPGPU_OK) s.rc = SNPGPU_E_IO;
                 t_read_wait += now_s() - tr;
-                if (sh.job_err[j] && s.rc == SNPGPU_OK) s.rc = SNPGPU_E_IO;
-                hipStream_t cs = (j & 1) ? p->copy_stream2 : p->copy_stream;
+                hipStream_t cs = ring.copy_stream(j);
                 hipError_t e = hipSuccess;
-                if (jb.len) e = hipMemcpyAsync(d_file + jb.off, p->staging[(j - JA) % R], jb.len, hipMemcpyHostToDevice, cs);
+                if (jb.len) e = hipMemcpyAsync(d_file + jb.off, ring.staging(j), jb.len, hipMemcpyHostToDevice, cs);
                 if (store) store->h2d_bytes += jb.len;
-                if (e == hipSuccess) e = hipEventRecord(p->ev_copy[(j - JA) % R], cs);
-                if (e == hipSuccess) e = hipStreamWaitEvent(st, p->ev_copy[(j - JA) % R], 0);
+                if (e == hipSuccess) e = hipEventRecord(ring.copy_event(j), cs);
+                if (e == hipSuccess) e = hipStreamWaitEvent(st, ring.copy_event(j), 0);
                 if (e != hipSuccess) { rcB = snpgpu_set_error(ctx, SNPGPU_E_HIP, "copying a piece of %s failed: %s", s.path, hipGetErrorString(e)); break; }
                 if (jb.last) rcB = file_complete(f);
             }
-            if (rcB) opener.cancel();
-            {
-                std::lock_guard<std::mutex> lk(sh.mu);
-                if (rcB) { sh.abort = true; sh.next.store(J); }
-            }
-            sh.cv.notify_all();
-            for (auto &t : readers) t.join();
-            ns_reading += sh.ns_reading.load();
-            ns_waiting += sh.ns_waiting.load();
+            ring.stop(rcB != SNPGPU_OK);
+            ns_reading += ring.ns_reading.load();
+            ns_waiting += ring.ns_waiting.load();
             if (rcB) { rc = rcB; goto done; }
         }
         while (harvested < file_of.size()) { rc = harvest(harvested++); if (rc) goto done; }
     }
 done:
-#undef VS_TRY
     {   // every copy has landed before the caller looks at resident memory (or reuses a slot)
         hipError_t e1 = hipStreamSynchronize(p->copy_stream), e2 = hipStreamSynchronize(p->copy_stream2);
         if (rc) (void)hipStreamSynchronize(st);
@@ -2004,9 +1964,7 @@ int vcf_stream(snpgpu_ctx *ctx, const char *const *paths, uint32_t n_files, size
         for (uint32_t f = 0; f < n_files; ++f) {
             Source &s = src[f];
             s.path = paths[f];
-            struct stat stt;
-            if (!s.path || stat(s.path, &stt) != 0 || !S_ISREG(stt.st_mode)) { s.rc = SNPGPU_E_IO; s.size = 0; }
-            else s.size = (uint64_t)stt.st_size;
+            size_source(s);
             const uint64_t n = s.size;
             const uint32_t nc = n ? (uint32_t)((n + step - 1) / step) : 1;      // an empty file still takes one (empty) job
             chunks_of[f] = nc;
@@ -2021,97 +1979,62 @@ int vcf_stream(snpgpu_ctx *ctx, const char *const *paths, uint32_t n_files, size
     const uint64_t J = jobs.size();
     // everything that has to be undone lives here, and every exit after this point goes through `done`
     Opener opener;
-    Shared sh;
-    std::vector<std::thread> readers;
+    Ring ring;
     hipEvent_t ev_counted[N_DEV] = {nullptr, nullptr, nullptr};
     snpgpu_stream_pool *p = nullptr;
     uint8_t *d_buf[N_DEV] = {nullptr, nullptr, nullptr};
     void *d_extra = nullptr;
     hipStream_t st = ctx->stream;
-    uint64_t R = 1;
     int rc = SNPGPU_OK;
     bool opened = false;
-#define VC_TRY(expr)                                                                                                \
-    do {                                                                                                            \
-        hipError_t e_ = (expr);                                                                                     \
-        if (e_ != hipSuccess) { rc = snpgpu_set_error(ctx, SNPGPU_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); goto done; } \
-    } while (0)
 
     try { opener.start(&src, chunks_of); } catch (const std::exception &) { rc = snpgpu_set_error(ctx, SNPGPU_E_NOMEM, "no memory for the file opener"); goto done; }
     opened = true;
     {
-        uint32_t n_readers = snpgpu_reader_threads();
-        if (n_readers > J) n_readers = (uint32_t)J;
-        uint32_t n_staging = n_readers + 4;
-        if (n_staging > J) n_staging = (uint32_t)J;
+        uint32_t n_readers, n_staging;
+        ring_sizes(J, snpgpu_reader_threads(), 4, &n_readers, &n_staging);
         rc = pool_ensure(ctx, chunk, n_staging, 0, 0, 0, 0);
         if (rc) goto done;
         p = ctx->pool;
-        R = p->staging.size() < n_staging ? p->staging.size() : n_staging;
         const size_t buf_bytes = chunk + 256, res_bytes = up(extra_bytes, 256);
         void *ws = nullptr;
         rc = snpgpu_scratch(ctx, N_DEV * buf_bytes + res_bytes + 256, &ws);
         if (rc) goto done;
         for (uint32_t i = 0; i < N_DEV; ++i) d_buf[i] = (uint8_t *)ws + i * buf_bytes;
         d_extra = (uint8_t *)ws + N_DEV * buf_bytes;
-        VC_TRY(hipStreamSynchronize(st));                       // whatever used the scratch before is done
-        for (uint32_t i = 0; i < N_DEV; ++i) VC_TRY(hipEventCreateWithFlags(&ev_counted[i], hipEventDisableTiming));
+        STREAM_TRY(hipStreamSynchronize(st));                       // whatever used the scratch before is done
+        for (uint32_t i = 0; i < N_DEV; ++i) STREAM_TRY(hipEventCreateWithFlags(&ev_counted[i], hipEventDisableTiming));
         rc = begin(d_extra);
         if (rc) goto done;
-        sh.R = R;
-        sh.opener = &opener;
-        try {
-            sh.filled.assign(J, 0);
-            sh.job_err.assign(J, 0);
-            for (uint32_t i = 0; i < n_readers; ++i) readers.emplace_back(reader_main, ctx, &sh, &jobs, &src);
-        } catch (const std::exception &e) {
-            rc = snpgpu_set_error(ctx, SNPGPU_E_NOMEM, "cannot start the reader threads: %s", e.what());
-            goto done;
-        }
+        rc = ring.start(ctx, &jobs, &src, 0, J, n_staging, n_readers, &opener);
+        if (rc) goto done;
     }
     {
-        int64_t copies_done = 0;
         for (uint64_t j = 0; j < J; ++j) {
             const Job &jb = jobs[j];
             Source &s = src[jb.file];
-            for (;;) {                                          // wait for the piece; meanwhile hand copied-out staging buffers back to the readers
-                bool progress = false;
-                while (copies_done < (int64_t)j && hipEventQuery(p->ev_copy[copies_done % R]) != hipErrorNotReady) { ++copies_done; progress = true; }
-                std::unique_lock<std::mutex> lk(sh.mu);
-                if (progress) { sh.freed = copies_done; lk.unlock(); sh.cv.notify_all(); lk.lock(); }
-                if (sh.filled[j]) break;
-                sh.cv.wait_for(lk, std::chrono::microseconds(copies_done < (int64_t)j ? 20 : 2000), [&] { return sh.filled[j] != 0; });
-                if (sh.filled[j]) break;
-            }
-            if (sh.job_err[j] && s.rc == SNPGPU_OK) s.rc = SNPGPU_E_IO;
-            uint8_t *h = (uint8_t *)p->staging[j % R];
+            if (ring.wait(j) && s.rc == SNPGPU_OK) s.rc = SNPGPU_E_IO;
+            uint8_t *h = (uint8_t *)ring.staging(j);
             uint32_t len = (uint32_t)jb.len;
             if (jb.last && len && h[len - 1] != '\n') h[len++] = '\n';      // a last line without a terminator is a line
             const uint32_t b = (uint32_t)(j % N_DEV);
-            hipStream_t cs = (j & 1) ? p->copy_stream2 : p->copy_stream;
-            if (j >= N_DEV) VC_TRY(hipStreamWaitEvent(cs, ev_counted[b], 0));      // the piece that was in this buffer has been counted
-            if (len) VC_TRY(hipMemcpyAsync(d_buf[b], h, len, hipMemcpyHostToDevice, cs));
-            VC_TRY(hipEventRecord(p->ev_copy[j % R], cs));
-            VC_TRY(hipStreamWaitEvent(st, p->ev_copy[j % R], 0));
+            hipStream_t cs = ring.copy_stream(j);
+            if (j >= N_DEV) STREAM_TRY(hipStreamWaitEvent(cs, ev_counted[b], 0));      // the piece that was in this buffer has been counted
+            if (len) STREAM_TRY(hipMemcpyAsync(d_buf[b], h, len, hipMemcpyHostToDevice, cs));
+            STREAM_TRY(hipEventRecord(ring.copy_event(j), cs));
+            STREAM_TRY(hipStreamWaitEvent(st, ring.copy_event(j), 0));
             if (s.rc == SNPGPU_OK && s.size) {
                 rc = piece(d_buf[b], len, jb.first ? 0u : (uint32_t)SNPGPU_VCF_LOOK, jb);
                 if (rc) goto done;
             }
-            VC_TRY(hipEventRecord(ev_counted[b], st));
+            STREAM_TRY(hipEventRecord(ev_counted[b], st));
         }
         rc = end(d_extra);
         if (rc) goto done;
     }
 done:
-#undef VC_TRY
     if (opened) {
-        if (rc) opener.cancel();
-        {
-            std::lock_guard<std::mutex> lk(sh.mu);
-            if (rc) { sh.abort = true; sh.next.store(J); }
-        }
-        sh.cv.notify_all();
-        for (auto &t : readers) t.join();
+        ring.stop(rc != SNPGPU_OK);
         if (rc && p) { (void)hipStreamSynchronize(p->copy_stream); (void)hipStreamSynchronize(p->copy_stream2); (void)hipStreamSynchronize(st); }
         opener.finish();
         for (auto &s2 : src) if (s2.fd >= 0) { close(s2.fd); s2.fd = -1; }
@@ -2236,8 +2159,6 @@ struct MergeBuffers {                // everything merge_vcf_files allocates on 
         return e;
     }
 };
-
-double seconds_since(const std::chrono::steady_clock::time_point &t0) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); }
 
 constexpr uint32_t MERGE_UNUSUAL_CAP = 1u << 16;            // lines outside the kernel's grammar the host takes in one merge
 
@@ -2453,7 +2374,7 @@ int merge_vcf_files(snpgpu_ctx *ctx, const char *const *paths, uint32_t n_files,
     constexpr uint32_t UNUSUAL_CAP = MERGE_UNUSUAL_CAP;
     HIP_TRY(ctx, snpgpu_enter(ctx));
     hipStream_t st = ctx->stream;
-    auto t0 = std::chrono::steady_clock::now();
+    double t0 = now_s();
     MergeInput own_input;
     if (!given) {
         const int hrc = merge_read_input(ctx, paths, n_files, stats, own_input);
@@ -2513,8 +2434,8 @@ int merge_vcf_files(snpgpu_ctx *ctx, const char *const *paths, uint32_t n_files,
         n_cells += extra.size();
     }
     stats->cells = n_cells;
-    stats->seconds_parse = seconds_since(t0);
-    t0 = std::chrono::steady_clock::now();
+    stats->seconds_parse = now_s() - t0;
+    t0 = now_s();
 
     // contigs in order of first appearance over the columns, then the site union
     std::vector<std::string> contigs;
@@ -2612,8 +2533,8 @@ int merge_vcf_files(snpgpu_ctx *ctx, const char *const *paths, uint32_t n_files,
     stats->rounds = (uint32_t)(rounds.size() < 0xFFFFFFFFu ? rounds.size() : 0xFFFFFFFFu);
     uint8_t *d_out = nullptr;
     if (n_sites) HIP_TRY(ctx, mem.get(&d_out, buf_bytes + 16));
-    stats->seconds_merge = seconds_since(t0);
-    t0 = std::chrono::steady_clock::now();
+    stats->seconds_merge = now_s() - t0;
+    t0 = now_s();
 
     // the file: each round's text comes back in pieces through the staging ring, writer threads pwrite each piece at its place
     // (the time of the rounds' text kernels is in seconds_write: they run between the copies)
@@ -2647,7 +2568,7 @@ int merge_vcf_files(snpgpu_ctx *ctx, const char *const *paths, uint32_t n_files,
     if (rc) return rc;
     if (!io_ok) return snpgpu_set_error(ctx, SNPGPU_E_IO, "cannot write %s", out_path);
     stats->bytes = head.size() + out_bytes;
-    stats->seconds_write = seconds_since(t0);
+    stats->seconds_write = now_s() - t0;
     return SNPGPU_OK;
 }
 
@@ -2766,7 +2687,7 @@ struct MergeTemp {
 int merge_vcf_files_bounded(snpgpu_ctx *ctx, const char *const *paths, uint32_t n_files, const char *out_path, const char *own_lines, uint32_t own_len,
                             uint64_t out_cap, uint64_t budget, const MergeInput &in, snpgpu_merge_stats *stats, snpgpu_merge_passes *passes) {
     hipStream_t st = ctx->stream;
-    auto t0 = std::chrono::steady_clock::now();
+    double t0 = now_s();
     const uint32_t n_filt = (uint32_t)in.filt_off.size() - 1;
     MergePlan pl;
     auto no_memory = [&](const MergePlan &q) {
@@ -2979,8 +2900,8 @@ int merge_vcf_files_bounded(snpgpu_ctx *ctx, const char *const *paths, uint32_t 
     if (merge_plan(n_files, n_sites, in.total_bytes, budget, out_cap, &pl)) return no_memory(pl);
     *passes = pl.p;
     const uint32_t per_round = (uint32_t)pl.p.sites_per_round;
-    stats->seconds_parse = seconds_since(t0);
-    t0 = std::chrono::steady_clock::now();
+    stats->seconds_parse = now_s() - t0;
+    t0 = now_s();
 
     // ---- the site rounds ----
     const std::string head = merge_head_text(in, contigs, own_lines, own_len);
@@ -3006,12 +2927,12 @@ int merge_vcf_files_bounded(snpgpu_ctx *ctx, const char *const *paths, uint32_t 
         HIP_TRY(ctx, mem.get(&d_out, out_bytes + 16));
         if (!extra.empty()) HIP_TRY(ctx, mem.get(&d_extra, MERGE_EXTRA_BUF * sizeof(snpgpu_merge_cell)));
     }
-    stats->seconds_merge = seconds_since(t0);
+    stats->seconds_merge = now_s() - t0;
     size_t next_extra = 0;
     std::vector<uint64_t> row_end;
     stats->writer_threads = 1;
     for (uint32_t lo = 0; lo < n_sites && io_ok; lo += per_round) {
-        t0 = std::chrono::steady_clock::now();
+        t0 = now_s();
         const uint32_t hi = n_sites - lo < per_round ? n_sites : lo + per_round, n_local = hi - lo;
         HIP_TRY(ctx, hipMemsetAsync(d_table, 0, 4ull * n_local * n_files, st));
         HIP_TRY(ctx, hipMemsetAsync(d_ctl, 0, 64, st));
@@ -3037,8 +2958,8 @@ int merge_vcf_files_bounded(snpgpu_ctx *ctx, const char *const *paths, uint32_t 
             HIP_TRY(ctx, hipStreamSynchronize(st));
             next_extra += n;
         }
-        stats->seconds_parse += seconds_since(t0);
-        t0 = std::chrono::steady_clock::now();
+        stats->seconds_parse += now_s() - t0;
+        t0 = now_s();
         // rows: the lengths and offsets of the round's sites, and the errors only the records show
         rc = snpgpu_enqueue_merge_rows(ctx, 0, d_cells, d_table, n_files, d_sites + lo, n_local, 0, n_local, 0, d_names, d_name_off, d_filt, d_filt_off, d_row_len, d_row_end,
                                        d_scan, nullptr, d_ctl);
@@ -3077,8 +2998,8 @@ int merge_vcf_files_bounded(snpgpu_ctx *ctx, const char *const *paths, uint32_t 
             out_bytes = longest;
         }
         n_rounds += rounds.size();
-        stats->seconds_merge += seconds_since(t0);
-        t0 = std::chrono::steady_clock::now();
+        stats->seconds_merge += now_s() - t0;
+        t0 = now_s();
         {
             MergeWriter wr(ctx, tmp_file.fd);
             uint32_t n_writers = 1;
@@ -3097,7 +3018,7 @@ int merge_vcf_files_bounded(snpgpu_ctx *ctx, const char *const *paths, uint32_t 
             if (wr.herr != hipSuccess) return snpgpu_set_error(ctx, SNPGPU_E_HIP, "copying the merged text back failed: %s", hipGetErrorString(wr.herr));
         }
         text_bytes += row_end[n_local - 1];
-        stats->seconds_write += seconds_since(t0);
+        stats->seconds_write += now_s() - t0;
     }
     stats->rounds = (uint32_t)(n_rounds < 0xFFFFFFFFu ? n_rounds : 0xFFFFFFFFu);
     if (!io_ok || !tmp_file.commit(out_path)) return snpgpu_set_error(ctx, SNPGPU_E_IO, "cannot write %s", out_path);
@@ -3131,6 +3052,7 @@ int merge_vcf_files_planned(snpgpu_ctx *ctx, const char *const *paths, uint32_t 
     return merge_vcf_files_bounded(ctx, paths, n_files, out_path, own_lines, own_len, out_cap, budget, in, stats, passes);
 }
 
+#undef STREAM_TRY
 }  // namespace
 
 extern "C" {
