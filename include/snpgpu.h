@@ -769,6 +769,50 @@ int  snpgpu_write_mst_tsv(const char *path, const char *ids, const uint64_t *id_
 int  snpgpu_write_dendrogram_newick(const char *path, const char *ids, const uint64_t *id_off, uint32_t n, const uint32_t *u,
                                     const uint32_t *v, const int32_t *dist, uint32_t n_edges);
 
+/* ---- the differing sites of pairs (csrc/pair_sites.hip) -----------------------------------------------------------------
+ * Additive entries of ABI 7, like the ones above: by which columns two samples differ.  Column s of pair (a, b) differs iff
+ * both bytes, after upper-casing, are in {A,C,G,T} and are not equal (utils.py:1135-1165, what the distance kernel counts), so
+ * pair (a, b) has matrix[a][b] entries.  A pair's entries come in ascending column order, the pairs in the order given.
+ *
+ * snpgpu_pair_sites_dev: d_packed is the packed matrix of snpgpu_pack_matrix_dev (rows of snpgpu_packed_row_bytes(n_sites)
+ * bytes, 16-byte aligned), d_a / d_b device lists of n_pairs row indices: any order, duplicates allowed, a == b gives no
+ * entries.  d_pair_off[n_pairs + 1] receives the offsets, d_site[] the 0-based columns, d_bases[] one byte per entry: the low
+ * nibble is the first sample (bits 0-1 the base A0 C1 G2 T3, bit 2 lower case), the high nibble the second.  No atomic decides
+ * a position: the same input gives the same bytes.  The capacity protocol of snpgpu_close_pairs_dev: *out_n (host) is always
+ * set; when it exceeds `capacity` nothing else is written; capacity 0 only counts; the call waits for the stream once, for the
+ * count.  SNPGPU_E_ARG, with *out_n 0 and nothing written, when a pair names a row >= n_rows or the entries of the call reach 2^32. */
+int  snpgpu_pair_sites_dev(snpgpu_ctx *ctx, const void *d_packed, uint32_t n_rows, uint32_t n_sites, const uint32_t *d_a,
+                           const uint32_t *d_b, uint64_t n_pairs, uint64_t capacity, uint64_t *d_pair_off, uint32_t *d_site,
+                           uint8_t *d_bases, uint64_t *out_n);
+/* Host form: uploads and packs the symbols (as snpgpu_distance), uploads the lists, calls the above and copies the three
+ * arrays back.  The indices are checked on the host. */
+int  snpgpu_pair_sites(snpgpu_ctx *ctx, const uint8_t *symbols, uint32_t n_rows, uint32_t n_sites, const uint32_t *a,
+                       const uint32_t *b, uint64_t n_pairs, uint64_t capacity, uint64_t *out_pair_off, uint32_t *out_site,
+                       uint8_t *out_bases, uint64_t *out_n);
+/* Everything the distance step hands out from ONE upload, pack and computation of the matrix: snpgpu_mst_close_pairs with the
+ * tree optional as well (want_tree 0: out_u / out_v / out_dist are not touched) and, with keep_packed not 0, the packed matrix
+ * left in the context — where snpgpu_pair_sites_kept, the host form above without symbols, finds it for any number of pair
+ * lists (the tree's edges, the close pairs: their entries are the sum of the distances the first call returned, so the caller
+ * knows the capacity) until snpgpu_packed_drop, the next keeping call or the end of the context frees it. */
+int  snpgpu_distance_outputs(snpgpu_ctx *ctx, const uint8_t *symbols, uint32_t n_rows, uint32_t n_sites, int want_tree,
+                             uint32_t *out_u, uint32_t *out_v, int32_t *out_dist, int32_t *out_matrix, int want_pairs,
+                             int32_t threshold, uint64_t capacity, uint64_t *out_row_off, uint32_t *out_col,
+                             int32_t *out_pair_dist, uint64_t *out_n, int keep_packed);
+int  snpgpu_pair_sites_kept(snpgpu_ctx *ctx, const uint32_t *a, const uint32_t *b, uint64_t n_pairs, uint64_t capacity,
+                            uint64_t *out_pair_off, uint32_t *out_site, uint8_t *out_bases, uint64_t *out_n);
+int  snpgpu_packed_drop(snpgpu_ctx *ctx);
+/* The text (host code, the thread scheme and CPU budget of snpgpu_write_distance_tsv; the threads take equal shares of the
+ * entries, not of the pairs): one row per entry of HOST arrays as the calls above fill them.  Without a site table (the last four
+ * arguments null): "Seq1\tSeq2\tSite\tBase1\tBase2\n", then "id_a\tid_b\t<1-based column>\t<letter>\t<letter>\n".  With one —
+ * chrom_names / chrom_off the contig names and their offsets, chrom_of_site[] / pos_of_site[] the contig and position of every
+ * column of the matrix (the caller's: no `site` may lie outside them) —: "Seq1\tSeq2\tChrom\tPos\tBase1\tBase2\n" and the
+ * contig name and position in place of the column.  Letters keep their case; a pair without entries has no row.
+ * SNPGPU_E_ARG for an index >= n or offsets that do not rise from 0; SNPGPU_E_IO when the file cannot be created or written. */
+int  snpgpu_write_pair_sites_tsv(const char *path, const char *ids, const uint64_t *id_off, uint32_t n, const uint32_t *a,
+                                 const uint32_t *b, uint64_t n_pairs, const uint64_t *pair_off, const uint32_t *site,
+                                 const uint8_t *bases, const char *chrom_names, const uint64_t *chrom_off,
+                                 const uint32_t *chrom_of_site, const uint64_t *pos_of_site);
+
 /* ---- the exchange steps of the sharded path: RCCL over xGMI, one process per GPU ------------------------
  * The reference fans out one process per sample (run.py:704-718, `run_array` with `max_processes`) over a shared file system
  * and has no exchange step; sharded over GPUs the hot path has three: C1, the all-gather of the per-rank SNP site keys

@@ -213,6 +213,11 @@ def parse_argument_list(argv):
     sub.add_argument("--amdClusterThresholds", dest="amdClusterThresholds", type=int, nargs="+", default=None, metavar="INT", help="Extension of this build: the SNP thresholds of the --amdClusters file; sorted and made unique.")
     sub.add_argument("--amdMst", dest="amdMstFile", type=str, default=None, metavar="FILE", help="Extension of this build: output file with the n - 1 edges of the minimum spanning tree of the samples (the tree Kruskal's algorithm builds under the edge order distance, first sample, second sample), one Seq1 / Seq2 / Distance row per edge in that order; built on the device, the full matrix is not written.")
     sub.add_argument("--amdDendrogram", dest="amdDendrogramFile", type=str, default=None, metavar="FILE", help="Extension of this build: output file with the single-linkage dendrogram of the samples as one Newick line: groups join at height distance / 2, so the path between two leaves through their join is their single-linkage distance.")
+    sub.add_argument("--amdClosePairSites", dest="amdClosePairSitesFile", type=str, default=None, metavar="FILE", help="Extension of this build: output file with the sites at which the two samples of every pair i < j within --amdMaxPairDistance differ, one Seq1 / Seq2 / Site / Base1 / Base2 row per site in ascending column order, the pairs in the pairwise file's order; a pair has as many rows as its distance.  Found on the device from the packed matrix; --amdClosePairs itself is not required and the full matrix is not written.")
+    sub.add_argument("--amdMstSites", dest="amdMstSitesFile", type=str, default=None, metavar="FILE", help="Extension of this build: output file with the sites at which the two samples of every edge of the minimum spanning tree differ, in the order of the --amdMst file; rows as in --amdClosePairSites.")
+    sub.add_argument("--amdPairSitesPairs", dest="amdPairSitesPairsFile", type=str, default=None, metavar="FILE", help="Extension of this build: input file with two tab-separated sample ids per line (further columns and a first line Seq1 / Seq2 are ignored); the sites at which each of these pairs differs go to --amdPairSitesOut.")
+    sub.add_argument("--amdPairSitesOut", dest="amdPairSitesOutFile", type=str, default=None, metavar="FILE", help="Extension of this build: output file with the differing sites of the pairs of --amdPairSitesPairs, in that file's order; rows as in --amdClosePairSites.")
+    sub.add_argument("--amdSnpList", dest="amdSnpListFile", type=str, default=None, metavar="FILE", help="Extension of this build: the snplist file of the snp matrix, whose k-th line names column k; the site files then carry Chrom and Pos in place of the column number Site.")
     _common(sub)
     sub.set_defaults(func=distance.calculate_snp_distances, excepthook=utils.handle_global_exception)
 

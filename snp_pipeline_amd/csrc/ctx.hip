@@ -118,6 +118,7 @@ void snpgpu_ctx_destroy(snpgpu_ctx *ctx) {
     snpgpu_comm_release(ctx);
     snpgpu_stream_pool_destroy(ctx);
     if (ctx->scratch) hipFree(ctx->scratch);
+    if (ctx->kept_packed) hipFree(ctx->kept_packed);
     if (ctx->d_spill) hipFree(ctx->d_spill);
     if (ctx->d_call_ctl) hipFree(ctx->d_call_ctl);
     for (auto &t : ctx->timed) { hipEventDestroy(t.a); hipEventDestroy(t.b); }

@@ -29,6 +29,9 @@ struct snpgpu_ctx {
     bool varscan_lds_attr = false;
     bool bgzf_lds_attr = false;
     void *comm = nullptr;               // comm.hip: the RCCL communicator of this rank (snpgpu_comm_init), or none
+    // the packed matrix snpgpu_distance_outputs left for snpgpu_pair_sites_kept (an allocation of its own), or none
+    void *kept_packed = nullptr;
+    uint32_t kept_rows = 0, kept_sites = 0;
     // positions with more than SNPGPU_MAX_SYMS symbols: [SNPGPU_SPILL_CAP] records + one counter word (allocated on first use)
     snpgpu_symbol_spill *d_spill = nullptr;
     uint32_t *d_spill_n = nullptr;

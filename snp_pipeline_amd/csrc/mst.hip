@@ -306,26 +306,35 @@ int snpgpu_mst_dev(snpgpu_ctx *ctx, const int32_t *d_matrix, uint32_t n, uint64_
     return SNPGPU_OK;
 }
 
-int snpgpu_mst_close_pairs(snpgpu_ctx *ctx, const uint8_t *symbols, uint32_t n_rows, uint32_t n_sites, uint32_t *out_u, uint32_t *out_v, int32_t *out_dist,
-                           int32_t *out_matrix, int want_pairs, int32_t threshold, uint64_t capacity, uint64_t *out_row_off, uint32_t *out_col,
-                           int32_t *out_pair_dist, uint64_t *out_n) {
+// One upload, pack and k_distance for everything the distance step hands out: the tree (want_tree), the close pairs (want_pairs),
+// the matrix (out_matrix) — and, with keep_packed, the packed matrix stays in the context for snpgpu_pair_sites_kept.
+int snpgpu_distance_outputs(snpgpu_ctx *ctx, const uint8_t *symbols, uint32_t n_rows, uint32_t n_sites, int want_tree, uint32_t *out_u, uint32_t *out_v,
+                            int32_t *out_dist, int32_t *out_matrix, int want_pairs, int32_t threshold, uint64_t capacity, uint64_t *out_row_off,
+                            uint32_t *out_col, int32_t *out_pair_dist, uint64_t *out_n, int keep_packed) {
     if (!ctx) return SNPGPU_E_ARG;
     if ((n_rows && n_sites && !symbols) || (want_pairs && !out_n)) return snpgpu_set_error(ctx, SNPGPU_E_ARG, "null mst argument");
-    if (n_rows > 1 && (!out_u || !out_v || !out_dist)) return snpgpu_set_error(ctx, SNPGPU_E_ARG, "null mst output");
+    if (want_tree && n_rows > 1 && (!out_u || !out_v || !out_dist)) return snpgpu_set_error(ctx, SNPGPU_E_ARG, "null mst output");
     HIP_TRY(ctx, snpgpu_enter(ctx));
+    if (keep_packed) {
+        const int rc_drop = snpgpu_packed_drop(ctx);
+        if (rc_drop != SNPGPU_OK) return rc_drop;
+    }
     if (want_pairs) *out_n = 0;
     if (n_rows == 0) {
         if (want_pairs && capacity && out_row_off) out_row_off[0] = 0;
         return SNPGPU_OK;
     }
     const size_t sym_bytes = (size_t)n_rows * n_sites;
-    const size_t o_pack = (sym_bytes + 255) / 256 * 256;
-    const size_t o_mat = o_pack + (snpgpu_packed_row_bytes(n_sites) * n_rows + 255) / 256 * 256;
+    const size_t o_mat = (sym_bytes + 255) / 256 * 256;
     const size_t o_edges = o_mat + ((size_t)n_rows * n_rows * 4 + 255) / 256 * 256;
     const size_t o_off = o_edges + ((size_t)n_rows * 12 + 255) / 256 * 256;
-    void *d = nullptr, *d_csr = nullptr;
+    void *d = nullptr, *d_csr = nullptr, *d_pack = nullptr;      // the packed matrix apart: it may outlive the call
     hipError_t he = hipMalloc(&d, o_off + ((size_t)n_rows + 1) * 8 + 256);
-    if (he != hipSuccess) return snpgpu_set_error(ctx, SNPGPU_E_NOMEM, "hipMalloc failed: %s", hipGetErrorString(he));
+    if (he == hipSuccess) he = hipMalloc(&d_pack, snpgpu_packed_row_bytes(n_sites) * n_rows + 256);
+    if (he != hipSuccess) {
+        (void)hipFree(d);
+        return snpgpu_set_error(ctx, SNPGPU_E_NOMEM, "hipMalloc failed: %s", hipGetErrorString(he));
+    }
     char *b = (char *)d;
     const int32_t *d_mat = (const int32_t *)(b + o_mat);
     uint32_t *d_u = (uint32_t *)(b + o_edges), *d_v = d_u + n_rows;
@@ -335,12 +344,12 @@ int snpgpu_mst_close_pairs(snpgpu_ctx *ctx, const uint8_t *symbols, uint32_t n_r
     int rc = SNPGPU_OK;
     uint32_t n_edges = 0, rounds = 0;
     if (sym_bytes) he = hipMemcpyAsync(b, symbols, sym_bytes, hipMemcpyHostToDevice, st);
-    if (he == hipSuccess && n_sites) rc = snpgpu_pack_matrix_dev(ctx, (const uint8_t *)b, n_rows, n_sites, n_sites, b + o_pack);
-    if (he == hipSuccess && rc == SNPGPU_OK) rc = snpgpu_distance_packed_dev(ctx, b + o_pack, n_rows, n_sites, 0, 1, (int32_t *)(b + o_mat));
+    if (he == hipSuccess && n_sites) rc = snpgpu_pack_matrix_dev(ctx, (const uint8_t *)b, n_rows, n_sites, n_sites, d_pack);
+    if (he == hipSuccess && rc == SNPGPU_OK) rc = snpgpu_distance_packed_dev(ctx, d_pack, n_rows, n_sites, 0, 1, (int32_t *)(b + o_mat));
     if (he == hipSuccess && rc == SNPGPU_OK && out_matrix)        // the caller writes the reference's tables too: one matrix for all
         he = hipMemcpyAsync(out_matrix, d_mat, (size_t)n_rows * n_rows * 4, hipMemcpyDeviceToHost, st);
-    if (he == hipSuccess && rc == SNPGPU_OK) rc = snpgpu_mst_dev(ctx, d_mat, n_rows, n_rows, 0, n_rows, d_u, d_v, d_dist, &n_edges, &rounds);
-    if (he == hipSuccess && rc == SNPGPU_OK && n_edges != n_rows - 1) rc = snpgpu_set_error(ctx, SNPGPU_E_HIP, "the tree of %u samples has %u edges", n_rows, n_edges);
+    if (he == hipSuccess && rc == SNPGPU_OK && want_tree) rc = snpgpu_mst_dev(ctx, d_mat, n_rows, n_rows, 0, n_rows, d_u, d_v, d_dist, &n_edges, &rounds);
+    if (he == hipSuccess && rc == SNPGPU_OK && want_tree && n_edges != n_rows - 1) rc = snpgpu_set_error(ctx, SNPGPU_E_HIP, "the tree of %u samples has %u edges", n_rows, n_edges);
     if (he == hipSuccess && rc == SNPGPU_OK && n_edges) {          // only the tree crosses the host link, never the matrix
         he = hipMemcpyAsync(out_u, d_u, (size_t)n_edges * 4, hipMemcpyDeviceToHost, st);
         if (he == hipSuccess) he = hipMemcpyAsync(out_v, d_v, (size_t)n_edges * 4, hipMemcpyDeviceToHost, st);
@@ -370,8 +379,22 @@ int snpgpu_mst_close_pairs(snpgpu_ctx *ctx, const uint8_t *symbols, uint32_t n_r
     if (he == hipSuccess) he = hs;
     (void)hipFree(d_csr);
     (void)hipFree(d);
+    if (keep_packed && he == hipSuccess && rc == SNPGPU_OK) {
+        ctx->kept_packed = d_pack;
+        ctx->kept_rows = n_rows;
+        ctx->kept_sites = n_sites;
+    } else {
+        (void)hipFree(d_pack);
+    }
     if (he != hipSuccess) return snpgpu_set_error(ctx, SNPGPU_E_HIP, "mst failed: %s", hipGetErrorString(he));
     return rc;
+}
+
+int snpgpu_mst_close_pairs(snpgpu_ctx *ctx, const uint8_t *symbols, uint32_t n_rows, uint32_t n_sites, uint32_t *out_u, uint32_t *out_v, int32_t *out_dist,
+                           int32_t *out_matrix, int want_pairs, int32_t threshold, uint64_t capacity, uint64_t *out_row_off, uint32_t *out_col,
+                           int32_t *out_pair_dist, uint64_t *out_n) {
+    return snpgpu_distance_outputs(ctx, symbols, n_rows, n_sites, 1, out_u, out_v, out_dist, out_matrix, want_pairs, threshold, capacity, out_row_off, out_col,
+                                   out_pair_dist, out_n, 0);
 }
 
 int snpgpu_mst(snpgpu_ctx *ctx, const uint8_t *symbols, uint32_t n_rows, uint32_t n_sites, uint32_t *out_u, uint32_t *out_v, int32_t *out_dist,

@@ -422,3 +422,69 @@ extern "C" int snpgpu_write_dendrogram_newick(const char *path, const char *ids,
     o.put(";\n", 2);
     return o.finish();
 }
+
+// ---- the differing sites of pairs (additive: the entries of csrc/pair_sites.hip as text) ----
+namespace {
+inline uint32_t digits_u64(uint64_t u) {
+    uint32_t k = 1;
+    while (u >= 10) { u /= 10; ++k; }
+    return k;
+}
+template <typename Sink>
+inline void put_u64(Sink &o, uint64_t u) {
+    char tmp[20];
+    int k = 20;
+    do { tmp[--k] = (char)('0' + u % 10); u /= 10; } while (u);
+    o.put(tmp + k, (size_t)(20 - k));
+}
+}  // namespace
+
+// One row per entry, pair by pair in the order given: the two ids, the column (1-based) — or, with a site table, the contig name
+// and position of the column —, and the two bases with their case.  The table is the caller's: chrom_of_site / pos_of_site hold
+// one entry per column of the matrix and every `site` lies below their length (not checked here: the writer is not told it).
+extern "C" int snpgpu_write_pair_sites_tsv(const char *path, const char *ids, const uint64_t *id_off, uint32_t n, const uint32_t *a, const uint32_t *b,
+                                           uint64_t n_pairs, const uint64_t *pair_off, const uint32_t *site, const uint8_t *bases, const char *chrom_names,
+                                           const uint64_t *chrom_off, const uint32_t *chrom_of_site, const uint64_t *pos_of_site) {
+    if (!path || (n && (!ids || !id_off)) || n_pairs >> 32 || (n_pairs && (!a || !b || !pair_off))) return SNPGPU_E_ARG;
+    const bool table = chrom_names || chrom_off || chrom_of_site || pos_of_site;
+    if (table && (!chrom_off || !chrom_of_site || !pos_of_site)) return SNPGPU_E_ARG;
+    const uint64_t n_entries = n_pairs ? pair_off[n_pairs] : 0;
+    if (n_pairs && (pair_off[0] != 0 || (n_entries && (!site || !bases)))) return SNPGPU_E_ARG;
+    for (uint64_t p = 0; p < n_pairs; ++p)
+        if (pair_off[p] > pair_off[p + 1] || a[p] >= n || b[p] >= n) return SNPGPU_E_ARG;
+    if (table && n_entries && !chrom_names) return SNPGPU_E_ARG;
+    auto len = [&](uint32_t i) { return id_off[i + 1] - id_off[i]; };
+    auto chrom_len = [&](uint32_t s) { const uint32_t c = chrom_of_site[s]; return chrom_off[c + 1] - chrom_off[c]; };
+    const uint64_t header_bytes = table ? 32 : 27;
+    auto header = [&](auto &o) {
+        if (table) o.put("Seq1\tSeq2\tChrom\tPos\tBase1\tBase2\n", 32);
+        else o.put("Seq1\tSeq2\tSite\tBase1\tBase2\n", 27);
+    };
+    auto size_rows = [&](uint32_t p0, uint32_t p1) {
+        uint64_t total = 0;
+        for (uint32_t p = p0; p < p1; ++p) {
+            const uint64_t names = len(a[p]) + len(b[p]);
+            for (uint64_t e = pair_off[p]; e < pair_off[p + 1]; ++e)
+                total += names + (table ? chrom_len(site[e]) + digits_u64(pos_of_site[site[e]]) + 8 : digits_u64((uint64_t)site[e] + 1) + 7);
+        }
+        return total;
+    };
+    auto format = [&](auto &o, uint32_t p0, uint32_t p1) {
+        for (uint32_t p = p0; p < p1 && !o.failed; ++p)
+            for (uint64_t e = pair_off[p]; e < pair_off[p + 1]; ++e) {
+                const uint32_t s = site[e];
+                o.put(ids + id_off[a[p]], (size_t)len(a[p])); o.put('\t');
+                o.put(ids + id_off[b[p]], (size_t)len(b[p])); o.put('\t');
+                if (table) {
+                    o.put(chrom_names + chrom_off[chrom_of_site[s]], (size_t)chrom_len(s)); o.put('\t');
+                    put_u64(o, pos_of_site[s]);
+                } else {
+                    put_u64(o, (uint64_t)s + 1);
+                }
+                o.put('\t'); o.put("ACGTacgt"[bases[e] & 7]);
+                o.put('\t'); o.put("ACGTacgt"[(bases[e] >> 4) & 7]);
+                o.put('\n');
+            }
+    };
+    return write_row_blocks(path, (uint32_t)n_pairs, n_entries, pair_off, header_bytes, header, size_rows, format);
+}

@@ -1170,6 +1170,78 @@ class Device(object):
                 return (u, v, dist, csr, mat) if want_matrix else (u, v, dist, csr)
             cap = int(out_n.value)
 
+    # ---- the differing sites of pairs (additive to distance.py:93-106) ---------------------------
+    def pair_sites_dev(self, d_packed, n_rows, n_sites, d_a, d_b, n_pairs, capacity=0, d_pair_off=0, d_site=0, d_bases=0):
+        """The columns at which the pairs (d_a[p], d_b[p]) of rows of a device packed matrix differ, pair by pair, ascending:
+        d_pair_off[n_pairs + 1] (uint64), d_site[] (uint32), d_bases[] (uint8: low nibble the first sample, bits 0-1 A0 C1 G2 T3,
+        bit 2 lower case; high nibble the second).  Returns the number of entries; the three device arrays are written only when
+        0 < capacity and the number fits."""
+        opt = lambda v: C.c_void_p(int(v)) if v else None     # noqa: E731
+        out_n = C.c_uint64(0)
+        self._check(self.lib.snpgpu_pair_sites_dev(self.ctx, opt(d_packed), int(n_rows), int(n_sites), opt(d_a), opt(d_b), int(n_pairs), int(capacity),
+                                                   opt(d_pair_off), opt(d_site), opt(d_bases), C.byref(out_n)))
+        return int(out_n.value)
+
+    def _pair_sites_host(self, call, a, b, expect):
+        a = np.ascontiguousarray(a, dtype=np.uint32)
+        b = np.ascontiguousarray(b, dtype=np.uint32)
+        if a.ndim != 1 or a.shape != b.shape:
+            raise ValueError("a and b hold one row index per pair")
+        m = len(a)
+        pair_off = np.zeros(m + 1, dtype=np.uint64)
+        opt = lambda x: _ptr(x) if x.size else None           # noqa: E731
+        cap = int(expect) if expect else 0                    # no room known: count, then emit
+        while True:
+            site, bases = np.zeros(max(cap, 1), dtype=np.uint32), np.zeros(max(cap, 1), dtype=np.uint8)
+            out_n = C.c_uint64(0)
+            self._check(call(opt(a), opt(b), m, cap, _ptr(pair_off), _ptr(site), _ptr(bases), C.byref(out_n)))
+            total = int(out_n.value)
+            if cap and total <= cap:
+                return pair_off, site[:total], bases[:total]
+            cap = max(total, 1)
+
+    def pair_sites(self, symbols, a, b, expect=None):
+        """symbols: (n, s) uint8 array of sequence bytes; a, b: row indices of the pairs.  Returns (pair_off uint64 [m + 1], site
+        uint32, bases uint8) as ``pair_sites_dev`` lays them out.  expect: the number of entries when the caller knows it (the sum
+        of the pairs' distances) — the first call then has room for them; without it a first call counts and a second emits."""
+        sym = np.ascontiguousarray(symbols, dtype=np.uint8)
+        n, s = sym.shape
+        return self._pair_sites_host(lambda *rest: self.lib.snpgpu_pair_sites(self.ctx, _ptr(sym) if sym.size else None, n, s, *rest), a, b, expect)
+
+    def pair_sites_kept(self, a, b, expect=None):
+        """``pair_sites`` against the packed matrix a ``distance_outputs(..., keep_packed=True)`` left in the context."""
+        return self._pair_sites_host(lambda *rest: self.lib.snpgpu_pair_sites_kept(self.ctx, *rest), a, b, expect)
+
+    def packed_drop(self):
+        self._check(self.lib.snpgpu_packed_drop(self.ctx))
+
+    def distance_outputs(self, symbols, want_tree=False, want_matrix=False, pairs_within=None, keep_packed=False):
+        """One upload, pack and computation of the matrix for everything the distance step hands out.  Returns (tree, csr, matrix):
+        the (u, v, dist) of ``mst``, the (row_off, col, dist) of ``close_pairs(symbols, pairs_within)``, the matrix of ``distance``
+        — each None when not asked for.  keep_packed leaves the packed matrix in the context for ``pair_sites_kept``."""
+        sym = np.ascontiguousarray(symbols, dtype=np.uint8)
+        n, s = sym.shape
+        m = max(n - 1, 0) if want_tree else 0
+        u, v, dist = np.zeros(m, dtype=np.uint32), np.zeros(m, dtype=np.uint32), np.zeros(m, dtype=np.int32)
+        mat = np.zeros((n, n), dtype=np.int32) if want_matrix else None
+        opt = lambda x: _ptr(x) if x is not None and x.size else None     # noqa: E731
+        row_off = np.zeros(n + 1, dtype=np.uint64)
+        want_pairs = pairs_within is not None
+        cap = max(min(n * n, max(64 * n, 1 << 26)), 1) if want_pairs else 0
+        have_matrix = False
+        while True:                                           # (the capacity protocol of close_pairs)
+            col, pd = np.zeros(max(cap, 1), dtype=np.uint32), np.zeros(max(cap, 1), dtype=np.int32)
+            out_n = C.c_uint64(0)
+            self._check(self.lib.snpgpu_distance_outputs(self.ctx, opt(sym), n, s, int(bool(want_tree)), opt(u), opt(v), opt(dist),
+                                                         opt(mat) if not have_matrix else None, int(want_pairs), int(pairs_within or 0), cap, _ptr(row_off),
+                                                         _ptr(col), _ptr(pd), C.byref(out_n), int(bool(keep_packed))))
+            have_matrix = True
+            if out_n.value <= cap:
+                break
+            cap = int(out_n.value)
+        csr = (row_off, col[:out_n.value], pd[:out_n.value]) if want_pairs else None
+        return ((u, v, dist) if want_tree else None), csr, mat
+
     # ---- filter_regions ------------------------------------------------------------------------
     def dense_windows(self, positions, seg_off, max_snps, windows):
         pos = np.ascontiguousarray(positions, dtype=np.int64)

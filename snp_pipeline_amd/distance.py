@@ -195,6 +195,98 @@ def write_dendrogram(path, ids, u, v, dist):
     _write_tree("snpgpu_write_dendrogram_newick", path, ids, u, v, dist)
 
 
+def pairs_of_csr(row_off, col, dist, threshold):
+    """The entries i < j, d <= threshold of a CSR in its order: (a, b, d) — each unordered pair of the close-pairs file once."""
+    row_off = np.asarray(row_off, dtype=np.int64)
+    col = np.asarray(col, dtype=np.uint32)
+    dist = np.asarray(dist, dtype=np.int32)
+    row = np.repeat(np.arange(len(row_off) - 1, dtype=np.uint32), np.diff(row_off))
+    keep = (row < col) & (dist <= threshold)
+    return row[keep], col[keep], dist[keep]
+
+
+def pair_sites_of_matrix(dev, file_ids, sym, lens, a, b, expect=None):
+    """The columns at which the pairs (a[p], b[p]) of samples — indices into the sorted ids, as everywhere in the distance step —
+    differ: (ids, pair_off, site, bases) as Device.pair_sites lays them out.  Pair p has as many entries as the matrix says at
+    [a[p]][b[p]]; expect is their sum when the caller has it.  Nothing but the pair lists and the entries crosses the host link
+    besides the symbols themselves."""
+    ids, rows = _sorted_rows(file_ids, sym, lens)
+    if rows is None:
+        rows = np.zeros((0, 0), dtype=np.uint8)
+    return (ids,) + tuple(dev.pair_sites(rows, a, b, expect=expect))
+
+
+def site_table(snp_list):
+    """[(chrom, pos)] per column (utils.read_snp_position_list) as the arrays the writer takes."""
+    names, index = [], {}
+    chrom_of = np.zeros(len(snp_list), dtype=np.uint32)
+    pos_of = np.zeros(len(snp_list), dtype=np.uint64)
+    for k, (chrom, pos) in enumerate(snp_list):
+        if chrom not in index:
+            index[chrom] = len(names)
+            names.append(chrom.encode("utf-8"))
+        if pos < 0:
+            raise ValueError("negative position %d of %s" % (pos, chrom))
+        chrom_of[k] = index[chrom]
+        pos_of[k] = pos
+    off = np.zeros(len(names) + 1, dtype=np.uint64)
+    np.cumsum([len(x) for x in names], out=off[1:])
+    return b"".join(names), off, chrom_of, pos_of
+
+
+def write_pair_sites(path, ids, a, b, pair_off, site, bases, snp_list=None):
+    """One row per differing site of every pair, in the order given (csrc/tsv_out.hip): "id\tid\tcolumn\tbase\tbase" with
+    1-based columns, or — snp_list: the (chrom, pos) of every column — "id\tid\tchrom\tpos\tbase\tbase"."""
+    from . import _lib as L
+    blob, off = _id_table(ids)
+    a = np.ascontiguousarray(a, dtype=np.uint32)
+    b = np.ascontiguousarray(b, dtype=np.uint32)
+    po = np.ascontiguousarray(pair_off, dtype=np.uint64)
+    st = np.ascontiguousarray(site, dtype=np.uint32)
+    bs = np.ascontiguousarray(bases, dtype=np.uint8)
+    if len(a) != len(b) or len(po) != len(a) + 1 or len(st) != len(bs) or int(po[-1]) != len(st):
+        raise ValueError("pair_off holds one offset per pair and one more, site and bases one entry per offset")
+    table = (None, None, None, None)
+    keep = None
+    if snp_list is not None:
+        if len(st) and int(st.max()) >= len(snp_list):
+            raise ValueError("a site lies beyond the %d columns of the site list" % len(snp_list))
+        keep = site_table(snp_list)
+        table = (keep[0], keep[1].ctypes.data, keep[2].ctypes.data if len(keep[2]) else None, keep[3].ctypes.data if len(keep[3]) else None)
+        if table[2] is None:                                   # a list without columns: the writer still wants to see a table
+            keep = keep + (np.zeros(1, dtype=np.uint32), np.zeros(1, dtype=np.uint64))
+            table = (keep[0], keep[1].ctypes.data, keep[4].ctypes.data, keep[5].ctypes.data)
+    opt = lambda x: x.ctypes.data if len(x) else None          # noqa: E731
+    rc = L.load().snpgpu_write_pair_sites_tsv(path.encode(), blob, off.ctypes.data, len(ids), opt(a), opt(b), len(a), po.ctypes.data, opt(st), opt(bs), *table)
+    if rc == L.E_IO:
+        raise IOError("cannot write %s" % path)
+    if rc == L.E_ARG:
+        raise ValueError("a pair names a sample outside the %d ids, or the offsets do not rise from 0" % len(ids))
+    if rc != 0:
+        raise RuntimeError("snpgpu_write_pair_sites_tsv failed (%d)" % rc)
+
+
+def read_pair_list(path, ids):
+    """The pairs of a user's two-column TSV of ids as indices into ids: (a, b).  Further columns are ignored and so is a first
+    line "Seq1\tSeq2...", so a close-pairs or tree file of this step can be handed back as it is.  An id the matrix does not
+    hold is a global error that names it."""
+    index = {name: k for k, name in enumerate(ids)}
+    a, b = [], []
+    with open(path, "r") as f:
+        for number, line in enumerate(f):
+            fields = line.rstrip("\r\n").split("\t")
+            if not line.strip() or (number == 0 and fields[:2] == ["Seq1", "Seq2"]):
+                continue
+            if len(fields) < 2:
+                utils.global_error("Error: line %d of %s does not hold two ids." % (number + 1, path))
+            for name in fields[:2]:
+                if name not in index:
+                    utils.global_error("Error: the id %s of %s is not in the snp matrix." % (name, path))
+            a.append(index[fields[0]])
+            b.append(index[fields[1]])
+    return np.asarray(a, dtype=np.uint32), np.asarray(b, dtype=np.uint32)
+
+
 def _write_tsv(path, layout, ids, mat):
     """distance.py:100-114 through the library's host formatter (csrc/tsv_out.hip): at 10 000 samples the pairwise file has
     10^8 lines, ~35 s of Python string formatting for 38 ms of kernel."""
@@ -234,25 +326,43 @@ def calculate_snp_distances(args):
     thresholds = list(getattr(args, "amdClusterThresholds", None) or [])
     mst_file = getattr(args, "amdMstFile", None)
     dendrogram_file = getattr(args, "amdDendrogramFile", None)
+    close_sites_file = getattr(args, "amdClosePairSitesFile", None)
+    mst_sites_file = getattr(args, "amdMstSitesFile", None)
+    user_pairs_file = getattr(args, "amdPairSitesPairsFile", None)
+    user_sites_file = getattr(args, "amdPairSitesOutFile", None)
+    snp_list_file = getattr(args, "amdSnpListFile", None)
     if utils.verify_existing_input_files("SNP matrix file", [input_file]) > 0:
         utils.global_error("Error: cannot calculate sequence distances without the snp matrix file.")
     if close_file and max_pair_distance is None:
         utils.global_error("Error: --amdClosePairs needs --amdMaxPairDistance.")
+    if close_sites_file and max_pair_distance is None:
+        utils.global_error("Error: --amdClosePairSites needs --amdMaxPairDistance.")
+    if bool(user_pairs_file) != bool(user_sites_file):
+        utils.global_error("Error: --amdPairSitesPairs and --amdPairSitesOut go together.")
+    if user_pairs_file and utils.verify_existing_input_files("pair list file", [user_pairs_file]) > 0:
+        utils.global_error("Error: cannot list the differing sites without the pair list file.")
+    if snp_list_file and utils.verify_existing_input_files("snplist file", [snp_list_file]) > 0:
+        utils.global_error("Error: cannot name the differing sites without the snplist file.")
     if clusters_file and not thresholds:
         utils.global_error("Error: --amdClusters needs at least one threshold in --amdClusterThresholds.")
     if (max_pair_distance is not None and max_pair_distance < 0) or any(t < 0 for t in thresholds):
         utils.global_error("Error: a distance threshold cannot be negative.")
-    if not pairwise_file and not matrix_file and not close_file and not clusters_file and not mst_file and not dendrogram_file:
+    outputs = [f for f in (pairwise_file, matrix_file, close_file, clusters_file, mst_file, dendrogram_file, close_sites_file, mst_sites_file, user_sites_file) if f]
+    if not outputs:
         utils.global_error("Error: no output file specified.")
 
-    outputs = [f for f in (pairwise_file, matrix_file, close_file, clusters_file, mst_file, dendrogram_file) if f]
-    if not (args.forceFlag or any(utils.target_needs_rebuild([input_file], f) for f in outputs)):
+    sources = [input_file] + [f for f in (user_pairs_file, snp_list_file) if f and (close_sites_file or mst_sites_file or user_sites_file)]
+    if not (args.forceFlag or any(utils.target_needs_rebuild(sources, f) for f in outputs)):
         utils.verbose_print("Distance files have already been freshly built.  Use the -f option to force a rebuild.")
         return
 
     file_ids, sym, lens = snp_matrix.load_matrix(input_file)
     utils.verbose_print("# %s %s" % (utils.timestamp(), "Calculating all pairwise distances"))
     from .device import default_device
+    if close_sites_file or mst_sites_file or user_sites_file:
+        _distances_with_sites(default_device, file_ids, sym, lens, snp_list_file, pairwise_file, matrix_file, close_file, max_pair_distance, clusters_file, thresholds,
+                              mst_file, dendrogram_file, close_sites_file, mst_sites_file, user_pairs_file, user_sites_file)
+        return
     dev = default_device()
     mat = None
     tree = None
@@ -285,3 +395,63 @@ def calculate_snp_distances(args):
         write_mst(mst_file, ids, *tree)
     if dendrogram_file:
         write_dendrogram(dendrogram_file, ids, *tree)
+
+
+def _distances_with_sites(device_of, file_ids, sym, lens, snp_list_file, pairwise_file, matrix_file, close_file, max_pair_distance, clusters_file, thresholds,
+                          mst_file, dendrogram_file, close_sites_file, mst_sites_file, user_pairs_file, user_sites_file):
+    """calculate_snp_distances when the differing sites of some pairs are asked for: the symbols are uploaded and packed once; the
+    matrix is computed once, and only when a tree, a threshold or a table needs it; the packed matrix stays on the device until
+    every pair list has been answered from it.  The n x n matrix comes to the host for -p / -m alone."""
+    ids, rows = _sorted_rows(file_ids, sym, lens)
+    if rows is None:
+        rows = np.zeros((0, 0), dtype=np.uint8)
+    n, columns = rows.shape
+    snp_list = None
+    if snp_list_file:
+        snp_list = utils.read_snp_position_list(snp_list_file)
+        if len(snp_list) != columns:
+            utils.global_error("Error: %s lists %d sites, the snp matrix has %d columns." % (snp_list_file, len(snp_list), columns))
+    user_pairs = read_pair_list(user_pairs_file, ids) if user_sites_file else None
+    dev = device_of()                                          # (the inputs have been checked: only now is a device needed)
+    want_tree = bool(mst_file or dendrogram_file or mst_sites_file)
+    want_matrix = bool(pairwise_file or matrix_file)
+    within = ([max_pair_distance] if (close_file or close_sites_file) else []) + (thresholds if clusters_file else [])
+    widest = max(within) if within else None
+    tree = csr = mat = None
+    kept = False
+    if n and (want_tree or want_matrix or widest is not None):
+        tree, csr, mat = dev.distance_outputs(rows, want_tree=want_tree, want_matrix=want_matrix, pairs_within=widest, keep_packed=True)
+        kept = True
+    elif n == 0:
+        empty = np.zeros(0, dtype=np.uint32)
+        tree, csr, mat = (empty, empty, np.zeros(0, dtype=np.int32)), (np.zeros(1, dtype=np.uint64), empty, np.zeros(0, dtype=np.int32)), np.zeros((0, 0), dtype=np.int32)
+
+    def sites_of(a, b, expect):
+        if n == 0 or len(a) == 0:
+            return np.zeros(len(a) + 1, dtype=np.uint64), np.zeros(0, dtype=np.uint32), np.zeros(0, dtype=np.uint8)
+        return dev.pair_sites_kept(a, b, expect=expect) if kept else dev.pair_sites(rows, a, b, expect=expect)
+
+    try:
+        if pairwise_file:
+            write_pairwise(pairwise_file, ids, mat)
+        if matrix_file:
+            write_matrix(matrix_file, ids, mat)
+        if close_file or clusters_file:
+            write_pairs_and_clusters(dev, ids, csr[0], csr[1], csr[2], close_file, max_pair_distance, clusters_file, thresholds)
+        if mst_file:
+            write_mst(mst_file, ids, *tree)
+        if dendrogram_file:
+            write_dendrogram(dendrogram_file, ids, *tree)
+        if close_sites_file:
+            a, b, d = pairs_of_csr(csr[0], csr[1], csr[2], max_pair_distance)
+            write_pair_sites(close_sites_file, ids, a, b, *sites_of(a, b, int(d.sum(dtype=np.int64))), snp_list=snp_list)
+        if mst_sites_file:
+            u, v, d = tree
+            write_pair_sites(mst_sites_file, ids, u, v, *sites_of(u, v, int(np.asarray(d).sum(dtype=np.int64))), snp_list=snp_list)
+        if user_sites_file:
+            a, b = user_pairs
+            expect = int(mat[a.astype(np.int64), b.astype(np.int64)].sum(dtype=np.int64)) if (mat is not None and len(a)) else None
+            write_pair_sites(user_sites_file, ids, a, b, *sites_of(a, b, expect), snp_list=snp_list)
+    finally:
+        if kept:
+            dev.packed_drop()

@@ -238,6 +238,14 @@ class _Job(object):
         if self.mst:
             self.outputs.update(mst=os.path.join(work_dir, "snp_mst.tsv"), mst_p=os.path.join(work_dir, "snp_mst_preserved.tsv"),
                                 dendrogram=os.path.join(work_dir, "snp_dendrogram.nwk"), dendrogram_p=os.path.join(work_dir, "snp_dendrogram_preserved.nwk"))
+        # --pairSites (additive to the distance step): the sites at which the close pairs / the tree's edges differ
+        self.pair_sites = bool(getattr(args, "pairSites", False))
+        if self.pair_sites and self.close_pairs is None and not self.mst:
+            utils.global_error("Error: --pairSites needs --closePairs or --mst.")
+        if self.pair_sites and self.close_pairs is not None:
+            self.outputs.update(close_sites=os.path.join(work_dir, "snp_close_pair_sites.tsv"), close_sites_p=os.path.join(work_dir, "snp_close_pair_sites_preserved.tsv"))
+        if self.pair_sites and self.mst:
+            self.outputs.update(mst_sites=os.path.join(work_dir, "snp_mst_sites.tsv"), mst_sites_p=os.path.join(work_dir, "snp_mst_sites_preserved.tsv"))
         self.filtered1, self.filtered2 = dirs_file + ".OrigVCF.filtered", dirs_file + ".PresVCF.filtered"
 
         self.samples = [_Sample(i, d, args.pileupName) for i, d in enumerate(self.sorted_dirs)]
@@ -1220,6 +1228,26 @@ def mst_over_ranks(torch, dev, comm, bands, dmat, band, n):
     return dmod.mst_of_edges(n, *(np.concatenate([p[k] for p in parts]) for k in range(3)))
 
 
+def _pair_sites_of_packed(torch, dev, packed, n, n_sites, a, b, expect):
+    """The differing sites of the pairs (a[p], b[p]) of rows of a device packed matrix (a torch tensor), found there: (pair_off,
+    site, bases) as host arrays.  expect: the sum of the pairs' distances — room for the first call; a mismatch costs a second."""
+    m = len(a)
+    if m == 0 or n == 0:
+        return np.zeros(m + 1, dtype=np.uint64), np.zeros(0, dtype=np.uint32), np.zeros(0, dtype=np.uint8)
+    d_a = torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint32).view(np.int32)).cuda()
+    d_b = torch.from_numpy(np.ascontiguousarray(b, dtype=np.uint32).view(np.int32)).cuda()
+    pair_off = torch.zeros(m + 1, dtype=torch.int64, device="cuda")
+    capacity = max(int(expect), 1)
+    while True:
+        site = torch.zeros(capacity, dtype=torch.int32, device="cuda")
+        bases = torch.zeros(capacity, dtype=torch.uint8, device="cuda")
+        total = dev.pair_sites_dev(packed.data_ptr(), n, n_sites, d_a.data_ptr(), d_b.data_ptr(), m, capacity, pair_off.data_ptr(), site.data_ptr(), bases.data_ptr())
+        if total <= capacity:
+            break
+        capacity = total
+    return pair_off.cpu().numpy().view(np.uint64), site[:total].cpu().numpy().view(np.uint32), bases[:total].cpu().numpy()
+
+
 def stage_matrices_and_distances(job):
     """Collectives interleaved with file output; the output runs under ``job.guard`` so that a rank whose disk is full still takes
     part in every collective and the failure surfaces at the agreement after the stage."""
@@ -1309,6 +1337,20 @@ def stage_matrices_and_distances(job):
                 sfx = "" if flow == 1 else "_p"
                 dmod.write_mst(outputs["mst" + sfx], ids, *tree)
                 dmod.write_dendrogram(outputs["dendrogram" + sfx], ids, *tree)
+        with job.guard() as go:
+            # every rank holds packed_sorted after the all-gather: rank 0 asks it for the sites behind the gathered pairs and edges
+            if go and rank == 0 and job.pair_sites:
+                sfx = "" if flow == 1 else "_p"
+                snp_list = utils.read_snp_position_list(outputs["snplist" + sfx])
+                if len(snp_list) != Sx:
+                    raise RuntimeError("%s lists %d sites, the matrix has %d columns" % (outputs["snplist" + sfx], len(snp_list), Sx))
+                if job.close_pairs is not None:
+                    a, b, d = dmod.pairs_of_csr(csr[0], csr[1], csr[2], job.close_pairs)
+                    got = _pair_sites_of_packed(torch, dev, packed_sorted, n, Sx, a, b, int(d.sum(dtype=np.int64)))
+                    dmod.write_pair_sites(outputs["close_sites" + sfx], ids, a, b, *got, snp_list=snp_list)
+                if tree is not None:
+                    got = _pair_sites_of_packed(torch, dev, packed_sorted, n, Sx, tree[0], tree[1], int(np.asarray(tree[2]).sum(dtype=np.int64)))
+                    dmod.write_pair_sites(outputs["mst_sites" + sfx], ids, tree[0], tree[1], *got, snp_list=snp_list)
         with job.guard() as go:
             if go and rank == 0:
                 dmod.write_pairwise(outputs[pairs], ids, full)
@@ -1529,6 +1571,7 @@ def add_arguments(sub):
     sub.add_argument("--closePairs", dest="closePairs", type=int, default=None, metavar="INT", help="Also write snp_distance_close_pairs.tsv and snp_distance_close_pairs_preserved.tsv into the work directory: the rows of the pairwise files whose distance is at most INT, thresholded on the device (as distance --amdClosePairs --amdMaxPairDistance)")
     sub.add_argument("--clusters", dest="clusters", type=int, nargs="+", default=None, metavar="INT", help="Also write snp_clusters.tsv and snp_clusters_preserved.tsv into the work directory: every sample's single-linkage cluster number at each of the SNP thresholds (as distance --amdClusters --amdClusterThresholds)")
     sub.add_argument("--mst", dest="mst", action="store_true", help="Also write snp_mst.tsv, snp_mst_preserved.tsv, snp_dendrogram.nwk and snp_dendrogram_preserved.nwk into the work directory: the minimum spanning tree of the samples and their single-linkage dendrogram, built on the device (as distance --amdMst --amdDendrogram)")
+    sub.add_argument("--pairSites", dest="pairSites", action="store_true", help="With --closePairs: also write snp_close_pair_sites.tsv and snp_close_pair_sites_preserved.tsv, with --mst: snp_mst_sites.tsv and snp_mst_sites_preserved.tsv, into the work directory: the sites (Chrom and Pos of the flow's snplist) at which the two samples of every close pair i < j / of every tree edge differ, and their bases, found on the device (as distance --amdClosePairSites / --amdMstSites --amdSnpList)")
     sub.add_argument("--noConsensusVcf", dest="noConsensusVcf", action="store_true", help="Do not write consensus.vcf / consensus_preserved.vcf")
     sub.add_argument("--residentBytes", dest="residentBytes", type=int, default=0, metavar="INT", help="Device memory for resident pileups (0 = what is free, less 24 GiB); files past it are streamed twice in site calling mode device only: in modes existing and varscan --pileupRoute auto streams every pileup once instead")
     sub.add_argument("--pileupRoute", dest="pileupRoute", type=str, default=None, choices=PILEUP_ROUTES, metavar="ROUTE",
