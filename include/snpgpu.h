@@ -769,6 +769,59 @@ int  snpgpu_write_mst_tsv(const char *path, const char *ids, const uint64_t *id_
 int  snpgpu_write_dendrogram_newick(const char *path, const char *ids, const uint64_t *id_off, uint32_t n, const uint32_t *u,
                                     const uint32_t *v, const int32_t *dist, uint32_t n_edges);
 
+/* ---- complete- and average-linkage trees (csrc/linkage.hip) ---------------------------------------------------------------
+ * Additive entries of ABI 7, like the ones above.  Samples are 0 ... n-1.  A cluster is a set of samples, its id its smallest
+ * sample.  kind 0, complete linkage: d(A,B) = max d(a,b); kind 1, average linkage (UPGMA): d(A,B) = S(A,B) / (|A| |B|), S the
+ * sum of d(a,b), held as the integer S and the two sizes, never as a float.  Pairs of live clusters are totally ordered by
+ * (d(A,B), min id, max id), rationals compared exactly; THE tree is the one that merges the least pair n - 1 times, so it is
+ * unique and its merges (a, b, sizeA, sizeB, num), a = idA < b = idB, num = d (complete) or S (average), ascend in that key.
+ *
+ * snpgpu_linkage_dev: the tree of the symmetric device int32 matrix (row i at d_matrix + i * row_stride elements, row_stride >= n,
+ * 4-byte aligned; columns >= n and the diagonal are never taken, whatever they hold; the matrix is not modified).  d_a, d_b,
+ * d_size_a, d_size_b, d_num (room for n - 1 each) receive the merges in ascending key order; *out_n_merges and *out_rounds
+ * (host) how many there are and how many rounds built them: a round merges every reciprocal-nearest-neighbour pair, so there
+ * are at most n - 1.  n <= 1: 0 merges, 0 rounds.  Every comparison is exact: products of two 64-bit numbers are compared in
+ * 128 bits.  A matrix whose sums could leave 64 bits — (largest entry) * floor(n/2) * ceil(n/2) >= 2^64, average linkage only —
+ * and a matrix with a negative entry are refused with SNPGPU_E_ARG before the first round.  Needs 8 n^2 bytes of device memory
+ * (SNPGPU_E_NOMEM).  The call waits for the stream once per round; the final ordering is host code. */
+int  snpgpu_linkage_dev(snpgpu_ctx *ctx, const int32_t *d_matrix, uint32_t n, uint64_t row_stride, int kind, uint32_t *d_a,
+                        uint32_t *d_b, uint32_t *d_size_a, uint32_t *d_size_b, uint64_t *d_num, uint32_t *out_n_merges,
+                        uint32_t *out_rounds);
+/* Host form (as snpgpu_mst): packs the symbols, computes the matrix and builds the tree on the device; the five host arrays hold
+ * n_rows - 1 merges.  With out_matrix null the n x n matrix never crosses the host link; not null: it is copied there too, from
+ * the same computation. */
+int  snpgpu_linkage(snpgpu_ctx *ctx, const uint8_t *symbols, uint32_t n_rows, uint32_t n_sites, int kind, uint32_t *out_a,
+                    uint32_t *out_b, uint32_t *out_size_a, uint32_t *out_size_b, uint64_t *out_num, int32_t *out_matrix,
+                    uint32_t *out_n_merges, uint32_t *out_rounds);
+/* Host form for a caller that has the matrix already (a table was asked for): uploads the HOST int32 matrix and builds the tree. */
+int  snpgpu_linkage_of_matrix(snpgpu_ctx *ctx, const int32_t *matrix, uint32_t n, uint64_t row_stride, int kind, uint32_t *out_a,
+                              uint32_t *out_b, uint32_t *out_size_a, uint32_t *out_size_b, uint64_t *out_num,
+                              uint32_t *out_n_merges, uint32_t *out_rounds);
+/* Host code: the clusters of a merge list (ascending key order, as the calls above give it) at every threshold: a merge belongs
+ * to T when num <= T (complete) or num <= T * sizeA * sizeB (average); heights are monotone, so those are a prefix.
+ * out_numbers[t * n + i] and out_n_clusters[t] as snpgpu_clusters: numbers 1, 2, ... in the order of the smallest sample.  With
+ * complete linkage every two members of a cluster are within T.  SNPGPU_E_ARG unless the merges are those of a tree of the n
+ * samples, checked as the writers below check them: a < b < n, both live clusters of the sizes given, fewer than n merges. */
+int  snpgpu_linkage_cut(int kind, uint32_t n, const uint32_t *a, const uint32_t *b, const uint32_t *size_a, const uint32_t *size_b,
+                        const uint64_t *num, uint32_t n_merges, const int32_t *thresholds, uint32_t n_thresholds,
+                        uint32_t *out_numbers, uint32_t *out_n_clusters);
+/* The two texts (host code).  Merge file: "Seq1\tSeq2\tSize1\tSize2\tDistance\n", then per merge in the order given the ids of a
+ * and b, the two sizes and the distance: num for complete linkage; for average linkage S / (sizeA sizeB) rounded half up to
+ * exactly six decimals, in integers: (2 S 10^6 + sa sb) / (2 sa sb), split at 10^6.  Dendrogram: one Newick line in the grammar
+ * of snpgpu_write_dendrogram_newick (same quoting, the child with the smaller sample first, no length at the root, ";\n" for
+ * n = 0, "id;\n" for n = 1, no recursion).  A node's height in integer millionths is round_half_up(num 10^6 / (2 sa sb)), sa sb
+ * taken as 1 for complete linkage, leaves 0; a branch length is H_parent - H_child: the integer part, then, when the fraction is
+ * not zero, "." and its six digits without trailing zeros ("7", "7.5", "0.0625").  SNPGPU_E_ARG unless the merges are a tree
+ * of the n samples: a < b < n live clusters of the sizes given, n - 1 of them for the dendrogram, heights that do not fall —
+ * and when a distance does not fit 64 bits as millionths (num 10^6 / (sa sb) >= 2^64: the dendrogram of either kind, the merge
+ * file of average linkage; no sum of int32 entries comes near it). */
+int  snpgpu_write_linkage_tsv(const char *path, const char *ids, const uint64_t *id_off, uint32_t n, int kind, const uint32_t *a,
+                              const uint32_t *b, const uint32_t *size_a, const uint32_t *size_b, const uint64_t *num,
+                              uint32_t n_merges);
+int  snpgpu_write_linkage_newick(const char *path, const char *ids, const uint64_t *id_off, uint32_t n, int kind,
+                                 const uint32_t *a, const uint32_t *b, const uint32_t *size_a, const uint32_t *size_b,
+                                 const uint64_t *num, uint32_t n_merges);
+
 /* ---- the differing sites of pairs (csrc/pair_sites.hip) -----------------------------------------------------------------
  * Additive entries of ABI 7, like the ones above: by which columns two samples differ.  Column s of pair (a, b) differs iff
  * both bytes, after upper-casing, are in {A,C,G,T} and are not equal (utils.py:1135-1165, what the distance kernel counts), so

@@ -213,6 +213,10 @@ def parse_argument_list(argv):
     sub.add_argument("--amdClusterThresholds", dest="amdClusterThresholds", type=int, nargs="+", default=None, metavar="INT", help="Extension of this build: the SNP thresholds of the --amdClusters file; sorted and made unique.")
     sub.add_argument("--amdMst", dest="amdMstFile", type=str, default=None, metavar="FILE", help="Extension of this build: output file with the n - 1 edges of the minimum spanning tree of the samples (the tree Kruskal's algorithm builds under the edge order distance, first sample, second sample), one Seq1 / Seq2 / Distance row per edge in that order; built on the device, the full matrix is not written.")
     sub.add_argument("--amdDendrogram", dest="amdDendrogramFile", type=str, default=None, metavar="FILE", help="Extension of this build: output file with the single-linkage dendrogram of the samples as one Newick line: groups join at height distance / 2, so the path between two leaves through their join is their single-linkage distance.")
+    sub.add_argument("--amdLinkage", dest="amdLinkage", type=str, choices=["complete", "average"], default=None, help="Extension of this build: the linkage of the three --amdLinkage* outputs.  complete: two groups are as far apart as their two farthest samples, so every two members of a group at threshold T are within T SNPs; average: the mean distance over all pairs of samples of the two groups (UPGMA).  The tree merges the closest two groups n - 1 times, ties broken by the groups' first samples; it is built on the device in integer arithmetic.")
+    sub.add_argument("--amdLinkageMerges", dest="amdLinkageMergesFile", type=str, default=None, metavar="FILE", help="Extension of this build: output file with the n - 1 merges of the --amdLinkage tree in the order they happen, one Seq1 / Seq2 / Size1 / Size2 / Distance row each: the first samples of the two groups, their sizes and their distance (average linkage: six decimals).")
+    sub.add_argument("--amdLinkageDendrogram", dest="amdLinkageDendrogramFile", type=str, default=None, metavar="FILE", help="Extension of this build: output file with the --amdLinkage tree as one Newick line in the form of --amdDendrogram: groups join at height distance / 2.")
+    sub.add_argument("--amdLinkageClusters", dest="amdLinkageClustersFile", type=str, default=None, metavar="FILE", help="Extension of this build: output file in the format of --amdClusters with every sample's cluster number in the --amdLinkage tree cut at each threshold of --amdClusterThresholds (the merges whose distance is at most the threshold).")
     sub.add_argument("--amdClosePairSites", dest="amdClosePairSitesFile", type=str, default=None, metavar="FILE", help="Extension of this build: output file with the sites at which the two samples of every pair i < j within --amdMaxPairDistance differ, one Seq1 / Seq2 / Site / Base1 / Base2 row per site in ascending column order, the pairs in the pairwise file's order; a pair has as many rows as its distance.  Found on the device from the packed matrix; --amdClosePairs itself is not required and the full matrix is not written.")
     sub.add_argument("--amdMstSites", dest="amdMstSitesFile", type=str, default=None, metavar="FILE", help="Extension of this build: output file with the sites at which the two samples of every edge of the minimum spanning tree differ, in the order of the --amdMst file; rows as in --amdClosePairSites.")
     sub.add_argument("--amdPairSitesPairs", dest="amdPairSitesPairsFile", type=str, default=None, metavar="FILE", help="Extension of this build: input file with two tab-separated sample ids per line (further columns and a first line Seq1 / Seq2 are ignored); the sites at which each of these pairs differs go to --amdPairSitesOut.")

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "internal.h"
+#include "linkage_host.h"
 
 namespace {
 
@@ -335,6 +336,21 @@ extern "C" int snpgpu_write_clusters_tsv(const char *path, const char *ids, cons
 }
 
 // ---- minimum spanning tree and dendrogram (additive: the tree of csrc/mst.hip as text) ----
+namespace {
+// a Newick leaf: the id as it is when it is [A-Za-z0-9.|-]+, else in single quotes with every ' doubled
+template <typename Sink>
+inline void put_newick_label(Sink &o, const char *s, size_t len) {
+    bool bare = len > 0;
+    for (size_t k = 0; k < len && bare; ++k) {
+        const unsigned char c = (unsigned char)s[k];
+        bare = (c >= 'A' && c <= 'Z') || (c >= 'a' && c <= 'z') || (c >= '0' && c <= '9') || c == '.' || c == '|' || c == '-';
+    }
+    if (bare) { o.put(s, len); return; }
+    o.put('\'');
+    for (size_t k = 0; k < len; ++k) { if (s[k] == '\'') o.put('\''); o.put(s[k]); }
+    o.put('\'');
+}
+}  // namespace
 extern "C" int snpgpu_write_mst_tsv(const char *path, const char *ids, const uint64_t *id_off, uint32_t n, const uint32_t *u, const uint32_t *v,
                                     const int32_t *dist, uint32_t n_edges) {
     if (!path || (n && (!ids || !id_off)) || (n_edges && (!u || !v || !dist))) return SNPGPU_E_ARG;
@@ -380,19 +396,7 @@ extern "C" int snpgpu_write_dendrogram_newick(const char *path, const char *ids,
     FileOut o(path);
     if (o.failed) return SNPGPU_E_IO;
     auto d_of = [&](uint32_t node) -> int64_t { return node < n ? 0 : (int64_t)dist[node - n]; };
-    auto label = [&](uint32_t i) {
-        const char *s = ids + id_off[i];
-        const size_t len = (size_t)(id_off[i + 1] - id_off[i]);
-        bool bare = len > 0;
-        for (size_t k = 0; k < len && bare; ++k) {
-            const unsigned char c = (unsigned char)s[k];
-            bare = (c >= 'A' && c <= 'Z') || (c >= 'a' && c <= 'z') || (c >= '0' && c <= '9') || c == '.' || c == '|' || c == '-';
-        }
-        if (bare) { o.put(s, len); return; }
-        o.put('\'');
-        for (size_t k = 0; k < len; ++k) { if (s[k] == '\'') o.put('\''); o.put(s[k]); }
-        o.put('\'');
-    };
+    auto label = [&](uint32_t i) { put_newick_label(o, ids + id_off[i], (size_t)(id_off[i + 1] - id_off[i])); };
     auto length = [&](int64_t twice) {                               // ":" and half of d_parent - d_child, never through a float
         o.put(':');
         o.put_i32((int32_t)(twice / 2));
@@ -487,4 +491,89 @@ extern "C" int snpgpu_write_pair_sites_tsv(const char *path, const char *ids, co
             }
     };
     return write_row_blocks(path, (uint32_t)n_pairs, n_entries, pair_off, header_bytes, header, size_rows, format);
+}
+
+// ---- complete- and average-linkage trees (additive: the merges of csrc/linkage.hip as text; the arithmetic is linkage_host.h) ----
+namespace {
+// millionths as the integer part and, when the fraction is not zero, "." and its six digits without trailing zeros
+inline void put_millionths_short(FileOut &o, uint64_t v) {
+    put_u64(o, v / 1000000u);
+    uint32_t frac = (uint32_t)(v % 1000000u);
+    if (!frac) return;
+    char d[7] = {'.', 0, 0, 0, 0, 0, 0};
+    for (int k = 6; k >= 1; --k) { d[k] = (char)('0' + frac % 10); frac /= 10; }
+    size_t len = 7;
+    while (d[len - 1] == '0') --len;
+    o.put(d, len);
+}
+}  // namespace
+
+extern "C" int snpgpu_write_linkage_tsv(const char *path, const char *ids, const uint64_t *id_off, uint32_t n, int kind, const uint32_t *a, const uint32_t *b,
+                                        const uint32_t *size_a, const uint32_t *size_b, const uint64_t *num, uint32_t n_merges) {
+    if (!path || (n && (!ids || !id_off)) || !lnk_merges_ok(n, kind, a, b, size_a, size_b, num, n_merges, false, kind == SNPGPU_LINKAGE_AVERAGE)) return SNPGPU_E_ARG;
+    FileOut o(path);
+    if (o.failed) return SNPGPU_E_IO;
+    o.put("Seq1\tSeq2\tSize1\tSize2\tDistance\n", 31);
+    for (uint32_t e = 0; e < n_merges && !o.failed; ++e) {
+        o.put(ids + id_off[a[e]], (size_t)(id_off[a[e] + 1] - id_off[a[e]])); o.put('\t');
+        o.put(ids + id_off[b[e]], (size_t)(id_off[b[e] + 1] - id_off[b[e]])); o.put('\t');
+        put_u64(o, size_a[e]); o.put('\t');
+        put_u64(o, size_b[e]); o.put('\t');
+        if (kind == SNPGPU_LINKAGE_COMPLETE) {
+            put_u64(o, num[e]);
+        } else {                                                     // S / (sa sb), half up, exactly six decimals
+            const uint64_t q = lnk_average_millionths(num[e], size_a[e], size_b[e]);
+            char d[7] = {'.', 0, 0, 0, 0, 0, 0};
+            uint32_t frac = (uint32_t)(q % 1000000u);
+            for (int k = 6; k >= 1; --k) { d[k] = (char)('0' + frac % 10); frac /= 10; }
+            put_u64(o, q / 1000000u);
+            o.put(d, 7);
+        }
+        o.put('\n');
+    }
+    return o.finish();
+}
+
+// Newick, one line, in the grammar of snpgpu_write_dendrogram_newick.  Node k < n is leaf k, node n + e the join of merge e; a
+// cluster's node is looked up by its id, which the merge names.  Heights in integer millionths, explicit stack.
+extern "C" int snpgpu_write_linkage_newick(const char *path, const char *ids, const uint64_t *id_off, uint32_t n, int kind, const uint32_t *a, const uint32_t *b,
+                                           const uint32_t *size_a, const uint32_t *size_b, const uint64_t *num, uint32_t n_merges) {
+    if (!path || (n && (!ids || !id_off)) || !lnk_merges_ok(n, kind, a, b, size_a, size_b, num, n_merges, true, true)) return SNPGPU_E_ARG;
+    std::vector<uint32_t> top(n), child((size_t)n_merges * 2);
+    std::vector<uint64_t> height(n_merges);
+    for (uint32_t i = 0; i < n; ++i) top[i] = i;
+    auto h_of = [&](uint32_t node) -> uint64_t { return node < n ? 0 : height[node - n]; };
+    for (uint32_t e = 0; e < n_merges; ++e) {
+        height[e] = lnk_height(kind, num[e], size_a[e], size_b[e]);
+        if (height[e] < h_of(top[a[e]]) || height[e] < h_of(top[b[e]])) return SNPGPU_E_ARG;      // a child above its parent: not this linkage's tree
+        child[2 * (size_t)e] = top[a[e]];                            // a < b: the child with the smaller sample first
+        child[2 * (size_t)e + 1] = top[b[e]];
+        top[a[e]] = n + e;
+    }
+    FileOut o(path);
+    if (o.failed) return SNPGPU_E_IO;
+    auto label = [&](uint32_t i) { put_newick_label(o, ids + id_off[i], (size_t)(id_off[i + 1] - id_off[i])); };
+    if (n) {
+        struct Frame { uint32_t node, up, state; };                  // up: the parent node (or itself at the root); state: children written
+        std::vector<Frame> stack;
+        const uint32_t root = n_merges ? n + n_merges - 1 : 0u;      // the last merge is the root: every other cluster has retired
+        stack.push_back({root, root, 0u});
+        while (!stack.empty() && !o.failed) {
+            Frame &f = stack.back();
+            if (f.node < n) {
+                label(f.node);
+                if (f.up != f.node) { o.put(':'); put_millionths_short(o, h_of(f.up)); }
+                stack.pop_back();
+                continue;
+            }
+            const uint32_t e = f.node - n, me = f.node;
+            if (f.state == 0) { o.put('('); f.state = 1; const uint32_t c = child[2 * (size_t)e]; stack.push_back({c, me, 0u}); continue; }
+            if (f.state == 1) { o.put(','); f.state = 2; const uint32_t c = child[2 * (size_t)e + 1]; stack.push_back({c, me, 0u}); continue; }
+            o.put(')');
+            if (f.up != f.node) { o.put(':'); put_millionths_short(o, h_of(f.up) - h_of(f.node)); }
+            stack.pop_back();
+        }
+    }
+    o.put(";\n", 2);
+    return o.finish();
 }

@@ -1170,6 +1170,60 @@ class Device(object):
                 return (u, v, dist, csr, mat) if want_matrix else (u, v, dist, csr)
             cap = int(out_n.value)
 
+    # ---- complete- and average-linkage trees (additive to distance.py:93-106) -------------------
+    @staticmethod
+    def _linkage_kind(kind):
+        try:
+            return {"complete": 0, "average": 1, 0: 0, 1: 1}[kind]
+        except (KeyError, TypeError):
+            raise ValueError("the linkage is 'complete' or 'average'")
+
+    def linkage_dev(self, d_matrix, n, row_stride, kind, d_a=0, d_b=0, d_size_a=0, d_size_b=0, d_num=0):
+        """The complete- ('complete' / 0) or average-linkage ('average' / 1) tree of a symmetric device int32 matrix (columns < n,
+        the diagonal left out) into d_a / d_b / d_size_a / d_size_b (uint32) and d_num (uint64), room for n - 1 each: the merges
+        in ascending key order.  Returns (number of merges, rounds)."""
+        opt = lambda v: C.c_void_p(int(v)) if v else None     # noqa: E731
+        n_merges, rounds = C.c_uint32(0), C.c_uint32(0)
+        self._check(self.lib.snpgpu_linkage_dev(self.ctx, opt(d_matrix), int(n), int(row_stride), self._linkage_kind(kind), opt(d_a), opt(d_b), opt(d_size_a),
+                                                opt(d_size_b), opt(d_num), C.byref(n_merges), C.byref(rounds)))
+        return int(n_merges.value), int(rounds.value)
+
+    def _linkage_host(self, n, call):
+        m = max(n - 1, 0)
+        a, b, sa, sb = (np.zeros(m, dtype=np.uint32) for _ in range(4))
+        num = np.zeros(m, dtype=np.uint64)
+        opt = lambda x: _ptr(x) if x.size else None           # noqa: E731
+        n_merges, rounds = C.c_uint32(0), C.c_uint32(0)
+        self._check(call(opt(a), opt(b), opt(sa), opt(sb), opt(num), C.byref(n_merges), C.byref(rounds)))
+        if int(n_merges.value) != m:
+            raise RuntimeError("the tree of %d samples has %d merges" % (n, int(n_merges.value)))
+        return (a, b, sa, sb, num), int(rounds.value)
+
+    def linkage(self, symbols, kind, want_matrix=False, want_rounds=False):
+        """symbols: (n, s) uint8 array of sequence bytes.  Returns (a, b, size_a, size_b uint32, num uint64): the n - 1 merges of
+        the complete- or average-linkage tree of the distance matrix in ascending key order, a < b the ids (smallest samples) of
+        the two clusters, num their distance (complete) or the sum of their distances (average).  The matrix stays on the
+        device — unless want_matrix, which adds the (n, n) int32 matrix of ``distance`` from the same computation; want_rounds
+        adds the number of rounds as the last value."""
+        sym = np.ascontiguousarray(symbols, dtype=np.uint8)
+        n, s = sym.shape
+        k = self._linkage_kind(kind)
+        mat = np.zeros((n, n), dtype=np.int32) if want_matrix else None
+        got, rounds = self._linkage_host(n, lambda a, b, sa, sb, num, nm, nr: self.lib.snpgpu_linkage(
+            self.ctx, _ptr(sym) if sym.size else None, n, s, k, a, b, sa, sb, num, _ptr(mat) if want_matrix and mat.size else None, nm, nr))
+        return got + ((mat,) if want_matrix else ()) + ((rounds,) if want_rounds else ())
+
+    def linkage_of_matrix(self, matrix, kind, want_rounds=False):
+        """As ``linkage`` for an (n, n) host int32 matrix a caller already has."""
+        mat = np.ascontiguousarray(matrix, dtype=np.int32)
+        if mat.ndim != 2 or mat.shape[0] != mat.shape[1]:
+            raise ValueError("the matrix is square")
+        n = mat.shape[0]
+        k = self._linkage_kind(kind)
+        got, rounds = self._linkage_host(n, lambda a, b, sa, sb, num, nm, nr: self.lib.snpgpu_linkage_of_matrix(
+            self.ctx, _ptr(mat) if mat.size else None, n, n, k, a, b, sa, sb, num, nm, nr))
+        return got + ((rounds,) if want_rounds else ())
+
     # ---- the differing sites of pairs (additive to distance.py:93-106) ---------------------------
     def pair_sites_dev(self, d_packed, n_rows, n_sites, d_a, d_b, n_pairs, capacity=0, d_pair_off=0, d_site=0, d_bases=0):
         """The columns at which the pairs (d_a[p], d_b[p]) of rows of a device packed matrix differ, pair by pair, ascending:

@@ -195,6 +195,76 @@ def write_dendrogram(path, ids, u, v, dist):
     _write_tree("snpgpu_write_dendrogram_newick", path, ids, u, v, dist)
 
 
+def linkage_of_symbols(dev, file_ids, sym, lens, kind):
+    """As mst_of_matrix, but what comes back is the complete- or average-linkage tree of the samples: (ids, a, b, size_a, size_b,
+    num), the n - 1 merges in ascending key order (Device.linkage); built on the device, where the matrix stays."""
+    ids, rows = _sorted_rows(file_ids, sym, lens)
+    if rows is None:
+        rows = np.zeros((0, 0), dtype=np.uint8)
+    return (ids,) + tuple(dev.linkage(rows, kind))
+
+
+def _merge_arrays(a, b, size_a, size_b, num):
+    arrays = [np.ascontiguousarray(x, dtype=np.uint32) for x in (a, b, size_a, size_b)] + [np.ascontiguousarray(num, dtype=np.uint64)]
+    if len(set(len(x) for x in arrays)) != 1:
+        raise ValueError("a, b, size_a, size_b and num hold one entry per merge")
+    return arrays
+
+
+def linkage_cut(kind, n, a, b, size_a, size_b, num, thresholds):
+    """Cluster numbers (len(thresholds), n) uint32 of a merge list at every threshold, numbered as Device.clusters numbers them:
+    a merge belongs to T when num <= T (complete) or num <= T * size_a * size_b (average)."""
+    from . import _lib as L
+    from .device import Device
+    arrays = _merge_arrays(a, b, size_a, size_b, num)
+    thr = np.ascontiguousarray(thresholds, dtype=np.int32)
+    numbers = np.zeros((len(thr), int(n)), dtype=np.uint32)
+    counts = np.zeros(len(thr), dtype=np.uint32)
+    opt = lambda x: x.ctypes.data if x.size else None          # noqa: E731
+    rc = L.load().snpgpu_linkage_cut(Device._linkage_kind(kind), int(n), *([opt(x) for x in arrays] + [len(arrays[0]), opt(thr), len(thr), opt(numbers), opt(counts)]))
+    if rc != 0:
+        raise ValueError("the merges are not those of a tree of %d samples" % int(n))
+    return numbers, counts
+
+
+def _write_linkage(entry, path, ids, kind, a, b, size_a, size_b, num):
+    from . import _lib as L
+    from .device import Device
+    blob, off = _id_table(ids)
+    arrays = _merge_arrays(a, b, size_a, size_b, num)
+    opt = lambda x: x.ctypes.data if x.size else None          # noqa: E731
+    rc = getattr(L.load(), entry)(path.encode(), blob, off.ctypes.data, len(ids), Device._linkage_kind(kind), *([opt(x) for x in arrays] + [len(arrays[0])]))
+    if rc == L.E_IO:
+        raise IOError("cannot write %s" % path)
+    if rc == L.E_ARG:
+        raise ValueError("the merges are not those of a tree of the %d ids" % len(ids))
+    if rc != 0:
+        raise RuntimeError("%s failed (%d)" % (entry, rc))
+
+
+def write_linkage_merges(path, ids, kind, a, b, size_a, size_b, num):
+    """Header and one "id\tid\tsize\tsize\tdistance" row per merge, in the order given; the distance of average linkage has six
+    decimals, rounded half up in integers (csrc/tsv_out.hip)."""
+    _write_linkage("snpgpu_write_linkage_tsv", path, ids, kind, a, b, size_a, size_b, num)
+
+
+def write_linkage_dendrogram(path, ids, kind, a, b, size_a, size_b, num):
+    """The tree of the n - 1 merges as one Newick line: a join lies at half the distance of its two clusters, in millionths."""
+    _write_linkage("snpgpu_write_linkage_newick", path, ids, kind, a, b, size_a, size_b, num)
+
+
+def write_linkage_outputs(ids, kind, merges, merges_file, dendrogram_file, clusters_file, thresholds):
+    """The three additive outputs of one tree."""
+    if merges_file:
+        write_linkage_merges(merges_file, ids, kind, *merges)
+    if dendrogram_file:
+        write_linkage_dendrogram(dendrogram_file, ids, kind, *merges)
+    if clusters_file:
+        thresholds = cluster_thresholds(thresholds)
+        numbers, _ = linkage_cut(kind, len(ids), *(tuple(merges) + (thresholds,)))
+        write_clusters(clusters_file, ids, thresholds, numbers)
+
+
 def pairs_of_csr(row_off, col, dist, threshold):
     """The entries i < j, d <= threshold of a CSR in its order: (a, b, d) — each unordered pair of the close-pairs file once."""
     row_off = np.asarray(row_off, dtype=np.int64)
@@ -331,6 +401,8 @@ def calculate_snp_distances(args):
     user_pairs_file = getattr(args, "amdPairSitesPairsFile", None)
     user_sites_file = getattr(args, "amdPairSitesOutFile", None)
     snp_list_file = getattr(args, "amdSnpListFile", None)
+    linkage_kind = getattr(args, "amdLinkage", None)
+    linkage_files = (getattr(args, "amdLinkageMergesFile", None), getattr(args, "amdLinkageDendrogramFile", None), getattr(args, "amdLinkageClustersFile", None))
     if utils.verify_existing_input_files("SNP matrix file", [input_file]) > 0:
         utils.global_error("Error: cannot calculate sequence distances without the snp matrix file.")
     if close_file and max_pair_distance is None:
@@ -345,9 +417,15 @@ def calculate_snp_distances(args):
         utils.global_error("Error: cannot name the differing sites without the snplist file.")
     if clusters_file and not thresholds:
         utils.global_error("Error: --amdClusters needs at least one threshold in --amdClusterThresholds.")
+    if any(linkage_files) and not linkage_kind:
+        utils.global_error("Error: --amdLinkageMerges, --amdLinkageDendrogram and --amdLinkageClusters need --amdLinkage.")
+    if linkage_kind and not any(linkage_files):
+        utils.global_error("Error: --amdLinkage needs at least one of --amdLinkageMerges, --amdLinkageDendrogram and --amdLinkageClusters.")
+    if linkage_files[2] and not thresholds:
+        utils.global_error("Error: --amdLinkageClusters needs at least one threshold in --amdClusterThresholds.")
     if (max_pair_distance is not None and max_pair_distance < 0) or any(t < 0 for t in thresholds):
         utils.global_error("Error: a distance threshold cannot be negative.")
-    outputs = [f for f in (pairwise_file, matrix_file, close_file, clusters_file, mst_file, dendrogram_file, close_sites_file, mst_sites_file, user_sites_file) if f]
+    outputs = [f for f in (pairwise_file, matrix_file, close_file, clusters_file, mst_file, dendrogram_file, close_sites_file, mst_sites_file, user_sites_file) + linkage_files if f]
     if not outputs:
         utils.global_error("Error: no output file specified.")
 
@@ -361,7 +439,7 @@ def calculate_snp_distances(args):
     from .device import default_device
     if close_sites_file or mst_sites_file or user_sites_file:
         _distances_with_sites(default_device, file_ids, sym, lens, snp_list_file, pairwise_file, matrix_file, close_file, max_pair_distance, clusters_file, thresholds,
-                              mst_file, dendrogram_file, close_sites_file, mst_sites_file, user_pairs_file, user_sites_file)
+                              mst_file, dendrogram_file, close_sites_file, mst_sites_file, user_pairs_file, user_sites_file, linkage_kind, linkage_files)
         return
     dev = default_device()
     mat = None
@@ -385,6 +463,15 @@ def calculate_snp_distances(args):
         mat = got[4] if len(got) > 4 else None
     elif pairwise_file or matrix_file:
         ids, mat = distance_of_matrix(dev, file_ids, sym, lens)
+    if linkage_kind:
+        # from the matrix of that computation when a table brought it to the host; else built where the matrix is computed, and
+        # only the n - 1 merges come to the host (beside a tree or a threshold that is one more computation of the matrix)
+        if mat is not None:
+            merges = dev.linkage_of_matrix(mat, linkage_kind)
+        else:
+            got = linkage_of_symbols(dev, file_ids, sym, lens, linkage_kind)
+            ids, merges = got[0], got[1:]
+        write_linkage_outputs(ids, linkage_kind, merges, linkage_files[0], linkage_files[1], linkage_files[2], thresholds)
     if pairwise_file:
         write_pairwise(pairwise_file, ids, mat)
     if matrix_file:
@@ -398,7 +485,8 @@ def calculate_snp_distances(args):
 
 
 def _distances_with_sites(device_of, file_ids, sym, lens, snp_list_file, pairwise_file, matrix_file, close_file, max_pair_distance, clusters_file, thresholds,
-                          mst_file, dendrogram_file, close_sites_file, mst_sites_file, user_pairs_file, user_sites_file):
+                          mst_file, dendrogram_file, close_sites_file, mst_sites_file, user_pairs_file, user_sites_file, linkage_kind=None,
+                          linkage_files=(None, None, None)):
     """calculate_snp_distances when the differing sites of some pairs are asked for: the symbols are uploaded and packed once; the
     matrix is computed once, and only when a tree, a threshold or a table needs it; the packed matrix stays on the device until
     every pair list has been answered from it.  The n x n matrix comes to the host for -p / -m alone."""
@@ -432,6 +520,9 @@ def _distances_with_sites(device_of, file_ids, sym, lens, snp_list_file, pairwis
         return dev.pair_sites_kept(a, b, expect=expect) if kept else dev.pair_sites(rows, a, b, expect=expect)
 
     try:
+        if linkage_kind:
+            merges = dev.linkage_of_matrix(mat, linkage_kind) if mat is not None else dev.linkage(rows, linkage_kind)
+            write_linkage_outputs(ids, linkage_kind, merges, linkage_files[0], linkage_files[1], linkage_files[2], thresholds)
         if pairwise_file:
             write_pairwise(pairwise_file, ids, mat)
         if matrix_file:

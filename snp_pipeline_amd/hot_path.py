@@ -238,6 +238,14 @@ class _Job(object):
         if self.mst:
             self.outputs.update(mst=os.path.join(work_dir, "snp_mst.tsv"), mst_p=os.path.join(work_dir, "snp_mst_preserved.tsv"),
                                 dendrogram=os.path.join(work_dir, "snp_dendrogram.nwk"), dendrogram_p=os.path.join(work_dir, "snp_dendrogram_preserved.nwk"))
+        # --linkage (additive to the distance step): the complete- or average-linkage tree, its dendrogram and, with --clusters, its cuts
+        self.linkage = getattr(args, "linkage", None)
+        if self.linkage:
+            self.outputs.update(linkage=os.path.join(work_dir, "snp_linkage.tsv"), linkage_p=os.path.join(work_dir, "snp_linkage_preserved.tsv"),
+                                linkage_nwk=os.path.join(work_dir, "snp_linkage.nwk"), linkage_nwk_p=os.path.join(work_dir, "snp_linkage_preserved.nwk"))
+            if self.cluster_thresholds:
+                self.outputs.update(linkage_clusters=os.path.join(work_dir, "snp_linkage_clusters.tsv"),
+                                    linkage_clusters_p=os.path.join(work_dir, "snp_linkage_clusters_preserved.tsv"))
         # --pairSites (additive to the distance step): the sites at which the close pairs / the tree's edges differ
         self.pair_sites = bool(getattr(args, "pairSites", False))
         if self.pair_sites and self.close_pairs is None and not self.mst:
@@ -1210,6 +1218,21 @@ def _mst_rows(torch, dev, d_matrix, n, row_stride, row_lo, row_hi):
     return u[:k].cpu().numpy().view(np.uint32), v[:k].cpu().numpy().view(np.uint32), dist[:k].cpu().numpy()
 
 
+def linkage_on_rank_0(torch, dev, comm, bands, dmat, full, n, kind):
+    """The complete- or average-linkage tree of the sorted samples, on rank 0 (None elsewhere): from the device matrix when this
+    is the only rank, else from the complete matrix rank 0 has gathered for the tables.  The rounds contract one working matrix,
+    which is not distributed over the ranks."""
+    if comm.rank != 0:
+        return None
+    if comm.dist and n:
+        return dev.linkage_of_matrix(full, kind)
+    m = max(n - 1, 1)
+    words = [torch.zeros(m, dtype=torch.int32, device="cuda") for _ in range(4)]
+    num = torch.zeros(m, dtype=torch.int64, device="cuda")
+    k, _ = dev.linkage_dev(dmat.data_ptr(), n, max(bands.n_padded, 1), kind, *([w.data_ptr() for w in words] + [num.data_ptr()]))
+    return tuple(w[:k].cpu().numpy().view(np.uint32) for w in words) + (num[:k].cpu().numpy().view(np.uint64),)
+
+
 def mst_over_ranks(torch, dev, comm, bands, dmat, band, n):
     """The minimum spanning tree of the whole n x n distance matrix as (u, v, dist) on rank 0, None on the others.  With one rank:
     from `dmat` (pitch bands.n_padded, n columns: the zero padding is never an edge).  With several: each rank builds the forest of
@@ -1337,6 +1360,13 @@ def stage_matrices_and_distances(job):
                 sfx = "" if flow == 1 else "_p"
                 dmod.write_mst(outputs["mst" + sfx], ids, *tree)
                 dmod.write_dendrogram(outputs["dendrogram" + sfx], ids, *tree)
+        with job.guard() as go:
+            if go and job.linkage:
+                merges = linkage_on_rank_0(torch, dev, comm, bands, dmat, full, n, job.linkage)
+                if rank == 0:
+                    sfx = "" if flow == 1 else "_p"
+                    dmod.write_linkage_outputs(ids, job.linkage, merges, outputs["linkage" + sfx], outputs["linkage_nwk" + sfx],
+                                               outputs["linkage_clusters" + sfx] if job.cluster_thresholds else None, job.cluster_thresholds)
         with job.guard() as go:
             # every rank holds packed_sorted after the all-gather: rank 0 asks it for the sites behind the gathered pairs and edges
             if go and rank == 0 and job.pair_sites:
@@ -1571,6 +1601,7 @@ def add_arguments(sub):
     sub.add_argument("--closePairs", dest="closePairs", type=int, default=None, metavar="INT", help="Also write snp_distance_close_pairs.tsv and snp_distance_close_pairs_preserved.tsv into the work directory: the rows of the pairwise files whose distance is at most INT, thresholded on the device (as distance --amdClosePairs --amdMaxPairDistance)")
     sub.add_argument("--clusters", dest="clusters", type=int, nargs="+", default=None, metavar="INT", help="Also write snp_clusters.tsv and snp_clusters_preserved.tsv into the work directory: every sample's single-linkage cluster number at each of the SNP thresholds (as distance --amdClusters --amdClusterThresholds)")
     sub.add_argument("--mst", dest="mst", action="store_true", help="Also write snp_mst.tsv, snp_mst_preserved.tsv, snp_dendrogram.nwk and snp_dendrogram_preserved.nwk into the work directory: the minimum spanning tree of the samples and their single-linkage dendrogram, built on the device (as distance --amdMst --amdDendrogram)")
+    sub.add_argument("--linkage", dest="linkage", type=str, choices=["complete", "average"], default=None, help="Also write snp_linkage.tsv, snp_linkage_preserved.tsv, snp_linkage.nwk and snp_linkage_preserved.nwk into the work directory: the merges and the dendrogram of the complete- or average-linkage tree of the samples (as distance --amdLinkage --amdLinkageMerges --amdLinkageDendrogram), and with --clusters snp_linkage_clusters.tsv and snp_linkage_clusters_preserved.tsv: the tree cut at each of the thresholds (as --amdLinkageClusters).  Built on the device of rank 0 from the complete matrix it gathers for the tables; the linkage itself is not distributed over the ranks")
     sub.add_argument("--pairSites", dest="pairSites", action="store_true", help="With --closePairs: also write snp_close_pair_sites.tsv and snp_close_pair_sites_preserved.tsv, with --mst: snp_mst_sites.tsv and snp_mst_sites_preserved.tsv, into the work directory: the sites (Chrom and Pos of the flow's snplist) at which the two samples of every close pair i < j / of every tree edge differ, and their bases, found on the device (as distance --amdClosePairSites / --amdMstSites --amdSnpList)")
     sub.add_argument("--noConsensusVcf", dest="noConsensusVcf", action="store_true", help="Do not write consensus.vcf / consensus_preserved.vcf")
     sub.add_argument("--residentBytes", dest="residentBytes", type=int, default=0, metavar="INT", help="Device memory for resident pileups (0 = what is free, less 24 GiB); files past it are streamed twice in site calling mode device only: in modes existing and varscan --pileupRoute auto streams every pileup once instead")
