@@ -866,6 +866,49 @@ int  snpgpu_write_pair_sites_tsv(const char *path, const char *ids, const uint64
                                  const uint8_t *bases, const char *chrom_names, const uint64_t *chrom_off,
                                  const uint32_t *chrom_of_site, const uint64_t *pos_of_site);
 
+/* ---- query-against-database nearest neighbours (csrc/nearest.hip) --------------------------------------------------------
+ * Additive entries of ABI 7, like the ones above: q query samples against n database samples, without the (n + q)^2 matrix.
+ * d(i, j) counts the columns at which query i and database sample j differ under the predicate of the distance kernel
+ * (utils.py:1135-1165).  For query i the database samples with d(i, j) <= threshold are ordered by (d, j) and the first k kept
+ * (k = 0: all of them; threshold = INT32_MAX: none): ties at the cut go to the smaller database index, so the answer is unique.
+ *
+ * snpgpu_distance_rect_packed_dev: d_packed_q (q rows) and d_packed_db (n rows) are packed matrices of snpgpu_pack_matrix_dev
+ * over the same n_sites (rows of snpgpu_packed_row_bytes(n_sites) bytes, 16-byte aligned); d_out[i * out_stride + j] = d(i, j)
+ * for i < q, j < n (int32, out_stride >= n elements, 4-byte aligned).  Nothing is written beyond column n of a row or beyond
+ * row q.  route: 0 auto (narrow for q <= 64, the measured crossover), 1 narrow (tiles of 16 queries x 64 database rows: the
+ * sweep of the database is HBM-bound for few queries), 2 tile (128 x 128, the shape of snpgpu_distance_packed_dev: VALU-bound);
+ * both give the same numbers.  With fewer tiles than CUs and at least 4 slabs per row (slabs of 16 words narrow, 4 words tile)
+ * the word range is split and the parts add into the zeroed output with integer atomics.  Enqueued on the context's stream;
+ * nothing waits. */
+int  snpgpu_distance_rect_packed_dev(snpgpu_ctx *ctx, const void *d_packed_q, uint32_t q, const void *d_packed_db, uint32_t n,
+                                     uint32_t n_sites, int route, int32_t *d_out, uint64_t out_stride);
+/* snpgpu_nearest_dev: the selection over rows 0 ... q-1 of a device int32 matrix (row i at d_matrix + i * row_stride elements,
+ * row_stride >= n, 4-byte aligned; signed entries; whatever lies between n and row_stride is never read) as a CSR:
+ * d_row_off[q + 1], then d_col[] / d_dist[] with row i's entries in ascending (d, column).  A radix select finds the k-th
+ * smallest value of a row that k cuts; every position comes from prefix sums and a stable sort, none from an atomic: the same
+ * matrix gives the same bytes.  The capacity protocol of snpgpu_close_pairs_dev: *out_n (host) is always set to the number of
+ * entries; when it exceeds `capacity` nothing else is written, and capacity 0 only counts.  q = 0 or n = 0: no entries, the
+ * offsets (written when capacity is not 0) all zero.  The call waits for the stream for the count, and again before it frees
+ * its sort workspace. */
+int  snpgpu_nearest_dev(snpgpu_ctx *ctx, const int32_t *d_matrix, uint32_t q, uint32_t n, uint64_t row_stride, uint32_t k,
+                        int32_t threshold, uint64_t capacity, uint64_t *d_row_off, uint32_t *d_col, int32_t *d_dist,
+                        uint64_t *out_n);
+/* Host form: uploads and packs both symbol matrices (q x n_sites and n x n_sites bytes) once, then works through the queries
+ * in bands of band_rows rows (0: the largest band whose band x n x 4 bytes stay within a quarter of the free device memory):
+ * per band one sweep of the database by snpgpu_distance_rect_packed_dev and one selection.  Queries are independent, so the
+ * band size does not change a byte.  Only the CSR crosses the host link — and, with out_matrix not null, the q x n int32
+ * matrix (row pitch n).  *out_n is always set; when it exceeds `capacity` (capacity 0 only counts) the contents of the three
+ * arrays are unspecified: q * min(k, n) entries always suffice when k is not 0. */
+int  snpgpu_nearest(snpgpu_ctx *ctx, const uint8_t *q_symbols, uint32_t q, const uint8_t *db_symbols, uint32_t n,
+                    uint32_t n_sites, uint32_t k, int32_t threshold, uint32_t band_rows, int route, uint64_t capacity,
+                    uint64_t *out_row_off, uint32_t *out_col, int32_t *out_dist, uint64_t *out_n, int32_t *out_matrix);
+/* The text (host code, the thread scheme and CPU budget of snpgpu_write_distance_tsv; the threads take equal shares of the
+ * entries): "Seq1\tSeq2\tDistance\n", then "query_id\tdb_id\td\n" per entry of the HOST CSR, query by query in its order.
+ * SNPGPU_E_ARG for a column >= n or offsets that do not rise from 0; SNPGPU_E_IO when the file cannot be created or written. */
+int  snpgpu_write_nearest_tsv(const char *path, const char *q_ids, const uint64_t *q_id_off, uint32_t q, const char *db_ids,
+                              const uint64_t *db_id_off, uint32_t n, const uint64_t *row_off, const uint32_t *col,
+                              const int32_t *dist);
+
 /* ---- the exchange steps of the sharded path: RCCL over xGMI, one process per GPU ------------------------
  * The reference fans out one process per sample (run.py:704-718, `run_array` with `max_processes`) over a shared file system
  * and has no exchange step; sharded over GPUs the hot path has three: C1, the all-gather of the per-rank SNP site keys

@@ -220,6 +220,11 @@ SIGNATURES = {
     "snpgpu_pair_sites_kept": (C.c_int, [_P, _P, _P, C.c_uint64, C.c_uint64, _P, _P, _P, C.POINTER(C.c_uint64)]),
     "snpgpu_packed_drop": (C.c_int, [_P]),
     "snpgpu_write_pair_sites_tsv": (C.c_int, [C.c_char_p, _P, _P, C.c_uint32, _P, _P, C.c_uint64, _P, _P, _P, _P, _P, _P, _P]),
+    "snpgpu_distance_rect_packed_dev": (C.c_int, [_P, _P, C.c_uint32, _P, C.c_uint32, C.c_uint32, C.c_int, _P, C.c_uint64]),
+    "snpgpu_nearest_dev": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_int32, C.c_uint64, _P, _P, _P, C.POINTER(C.c_uint64)]),
+    "snpgpu_nearest": (C.c_int, [_P, _P, C.c_uint32, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, C.c_uint32, C.c_int, C.c_uint64, _P, _P, _P,
+                                 C.POINTER(C.c_uint64), _P]),
+    "snpgpu_write_nearest_tsv": (C.c_int, [C.c_char_p, _P, _P, C.c_uint32, _P, _P, C.c_uint32, _P, _P, _P]),
     "snpgpu_dense_windows": (C.c_int, [_P, _P, _P, C.c_uint32, _P, _P, C.c_uint32, _P, _P, _P, C.POINTER(C.c_uint32)]),
     "snpgpu_merge_regions": (C.c_int, [_P, _P, _P, _P, C.c_uint32, _P, _P, _P, C.POINTER(C.c_uint32)]),
     "snpgpu_in_regions": (C.c_int, [_P, _P, _P, C.c_uint32, _P, _P, _P, C.c_uint32, _P]),

@@ -222,6 +222,9 @@ def parse_argument_list(argv):
     sub.add_argument("--amdPairSitesPairs", dest="amdPairSitesPairsFile", type=str, default=None, metavar="FILE", help="Extension of this build: input file with two tab-separated sample ids per line (further columns and a first line Seq1 / Seq2 are ignored); the sites at which each of these pairs differs go to --amdPairSitesOut.")
     sub.add_argument("--amdPairSitesOut", dest="amdPairSitesOutFile", type=str, default=None, metavar="FILE", help="Extension of this build: output file with the differing sites of the pairs of --amdPairSitesPairs, in that file's order; rows as in --amdClosePairSites.")
     sub.add_argument("--amdSnpList", dest="amdSnpListFile", type=str, default=None, metavar="FILE", help="Extension of this build: the snplist file of the snp matrix, whose k-th line names column k; the site files then carry Chrom and Pos in place of the column number Site.")
+    sub.add_argument("--amdQuery", dest="amdQueryFile", type=str, default=None, metavar="FILE", help="Extension of this build: a second multi-fasta file of query samples with as many columns as the snp matrix; the samples of the snp matrix closest to each of them go to --amdNearest.  An id that is in both files is a sample like any other.")
+    sub.add_argument("--amdNearest", dest="amdNearestFile", type=str, default=None, metavar="FILE", help="Extension of this build: output file with one Seq1 / Seq2 / Distance row per query sample of --amdQuery and sample of the snp matrix within --amdMaxPairDistance (when given), per query in ascending distance, ties in the order of the snp matrix's sorted ids, at most --amdNearestCount rows per query.  Computed on the device query by database: the matrix over all samples is not computed.")
+    sub.add_argument("--amdNearestCount", dest="amdNearestCount", type=int, default=None, metavar="INT", help="Extension of this build: the largest number of rows per query in the --amdNearest file; 0, the default, keeps every row.")
     _common(sub)
     sub.set_defaults(func=distance.calculate_snp_distances, excepthook=utils.handle_global_exception)
 

@@ -306,6 +306,36 @@ extern "C" int snpgpu_write_close_pairs_tsv(const char *path, const char *ids, c
     return write_row_blocks(path, n, n_edges, row_off, 19, header, size_rows, format);
 }
 
+// The nearest-neighbour file (csrc/nearest.hip): the rows of a CSR over the queries whose columns name database samples.
+extern "C" int snpgpu_write_nearest_tsv(const char *path, const char *q_ids, const uint64_t *q_id_off, uint32_t q, const char *db_ids,
+                                        const uint64_t *db_id_off, uint32_t n, const uint64_t *row_off, const uint32_t *col, const int32_t *dist) {
+    if (!path || (q && (!q_ids || !q_id_off || !row_off))) return SNPGPU_E_ARG;
+    const uint64_t n_entries = q ? row_off[q] : 0;
+    if (q && (row_off[0] != 0 || (n_entries && (!col || !dist || !db_ids || !db_id_off)))) return SNPGPU_E_ARG;
+    for (uint32_t i = 0; i < q; ++i)
+        if (row_off[i] > row_off[i + 1]) return SNPGPU_E_ARG;
+    for (uint64_t e = 0; e < n_entries; ++e)
+        if (col[e] >= n) return SNPGPU_E_ARG;
+    auto q_len = [&](uint32_t i) { return q_id_off[i + 1] - q_id_off[i]; };
+    auto db_len = [&](uint32_t j) { return db_id_off[j + 1] - db_id_off[j]; };
+    auto header = [&](auto &o) { o.put("Seq1\tSeq2\tDistance\n", 19); };
+    auto size_rows = [&](uint32_t r0, uint32_t r1) {
+        uint64_t total = 0;
+        for (uint32_t i = r0; i < r1; ++i)
+            for (uint64_t e = row_off[i]; e < row_off[i + 1]; ++e) total += q_len(i) + db_len(col[e]) + digits_i32(dist[e]) + 3;
+        return total;
+    };
+    auto format = [&](auto &o, uint32_t r0, uint32_t r1) {
+        for (uint32_t i = r0; i < r1 && !o.failed; ++i)
+            for (uint64_t e = row_off[i]; e < row_off[i + 1]; ++e) {
+                o.put(q_ids + q_id_off[i], (size_t)q_len(i)); o.put('\t');
+                o.put(db_ids + db_id_off[col[e]], (size_t)db_len(col[e])); o.put('\t');
+                o.put_i32(dist[e]); o.put('\n');
+            }
+    };
+    return write_row_blocks(path, q, n_entries, row_off, 19, header, size_rows, format);
+}
+
 extern "C" int snpgpu_write_clusters_tsv(const char *path, const char *ids, const uint64_t *id_off, uint32_t n, const int32_t *thresholds,
                                          uint32_t n_thresholds, const uint32_t *numbers) {
     const uint32_t k = n_thresholds;

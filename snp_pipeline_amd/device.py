@@ -1296,6 +1296,67 @@ class Device(object):
         csr = (row_off, col[:out_n.value], pd[:out_n.value]) if want_pairs else None
         return ((u, v, dist) if want_tree else None), csr, mat
 
+    # ---- query-against-database nearest neighbours (additive to distance.py:93-106) -------------
+    ROUTES = {"auto": 0, "narrow": 1, "tile": 2, 0: 0, 1: 1, 2: 2}
+
+    @classmethod
+    def _route(cls, route):
+        try:
+            return cls.ROUTES[route]
+        except (KeyError, TypeError):
+            raise ValueError("the route is 0 / 'auto', 1 / 'narrow' or 2 / 'tile'")
+
+    def distance_rect_dev(self, d_packed_q, q, d_packed_db, n, n_sites, d_out, out_stride=None, route=0):
+        """The distances of the q rows of one device packed matrix against the n rows of another (both of ``pack_matrix_dev`` over
+        n_sites columns) into the device int32 matrix d_out, row pitch out_stride elements (default n); nothing beyond column n
+        of a row or beyond row q is written.  route: 0 auto, 1 narrow (16 x 64 tiles), 2 tile (128 x 128)."""
+        opt = lambda v: C.c_void_p(int(v)) if v else None     # noqa: E731
+        self._check(self.lib.snpgpu_distance_rect_packed_dev(self.ctx, opt(d_packed_q), int(q), opt(d_packed_db), int(n), int(n_sites), self._route(route),
+                                                             opt(d_out), int(n if out_stride is None else out_stride)))
+
+    def nearest_dev(self, d_matrix, q, n, row_stride, k=0, threshold=None, capacity=0, d_row_off=0, d_col=0, d_dist=0):
+        """Rows 0 ... q-1 of a device int32 matrix (columns < n) as a CSR of each row's entries <= threshold (None: no threshold)
+        in ascending (d, column), the first k of them (0: all).  Returns the number of entries; the three device arrays are written
+        only when 0 < capacity and the number fits."""
+        opt = lambda v: C.c_void_p(int(v)) if v else None     # noqa: E731
+        out_n = C.c_uint64(0)
+        thr = 0x7FFFFFFF if threshold is None else int(threshold)
+        self._check(self.lib.snpgpu_nearest_dev(self.ctx, opt(d_matrix), int(q), int(n), int(row_stride), int(k), thr, int(capacity), opt(d_row_off), opt(d_col),
+                                                opt(d_dist), C.byref(out_n)))
+        return int(out_n.value)
+
+    def nearest(self, q_symbols, db_symbols, k=0, threshold=None, band_rows=0, route=0, want_matrix=False):
+        """q_symbols: (q, s), db_symbols: (n, s) uint8 arrays of sequence bytes.  Returns (row_off uint64 [q + 1], col uint32, dist
+        int32): per query the database rows within `threshold` (None: any distance) in ascending (distance, database row), the
+        first k of them (0: all).  Both matrices are uploaded and packed once; the queries go through the device in bands of
+        band_rows rows (0: as many as a quarter of the free device memory holds), one sweep of the database each, and only the
+        lists come back — unless want_matrix, which adds the (q, n) int32 matrix of the same computation as a fourth value."""
+        qs = np.ascontiguousarray(q_symbols, dtype=np.uint8)
+        db = np.ascontiguousarray(db_symbols, dtype=np.uint8)
+        if qs.ndim != 2 or db.ndim != 2 or (qs.shape[0] and db.shape[0] and qs.shape[1] != db.shape[1]):
+            raise ValueError("the queries have %d columns, the database has %d" % (qs.shape[-1], db.shape[-1]))
+        q, n = qs.shape[0], db.shape[0]
+        s = db.shape[1] if n else qs.shape[1]
+        k = int(k)
+        if k < 0:
+            raise ValueError("k cannot be negative")
+        thr = 0x7FFFFFFF if threshold is None else int(threshold)
+        row_off = np.zeros(q + 1, dtype=np.uint64)
+        mat = np.zeros((q, n), dtype=np.int32) if want_matrix else None
+        opt = lambda x: _ptr(x) if x is not None and x.size else None     # noqa: E731
+        cap = max(q * min(k, n) if k else min(q * n, max(64 * q, 1 << 26)), 1)
+        have_matrix = False
+        while True:                                           # (a second call only without k, past max(64 q, 2^26) entries)
+            col, dist = np.zeros(cap, dtype=np.uint32), np.zeros(cap, dtype=np.int32)
+            out_n = C.c_uint64(0)
+            self._check(self.lib.snpgpu_nearest(self.ctx, opt(qs), q, opt(db), n, s, k, thr, int(band_rows), self._route(route), cap, _ptr(row_off), _ptr(col),
+                                                _ptr(dist), C.byref(out_n), opt(mat) if not have_matrix else None))
+            have_matrix = True
+            if out_n.value <= cap:
+                csr = (row_off, col[:out_n.value], dist[:out_n.value])
+                return csr + (mat,) if want_matrix else csr
+            cap = int(out_n.value)
+
     # ---- filter_regions ------------------------------------------------------------------------
     def dense_windows(self, positions, seg_off, max_snps, windows):
         pos = np.ascontiguousarray(positions, dtype=np.int64)

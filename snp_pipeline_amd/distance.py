@@ -357,6 +357,58 @@ def read_pair_list(path, ids):
     return np.asarray(a, dtype=np.uint32), np.asarray(b, dtype=np.uint32)
 
 
+def query_rows(q_file_ids, q_sym, q_lens, columns):
+    """The query records of a second multi-FASTA in the order the nearest-neighbour output works in: equal ids keep their last
+    record, rows go into sorted-id order.  columns: the width of the database matrix, which every query must have exactly (None:
+    a database without records, nothing to compare with) — else a global error that names both counts.  Returns (ids, (q, s)
+    byte matrix)."""
+    last = {}
+    for r, i in enumerate(q_file_ids):
+        last[i] = r
+    ids = sorted(last)
+    rows = np.asarray([last[i] for i in ids], dtype=np.int64)
+    if columns is not None:
+        for i, r in zip(ids, rows):
+            if int(q_lens[r]) != columns:
+                utils.global_error("Error: the query %s has %d columns, the snp matrix has %d columns." % (i, int(q_lens[r]), columns))
+    if len(ids) == 0:
+        return ids, np.zeros((0, columns or 0), dtype=np.uint8)
+    return ids, np.ascontiguousarray(q_sym[rows])
+
+
+def nearest_of_matrices(dev, db_file_ids, db_sym, db_lens, q_file_ids, q_sym, q_lens, k, threshold, band_rows=0, route=0):
+    """The database samples closest to each query: (q_ids, db_ids, row_off, col, dist) — both id lists sorted (the database as
+    for every other output of the step, the queries by query_rows), per query the database samples within `threshold` SNPs (None:
+    any distance) in ascending (distance, database index), the first k of them (0: all).  The q x n distances are computed on
+    the device query band by query band and selected there; the (n + q)^2 matrix is never computed and only the lists come back."""
+    db_ids, db_rows = _sorted_rows(db_file_ids, db_sym, db_lens)
+    q_ids, q_rows = query_rows(q_file_ids, q_sym, q_lens, None if db_rows is None else db_rows.shape[1])
+    if db_rows is None:
+        db_rows = np.zeros((0, q_rows.shape[1]), dtype=np.uint8)
+    return (q_ids, db_ids) + tuple(dev.nearest(q_rows, db_rows, k=k, threshold=threshold, band_rows=band_rows, route=route))
+
+
+def write_nearest(path, q_ids, db_ids, row_off, col, dist):
+    """Header and "query id\tdatabase id\tdistance" rows of a CSR over the queries whose columns are database samples, query by
+    query, through the library's host formatter (csrc/tsv_out.hip)."""
+    from . import _lib as L
+    q_blob, q_off = _id_table(q_ids)
+    db_blob, db_off = _id_table(db_ids)
+    ro = np.ascontiguousarray(row_off, dtype=np.uint64)
+    c = np.ascontiguousarray(col, dtype=np.uint32)
+    d = np.ascontiguousarray(dist, dtype=np.int32)
+    if len(ro) != len(q_ids) + 1 or len(c) != len(d) or int(ro[-1]) != len(c):
+        raise ValueError("row_off holds one offset per query and one more, col and dist one entry per offset")
+    opt = lambda x: x.ctypes.data if len(x) else None          # noqa: E731
+    rc = L.load().snpgpu_write_nearest_tsv(path.encode(), q_blob, q_off.ctypes.data, len(q_ids), db_blob, db_off.ctypes.data, len(db_ids), ro.ctypes.data, opt(c), opt(d))
+    if rc == L.E_IO:
+        raise IOError("cannot write %s" % path)
+    if rc == L.E_ARG:
+        raise ValueError("a column names a sample outside the %d database ids, or the offsets do not rise from 0" % len(db_ids))
+    if rc != 0:
+        raise RuntimeError("snpgpu_write_nearest_tsv failed (%d)" % rc)
+
+
 def _write_tsv(path, layout, ids, mat):
     """distance.py:100-114 through the library's host formatter (csrc/tsv_out.hip): at 10 000 samples the pairwise file has
     10^8 lines, ~35 s of Python string formatting for 38 ms of kernel."""
@@ -403,6 +455,9 @@ def calculate_snp_distances(args):
     snp_list_file = getattr(args, "amdSnpListFile", None)
     linkage_kind = getattr(args, "amdLinkage", None)
     linkage_files = (getattr(args, "amdLinkageMergesFile", None), getattr(args, "amdLinkageDendrogramFile", None), getattr(args, "amdLinkageClustersFile", None))
+    query_file = getattr(args, "amdQueryFile", None)
+    nearest_file = getattr(args, "amdNearestFile", None)
+    nearest_count = getattr(args, "amdNearestCount", None)
     if utils.verify_existing_input_files("SNP matrix file", [input_file]) > 0:
         utils.global_error("Error: cannot calculate sequence distances without the snp matrix file.")
     if close_file and max_pair_distance is None:
@@ -425,11 +480,20 @@ def calculate_snp_distances(args):
         utils.global_error("Error: --amdLinkageClusters needs at least one threshold in --amdClusterThresholds.")
     if (max_pair_distance is not None and max_pair_distance < 0) or any(t < 0 for t in thresholds):
         utils.global_error("Error: a distance threshold cannot be negative.")
-    outputs = [f for f in (pairwise_file, matrix_file, close_file, clusters_file, mst_file, dendrogram_file, close_sites_file, mst_sites_file, user_sites_file) + linkage_files if f]
+    if bool(query_file) != bool(nearest_file):
+        utils.global_error("Error: --amdQuery and --amdNearest go together.")
+    if nearest_count is not None and not nearest_file:
+        utils.global_error("Error: --amdNearestCount needs --amdQuery and --amdNearest.")
+    if nearest_count is not None and nearest_count < 0:
+        utils.global_error("Error: --amdNearestCount cannot be negative.")
+    if query_file and utils.verify_existing_input_files("query file", [query_file]) > 0:
+        utils.global_error("Error: cannot find the nearest samples without the query file.")
+    outputs = [f for f in (pairwise_file, matrix_file, close_file, clusters_file, mst_file, dendrogram_file, close_sites_file, mst_sites_file, user_sites_file, nearest_file)
+               + linkage_files if f]
     if not outputs:
         utils.global_error("Error: no output file specified.")
 
-    sources = [input_file] + [f for f in (user_pairs_file, snp_list_file) if f and (close_sites_file or mst_sites_file or user_sites_file)]
+    sources = [input_file] + [f for f in (user_pairs_file, snp_list_file) if f and (close_sites_file or mst_sites_file or user_sites_file)] + ([query_file] if query_file else [])
     if not (args.forceFlag or any(utils.target_needs_rebuild(sources, f) for f in outputs)):
         utils.verbose_print("Distance files have already been freshly built.  Use the -f option to force a rebuild.")
         return
@@ -437,6 +501,12 @@ def calculate_snp_distances(args):
     file_ids, sym, lens = snp_matrix.load_matrix(input_file)
     utils.verbose_print("# %s %s" % (utils.timestamp(), "Calculating all pairwise distances"))
     from .device import default_device
+    if nearest_file:
+        # the queries against the database, on their own: this first form uploads and packs the database itself, whatever else is
+        # asked for, and the other outputs are computed as without it
+        _write_nearest_output(default_device, file_ids, sym, lens, query_file, nearest_file, nearest_count or 0, max_pair_distance)
+        if len(outputs) == 1:
+            return
     if close_sites_file or mst_sites_file or user_sites_file:
         _distances_with_sites(default_device, file_ids, sym, lens, snp_list_file, pairwise_file, matrix_file, close_file, max_pair_distance, clusters_file, thresholds,
                               mst_file, dendrogram_file, close_sites_file, mst_sites_file, user_pairs_file, user_sites_file, linkage_kind, linkage_files)
@@ -482,6 +552,18 @@ def calculate_snp_distances(args):
         write_mst(mst_file, ids, *tree)
     if dendrogram_file:
         write_dendrogram(dendrogram_file, ids, *tree)
+
+
+def _write_nearest_output(device_of, file_ids, sym, lens, query_file, nearest_file, count, max_pair_distance):
+    """--amdNearest: the inputs are checked before a device is asked for; nothing but the lists crosses the host link."""
+    db_ids, db_rows = _sorted_rows(file_ids, sym, lens)
+    q_file_ids, q_sym, q_lens = snp_matrix.load_matrix(query_file)
+    q_ids, q_rows = query_rows(q_file_ids, q_sym, q_lens, None if db_rows is None else db_rows.shape[1])
+    if db_rows is None or len(q_ids) == 0:                      # no pair at all: the header
+        write_nearest(nearest_file, q_ids, db_ids, np.zeros(len(q_ids) + 1, dtype=np.uint64), np.zeros(0, dtype=np.uint32), np.zeros(0, dtype=np.int32))
+        return
+    dev = device_of()
+    write_nearest(nearest_file, q_ids, db_ids, *dev.nearest(q_rows, db_rows, k=count, threshold=max_pair_distance))
 
 
 def _distances_with_sites(device_of, file_ids, sym, lens, snp_list_file, pairwise_file, matrix_file, close_file, max_pair_distance, clusters_file, thresholds,
