@@ -909,6 +909,50 @@ int  snpgpu_write_nearest_tsv(const char *path, const char *q_ids, const uint64_
                               const uint64_t *db_id_off, uint32_t n, const uint64_t *row_off, const uint32_t *col,
                               const int32_t *dist);
 
+/* ---- compared-site counts (csrc/compared.hip) ------------------------------------------------------------------------------
+ * Additive entries of ABI 7, like the ones above: at how many columns a pair was compared at all.  Compared(i, j) counts the
+ * columns at which both bytes, after upper-casing a-z, are in {A,C,G,T} — the predicate of the distance kernel
+ * (utils.py:1135-1165) without "and differ" — so Distance(i, j) <= Compared(i, j) <= min(Compared(i, i), Compared(j, j)),
+ * Compared(i, i) is sample i's own count of ACGT columns, and the matrix is symmetric.  int32, as the distance.
+ *
+ * snpgpu_valid_plane_dev: the `valid` words of the packed matrix of snpgpu_pack_matrix_dev (n_rows rows of
+ * snpgpu_packed_row_bytes(n_sites) bytes) as a dense plane: one uint32 per 32 sites, bit i of word w = column 32 w + i, row r at
+ * d_plane + r * snpgpu_valid_plane_row_bytes(n_sites) bytes — rows are padded to a multiple of 16 words (64 bytes).  Every byte of
+ * the n_rows rows is written, the padding words zero whatever lay there, and nothing behind the last row; no bit at or beyond
+ * n_sites is set whatever the packed matrix holds.  Both pointers 16-byte aligned.  n_rows or n_sites 0: nothing to do.
+ * Enqueued on the context's stream; nothing waits. */
+size_t snpgpu_valid_plane_row_bytes(uint32_t n_sites);
+int  snpgpu_valid_plane_dev(snpgpu_ctx *ctx, const void *d_packed, uint32_t n_rows, uint32_t n_sites, void *d_plane);
+/* snpgpu_compared_rect_dev: d_plane_q (q rows) and d_plane_db (n rows) are planes of snpgpu_valid_plane_dev over the same
+ * n_sites; d_out[i * out_stride + j] = Compared(query i, database sample j) for i < q, j < n (int32, out_stride >= n elements,
+ * 4-byte aligned) — the conventions of snpgpu_distance_rect_packed_dev: nothing is written beyond column n of a row or beyond
+ * row q.  The same plane twice with q == n is the symmetric matrix: the tiles of the upper triangle are computed and mirrored.
+ * Tiles of 128 x 128 pairs, no split of the word range for shapes of few tiles.  n_sites == 0 gives zeros.  Enqueued on the
+ * context's stream; nothing waits. */
+int  snpgpu_compared_rect_dev(snpgpu_ctx *ctx, const void *d_plane_q, uint32_t q, const void *d_plane_db, uint32_t n,
+                              uint32_t n_sites, int32_t *d_out, uint64_t out_stride);
+/* snpgpu_compared_pairs_dev: d_out[p] = Compared(row d_a[p] of plane a, row d_b[p] of plane b) for the n_pairs pairs of two
+ * device lists (any order, duplicates allowed; d_plane_b may be d_plane_a), without the matrix.  No atomic: the same input gives
+ * the same bytes.  SNPGPU_E_ARG, with nothing written, when a pair names a row >= n_a or >= n_b: the lists are checked first,
+ * and the call waits for the stream once, for that check. */
+int  snpgpu_compared_pairs_dev(snpgpu_ctx *ctx, const void *d_plane_a, uint32_t n_a, const void *d_plane_b, uint32_t n_b,
+                               uint32_t n_sites, const uint32_t *d_a, const uint32_t *d_b, uint64_t n_pairs, int32_t *d_out);
+/* Host forms: upload and pack the symbols (as snpgpu_distance), extract the plane, call the above and copy the result back.
+ * snpgpu_compared: the n x n matrix (row pitch n).  snpgpu_compared_pairs: out[p] for host lists over symbols_a (n_a x n_sites)
+ * and symbols_b (n_b x n_sites); a null symbols_b means both indices address symbols_a (n_b is ignored).  The indices are
+ * checked on the host: SNPGPU_E_ARG with nothing written. */
+int  snpgpu_compared(snpgpu_ctx *ctx, const uint8_t *symbols, uint32_t n, uint32_t n_sites, int32_t *out_matrix);
+int  snpgpu_compared_pairs(snpgpu_ctx *ctx, const uint8_t *symbols_a, uint32_t n_a, const uint8_t *symbols_b, uint32_t n_b,
+                           uint32_t n_sites, const uint32_t *a, const uint32_t *b, uint64_t n_pairs, int32_t *out);
+/* The text of pair lists with their counts (host code, the thread scheme and CPU budget of snpgpu_write_distance_tsv):
+ * "Seq1\tSeq2\tDistance\tCompared\n", then "id_a\tid_b\tdist\tcompared\n" per entry of the HOST arrays a[], b[], dist[],
+ * compared[] in the order given; a[] indexes the first id table (n_a ids), b[] the second (n_b ids; the same table may be given
+ * twice).  SNPGPU_E_ARG for an index outside its table or 2^32 rows and more; SNPGPU_E_IO when the file cannot be created or
+ * written. */
+int  snpgpu_write_pair_rows_tsv(const char *path, const char *a_ids, const uint64_t *a_id_off, uint32_t n_a, const char *b_ids,
+                                const uint64_t *b_id_off, uint32_t n_b, const uint32_t *a, const uint32_t *b,
+                                const int32_t *dist, const int32_t *compared, uint64_t n_rows);
+
 /* ---- the exchange steps of the sharded path: RCCL over xGMI, one process per GPU ------------------------
  * The reference fans out one process per sample (run.py:704-718, `run_array` with `max_processes`) over a shared file system
  * and has no exchange step; sharded over GPUs the hot path has three: C1, the all-gather of the per-rank SNP site keys

@@ -225,6 +225,13 @@ SIGNATURES = {
     "snpgpu_nearest": (C.c_int, [_P, _P, C.c_uint32, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, C.c_uint32, C.c_int, C.c_uint64, _P, _P, _P,
                                  C.POINTER(C.c_uint64), _P]),
     "snpgpu_write_nearest_tsv": (C.c_int, [C.c_char_p, _P, _P, C.c_uint32, _P, _P, C.c_uint32, _P, _P, _P]),
+    "snpgpu_valid_plane_row_bytes": (C.c_size_t, [C.c_uint32]),
+    "snpgpu_valid_plane_dev": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, _P]),
+    "snpgpu_compared_rect_dev": (C.c_int, [_P, _P, C.c_uint32, _P, C.c_uint32, C.c_uint32, _P, C.c_uint64]),
+    "snpgpu_compared_pairs_dev": (C.c_int, [_P, _P, C.c_uint32, _P, C.c_uint32, C.c_uint32, _P, _P, C.c_uint64, _P]),
+    "snpgpu_compared": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, _P]),
+    "snpgpu_compared_pairs": (C.c_int, [_P, _P, C.c_uint32, _P, C.c_uint32, C.c_uint32, _P, _P, C.c_uint64, _P]),
+    "snpgpu_write_pair_rows_tsv": (C.c_int, [C.c_char_p, _P, _P, C.c_uint32, _P, _P, C.c_uint32, _P, _P, _P, _P, C.c_uint64]),
     "snpgpu_dense_windows": (C.c_int, [_P, _P, _P, C.c_uint32, _P, _P, C.c_uint32, _P, _P, _P, C.POINTER(C.c_uint32)]),
     "snpgpu_merge_regions": (C.c_int, [_P, _P, _P, _P, C.c_uint32, _P, _P, _P, C.POINTER(C.c_uint32)]),
     "snpgpu_in_regions": (C.c_int, [_P, _P, _P, C.c_uint32, _P, _P, _P, C.c_uint32, _P]),

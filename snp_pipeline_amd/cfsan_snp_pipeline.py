@@ -225,6 +225,8 @@ def parse_argument_list(argv):
     sub.add_argument("--amdQuery", dest="amdQueryFile", type=str, default=None, metavar="FILE", help="Extension of this build: a second multi-fasta file of query samples with as many columns as the snp matrix; the samples of the snp matrix closest to each of them go to --amdNearest.  An id that is in both files is a sample like any other.")
     sub.add_argument("--amdNearest", dest="amdNearestFile", type=str, default=None, metavar="FILE", help="Extension of this build: output file with one Seq1 / Seq2 / Distance row per query sample of --amdQuery and sample of the snp matrix within --amdMaxPairDistance (when given), per query in ascending distance, ties in the order of the snp matrix's sorted ids, at most --amdNearestCount rows per query.  Computed on the device query by database: the matrix over all samples is not computed.")
     sub.add_argument("--amdNearestCount", dest="amdNearestCount", type=int, default=None, metavar="INT", help="Extension of this build: the largest number of rows per query in the --amdNearest file; 0, the default, keeps every row.")
+    sub.add_argument("--amdComparedMatrix", dest="amdComparedMatrixFile", type=str, default=None, metavar="FILE", help="Extension of this build: output file in the layout of --matrix whose entries are not distances but Compared: at how many columns both samples of the pair hold one of A, C, G, T (either case), the only columns the distance counts; the diagonal is each sample's own count.")
+    sub.add_argument("--amdCompared", dest="amdCompared", action="store_true", help="Extension of this build: the files of --amdClosePairs, --amdMst and --amdNearest carry a fourth column Compared, the number of columns at which both samples of the row hold one of A, C, G, T; the first three columns and the order of the rows stay as they are.")
     _common(sub)
     sub.set_defaults(func=distance.calculate_snp_distances, excepthook=utils.handle_global_exception)
 

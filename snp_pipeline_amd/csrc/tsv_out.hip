@@ -336,6 +336,33 @@ extern "C" int snpgpu_write_nearest_tsv(const char *path, const char *q_ids, con
     return write_row_blocks(path, q, n_entries, row_off, 19, header, size_rows, format);
 }
 
+// Pair lists with their compared-site counts (csrc/compared.hip): the rows of a close-pairs, tree or nearest file with a fourth
+// column; a[] names ids of the first table, b[] of the second.
+extern "C" int snpgpu_write_pair_rows_tsv(const char *path, const char *a_ids, const uint64_t *a_id_off, uint32_t n_a, const char *b_ids,
+                                          const uint64_t *b_id_off, uint32_t n_b, const uint32_t *a, const uint32_t *b, const int32_t *dist,
+                                          const int32_t *compared, uint64_t n_rows) {
+    if (!path || n_rows >> 32 || (n_rows && (!a || !b || !dist || !compared || !a_ids || !a_id_off || !b_ids || !b_id_off))) return SNPGPU_E_ARG;
+    for (uint64_t p = 0; p < n_rows; ++p)
+        if (a[p] >= n_a || b[p] >= n_b) return SNPGPU_E_ARG;
+    auto a_len = [&](uint32_t i) { return a_id_off[i + 1] - a_id_off[i]; };
+    auto b_len = [&](uint32_t j) { return b_id_off[j + 1] - b_id_off[j]; };
+    auto header = [&](auto &o) { o.put("Seq1\tSeq2\tDistance\tCompared\n", 28); };
+    auto size_rows = [&](uint32_t p0, uint32_t p1) {
+        uint64_t total = 0;
+        for (uint32_t p = p0; p < p1; ++p) total += a_len(a[p]) + b_len(b[p]) + digits_i32(dist[p]) + digits_i32(compared[p]) + 4;
+        return total;
+    };
+    auto format = [&](auto &o, uint32_t p0, uint32_t p1) {
+        for (uint32_t p = p0; p < p1 && !o.failed; ++p) {
+            o.put(a_ids + a_id_off[a[p]], (size_t)a_len(a[p])); o.put('\t');
+            o.put(b_ids + b_id_off[b[p]], (size_t)b_len(b[p])); o.put('\t');
+            o.put_i32(dist[p]); o.put('\t');
+            o.put_i32(compared[p]); o.put('\n');
+        }
+    };
+    return write_row_blocks(path, (uint32_t)n_rows, n_rows, nullptr, 28, header, size_rows, format);
+}
+
 extern "C" int snpgpu_write_clusters_tsv(const char *path, const char *ids, const uint64_t *id_off, uint32_t n, const int32_t *thresholds,
                                          uint32_t n_thresholds, const uint32_t *numbers) {
     const uint32_t k = n_thresholds;

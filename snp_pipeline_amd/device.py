@@ -1357,6 +1357,61 @@ class Device(object):
                 return csr + (mat,) if want_matrix else csr
             cap = int(out_n.value)
 
+    # ---- compared-site counts (additive to distance.py:93-106) ------------------------------------
+    def valid_plane_row_bytes(self, n_sites):
+        return int(self.lib.snpgpu_valid_plane_row_bytes(n_sites))
+
+    def valid_plane_dev(self, d_packed, n_rows, n_sites, d_plane):
+        """The ``valid`` words of a device packed matrix as a dense plane (rows of ``valid_plane_row_bytes(n_sites)`` bytes, the
+        padding words zero): what ``compared_rect_dev`` and ``compared_pairs_dev`` read."""
+        opt = lambda v: C.c_void_p(int(v)) if v else None     # noqa: E731
+        self._check(self.lib.snpgpu_valid_plane_dev(self.ctx, opt(d_packed), int(n_rows), int(n_sites), opt(d_plane)))
+
+    def compared_rect_dev(self, d_plane_q, q, d_plane_db, n, n_sites, d_out, out_stride=None):
+        """At how many columns each of the q rows of one device plane and each of the n rows of another both hold one of ACGT,
+        into the device int32 matrix d_out, row pitch out_stride elements (default n); nothing beyond column n of a row or beyond
+        row q is written.  The same plane twice with q == n: the symmetric matrix."""
+        opt = lambda v: C.c_void_p(int(v)) if v else None     # noqa: E731
+        self._check(self.lib.snpgpu_compared_rect_dev(self.ctx, opt(d_plane_q), int(q), opt(d_plane_db), int(n), int(n_sites), opt(d_out),
+                                                      int(n if out_stride is None else out_stride)))
+
+    def compared_pairs_dev(self, d_plane_a, n_a, d_plane_b, n_b, n_sites, d_a, d_b, n_pairs, d_out):
+        """d_out[p] (int32) = the count of ``compared_rect_dev`` for row d_a[p] of plane a and row d_b[p] of plane b, without the
+        matrix.  A pair that names a row outside its plane is refused before anything is written."""
+        opt = lambda v: C.c_void_p(int(v)) if v else None     # noqa: E731
+        self._check(self.lib.snpgpu_compared_pairs_dev(self.ctx, opt(d_plane_a), int(n_a), opt(d_plane_b), int(n_b), int(n_sites), opt(d_a), opt(d_b), int(n_pairs),
+                                                       opt(d_out)))
+
+    def compared(self, symbols):
+        """symbols: (n, s) uint8 array of sequence bytes.  Returns (n, n) int32: entry (i, j) is the number of columns at which
+        both samples hold one of ACGT (any case) — the columns the distance of the pair was taken over."""
+        sym = np.ascontiguousarray(symbols, dtype=np.uint8)
+        n, s = sym.shape
+        out = np.zeros((n, n), dtype=np.int32)
+        self._check(self.lib.snpgpu_compared(self.ctx, _ptr(sym) if sym.size else None, n, s, _ptr(out) if n else None))
+        return out
+
+    def compared_pairs(self, symbols_a, a, b, symbols_b=None):
+        """The entries (a[p], b[p]) of ``compared`` without the matrix: a indexes the rows of symbols_a, b those of symbols_b (None:
+        of symbols_a too).  Returns int32 [len(a)]."""
+        sa = np.ascontiguousarray(symbols_a, dtype=np.uint8)
+        sb = None if symbols_b is None else np.ascontiguousarray(symbols_b, dtype=np.uint8)
+        if sa.ndim != 2 or (sb is not None and (sb.ndim != 2 or (sa.shape[0] and sb.shape[0] and sa.shape[1] != sb.shape[1]))):
+            raise ValueError("the two matrices have %d and %d columns" % (sa.shape[-1], sb.shape[-1] if sb is not None else 0))
+        a = np.ascontiguousarray(a, dtype=np.uint32)
+        b = np.ascontiguousarray(b, dtype=np.uint32)
+        if a.ndim != 1 or a.shape != b.shape:
+            raise ValueError("a and b hold one row index per pair")
+        n_b = sa.shape[0] if sb is None else sb.shape[0]
+        if len(a) and (int(a.max()) >= sa.shape[0] or int(b.max()) >= n_b):
+            raise ValueError("a pair names a row outside the %d and %d rows of its matrices" % (sa.shape[0], n_b))
+        out = np.zeros(len(a), dtype=np.int32)
+        opt = lambda x: _ptr(x) if x is not None and x.size else None     # noqa: E731
+        if sa.shape[1] == 0:                                  # no columns: nothing was compared (the indices have been checked)
+            return out
+        self._check(self.lib.snpgpu_compared_pairs(self.ctx, opt(sa), sa.shape[0], opt(sb), n_b, sa.shape[1], opt(a), opt(b), len(a), opt(out)))
+        return out
+
     # ---- filter_regions ------------------------------------------------------------------------
     def dense_windows(self, positions, seg_off, max_snps, windows):
         pos = np.ascontiguousarray(positions, dtype=np.int64)

@@ -100,8 +100,40 @@ def _id_table(ids):
     return b"".join(names), off
 
 
-def write_close_pairs(path, ids, row_off, col, dist):
-    """Header and "id\tid\tdistance" rows of a CSR over ids, row by row, through the library's host formatter (csrc/tsv_out.hip)."""
+def write_pair_rows(path, a_ids, b_ids, a, b, dist, compared):
+    """Header and "id\tid\tdistance\tcompared" rows of pair lists in the order given (csrc/tsv_out.hip): a names ids of a_ids, b of
+    b_ids — the rows of a close-pairs, tree or nearest file with the fourth column of --amdCompared."""
+    from . import _lib as L
+    a_blob, a_off = _id_table(a_ids)
+    b_blob, b_off = _id_table(b_ids)
+    a = np.ascontiguousarray(a, dtype=np.uint32)
+    b = np.ascontiguousarray(b, dtype=np.uint32)
+    d = np.ascontiguousarray(dist, dtype=np.int32)
+    c = np.ascontiguousarray(compared, dtype=np.int32)
+    if not len(a) == len(b) == len(d) == len(c):
+        raise ValueError("a, b, dist and compared hold one entry per row")
+    opt = lambda x: x.ctypes.data if len(x) else None          # noqa: E731
+    rc = L.load().snpgpu_write_pair_rows_tsv(path.encode(), a_blob, a_off.ctypes.data, len(a_ids), b_blob, b_off.ctypes.data, len(b_ids), opt(a), opt(b), opt(d), opt(c),
+                                             len(a))
+    if rc == L.E_IO:
+        raise IOError("cannot write %s" % path)
+    if rc == L.E_ARG:
+        raise ValueError("a row names a sample outside the %d and %d ids" % (len(a_ids), len(b_ids)))
+    if rc != 0:
+        raise RuntimeError("snpgpu_write_pair_rows_tsv failed (%d)" % rc)
+
+
+def rows_of_csr(row_off):
+    """The row of every entry of a CSR."""
+    row_off = np.asarray(row_off, dtype=np.int64)
+    return np.repeat(np.arange(len(row_off) - 1, dtype=np.uint32), np.diff(row_off))
+
+
+def write_close_pairs(path, ids, row_off, col, dist, compared=None):
+    """Header and "id\tid\tdistance" rows of a CSR over ids, row by row, through the library's host formatter (csrc/tsv_out.hip);
+    compared (one count per entry): a fourth column."""
+    if compared is not None:
+        return write_pair_rows(path, ids, ids, rows_of_csr(row_off), col, dist, compared)
     from . import _lib as L
     blob, off = _id_table(ids)
     ro = np.ascontiguousarray(row_off, dtype=np.uint64)
@@ -127,10 +159,11 @@ def write_clusters(path, ids, thresholds, numbers):
         raise RuntimeError("snpgpu_write_clusters_tsv failed (%d)" % rc)
 
 
-def write_pairs_and_clusters(dev, ids, row_off, col, dist, pairs_file, max_pair_distance, clusters_file, thresholds):
-    """The two additive outputs from one CSR that holds at least every entry within the largest threshold asked for."""
+def write_pairs_and_clusters(dev, ids, row_off, col, dist, pairs_file, max_pair_distance, clusters_file, thresholds, pairs_compared=None):
+    """The two additive outputs from one CSR that holds at least every entry within the largest threshold asked for;
+    pairs_compared: the fourth column of the pairs file, one count per entry within max_pair_distance."""
     if pairs_file:
-        write_close_pairs(pairs_file, ids, *filter_pairs(row_off, col, dist, max_pair_distance))
+        write_close_pairs(pairs_file, ids, *filter_pairs(row_off, col, dist, max_pair_distance), compared=pairs_compared)
     if clusters_file:
         thresholds = cluster_thresholds(thresholds)
         numbers, _ = dev.clusters(len(ids), row_off, col, dist, thresholds)
@@ -184,8 +217,10 @@ def _write_tree(entry, path, ids, u, v, dist):
         raise RuntimeError("%s failed (%d)" % (entry, rc))
 
 
-def write_mst(path, ids, u, v, dist):
-    """Header and one "id\tid\tdistance" row per tree edge, in the order given."""
+def write_mst(path, ids, u, v, dist, compared=None):
+    """Header and one "id\tid\tdistance" row per tree edge, in the order given; compared (one count per edge): a fourth column."""
+    if compared is not None:
+        return write_pair_rows(path, ids, ids, u, v, dist, compared)
     _write_tree("snpgpu_write_mst_tsv", path, ids, u, v, dist)
 
 
@@ -388,9 +423,13 @@ def nearest_of_matrices(dev, db_file_ids, db_sym, db_lens, q_file_ids, q_sym, q_
     return (q_ids, db_ids) + tuple(dev.nearest(q_rows, db_rows, k=k, threshold=threshold, band_rows=band_rows, route=route))
 
 
-def write_nearest(path, q_ids, db_ids, row_off, col, dist):
+def write_nearest(path, q_ids, db_ids, row_off, col, dist, compared=None):
     """Header and "query id\tdatabase id\tdistance" rows of a CSR over the queries whose columns are database samples, query by
-    query, through the library's host formatter (csrc/tsv_out.hip)."""
+    query, through the library's host formatter (csrc/tsv_out.hip); compared (one count per entry): a fourth column."""
+    if compared is not None:
+        if len(row_off) != len(q_ids) + 1:
+            raise ValueError("row_off holds one offset per query and one more")
+        return write_pair_rows(path, q_ids, db_ids, rows_of_csr(row_off), col, dist, compared)
     from . import _lib as L
     q_blob, q_off = _id_table(q_ids)
     db_blob, db_off = _id_table(db_ids)
@@ -423,6 +462,35 @@ def _write_tsv(path, layout, ids, mat):
         raise IOError("cannot write %s" % path)
     if rc != 0:
         raise RuntimeError("snpgpu_write_distance_tsv failed (%d)" % rc)
+
+
+def compared_of_matrix(device_of, file_ids, sym, lens):
+    """As distance_of_matrix, but entry (i, j) is Compared: at how many columns both samples hold one of ACGT (either case) — the
+    columns a distance counts over; the diagonal is each sample's own count (csrc/compared.hip).  device_of: asked only when there
+    is something to count."""
+    ids, rows = _sorted_rows(file_ids, sym, lens)
+    n = len(ids)
+    if rows is None or rows.shape[1] == 0:
+        return ids, np.zeros((n, n), dtype=np.int32)
+    return ids, device_of().compared(rows)
+
+
+def compared_columns(dev, rows, pairs_csr, tree):
+    """--amdCompared: the fourth column of the close-pairs file (pairs_csr: its (row_off, col, dist), or None) and of the tree
+    file (tree: its (u, v, dist), or None) from one upload, pack and plane of the sorted rows: (per entry, per edge), None where
+    not asked for.  The pairs are the host lists the other outputs returned; the n x n matrix is never formed."""
+    lists = []
+    if pairs_csr is not None:
+        lists.append((rows_of_csr(pairs_csr[0]), np.asarray(pairs_csr[1], dtype=np.uint32)))
+    if tree is not None:
+        lists.append((np.asarray(tree[0], dtype=np.uint32), np.asarray(tree[1], dtype=np.uint32)))
+    total = sum(len(a) for a, _ in lists)
+    if total == 0 or rows is None:
+        counts = np.zeros(total, dtype=np.int32)
+    else:
+        counts = dev.compared_pairs(rows, np.concatenate([a for a, _ in lists]), np.concatenate([b for _, b in lists]))
+    first = len(lists[0][0]) if pairs_csr is not None else 0
+    return (counts[:first] if pairs_csr is not None else None), (counts[first:] if tree is not None else None)
 
 
 def write_pairwise(path, ids, mat):
@@ -458,6 +526,8 @@ def calculate_snp_distances(args):
     query_file = getattr(args, "amdQueryFile", None)
     nearest_file = getattr(args, "amdNearestFile", None)
     nearest_count = getattr(args, "amdNearestCount", None)
+    compared_matrix_file = getattr(args, "amdComparedMatrixFile", None)
+    with_compared = bool(getattr(args, "amdCompared", False))
     if utils.verify_existing_input_files("SNP matrix file", [input_file]) > 0:
         utils.global_error("Error: cannot calculate sequence distances without the snp matrix file.")
     if close_file and max_pair_distance is None:
@@ -488,8 +558,10 @@ def calculate_snp_distances(args):
         utils.global_error("Error: --amdNearestCount cannot be negative.")
     if query_file and utils.verify_existing_input_files("query file", [query_file]) > 0:
         utils.global_error("Error: cannot find the nearest samples without the query file.")
-    outputs = [f for f in (pairwise_file, matrix_file, close_file, clusters_file, mst_file, dendrogram_file, close_sites_file, mst_sites_file, user_sites_file, nearest_file)
-               + linkage_files if f]
+    if with_compared and not (close_file or mst_file or nearest_file):
+        utils.global_error("Error: --amdCompared needs at least one of --amdClosePairs, --amdMst and --amdNearest.")
+    outputs = [f for f in (pairwise_file, matrix_file, close_file, clusters_file, mst_file, dendrogram_file, close_sites_file, mst_sites_file, user_sites_file, nearest_file,
+                           compared_matrix_file) + linkage_files if f]
     if not outputs:
         utils.global_error("Error: no output file specified.")
 
@@ -501,15 +573,21 @@ def calculate_snp_distances(args):
     file_ids, sym, lens = snp_matrix.load_matrix(input_file)
     utils.verbose_print("# %s %s" % (utils.timestamp(), "Calculating all pairwise distances"))
     from .device import default_device
+    on_their_own = 0
     if nearest_file:
         # the queries against the database, on their own: this first form uploads and packs the database itself, whatever else is
         # asked for, and the other outputs are computed as without it
-        _write_nearest_output(default_device, file_ids, sym, lens, query_file, nearest_file, nearest_count or 0, max_pair_distance)
-        if len(outputs) == 1:
-            return
+        _write_nearest_output(default_device, file_ids, sym, lens, query_file, nearest_file, nearest_count or 0, max_pair_distance, with_compared)
+        on_their_own += 1
+    if compared_matrix_file:
+        # likewise on its own: one more upload and pack beside the other outputs, and the matrix in the layout of -m
+        write_matrix(compared_matrix_file, *compared_of_matrix(default_device, file_ids, sym, lens))
+        on_their_own += 1
+    if len(outputs) == on_their_own:
+        return
     if close_sites_file or mst_sites_file or user_sites_file:
         _distances_with_sites(default_device, file_ids, sym, lens, snp_list_file, pairwise_file, matrix_file, close_file, max_pair_distance, clusters_file, thresholds,
-                              mst_file, dendrogram_file, close_sites_file, mst_sites_file, user_pairs_file, user_sites_file, linkage_kind, linkage_files)
+                              mst_file, dendrogram_file, close_sites_file, mst_sites_file, user_pairs_file, user_sites_file, linkage_kind, linkage_files, with_compared)
         return
     dev = default_device()
     mat = None
@@ -546,29 +624,37 @@ def calculate_snp_distances(args):
         write_pairwise(pairwise_file, ids, mat)
     if matrix_file:
         write_matrix(matrix_file, ids, mat)
+    pairs_compared = tree_compared = None
+    if with_compared:
+        pairs_compared, tree_compared = compared_columns(dev, _sorted_rows(file_ids, sym, lens)[1], filter_pairs(row_off, col, dist, max_pair_distance) if close_file else None,
+                                                         tree if mst_file else None)
     if close_file or clusters_file:
-        write_pairs_and_clusters(dev, ids, row_off, col, dist, close_file, max_pair_distance, clusters_file, thresholds)
+        write_pairs_and_clusters(dev, ids, row_off, col, dist, close_file, max_pair_distance, clusters_file, thresholds, pairs_compared)
     if mst_file:
-        write_mst(mst_file, ids, *tree)
+        write_mst(mst_file, ids, *tree, compared=tree_compared)
     if dendrogram_file:
         write_dendrogram(dendrogram_file, ids, *tree)
 
 
-def _write_nearest_output(device_of, file_ids, sym, lens, query_file, nearest_file, count, max_pair_distance):
-    """--amdNearest: the inputs are checked before a device is asked for; nothing but the lists crosses the host link."""
+def _write_nearest_output(device_of, file_ids, sym, lens, query_file, nearest_file, count, max_pair_distance, with_compared=False):
+    """--amdNearest: the inputs are checked before a device is asked for; nothing but the lists crosses the host link.
+    with_compared: the fourth column, the pairs (query row, database row) over the two matrices."""
     db_ids, db_rows = _sorted_rows(file_ids, sym, lens)
     q_file_ids, q_sym, q_lens = snp_matrix.load_matrix(query_file)
     q_ids, q_rows = query_rows(q_file_ids, q_sym, q_lens, None if db_rows is None else db_rows.shape[1])
     if db_rows is None or len(q_ids) == 0:                      # no pair at all: the header
-        write_nearest(nearest_file, q_ids, db_ids, np.zeros(len(q_ids) + 1, dtype=np.uint64), np.zeros(0, dtype=np.uint32), np.zeros(0, dtype=np.int32))
+        write_nearest(nearest_file, q_ids, db_ids, np.zeros(len(q_ids) + 1, dtype=np.uint64), np.zeros(0, dtype=np.uint32), np.zeros(0, dtype=np.int32),
+                      compared=np.zeros(0, dtype=np.int32) if with_compared else None)
         return
     dev = device_of()
-    write_nearest(nearest_file, q_ids, db_ids, *dev.nearest(q_rows, db_rows, k=count, threshold=max_pair_distance))
+    row_off, col, dist = dev.nearest(q_rows, db_rows, k=count, threshold=max_pair_distance)
+    compared = dev.compared_pairs(q_rows, rows_of_csr(row_off), col, db_rows) if with_compared else None
+    write_nearest(nearest_file, q_ids, db_ids, row_off, col, dist, compared=compared)
 
 
 def _distances_with_sites(device_of, file_ids, sym, lens, snp_list_file, pairwise_file, matrix_file, close_file, max_pair_distance, clusters_file, thresholds,
                           mst_file, dendrogram_file, close_sites_file, mst_sites_file, user_pairs_file, user_sites_file, linkage_kind=None,
-                          linkage_files=(None, None, None)):
+                          linkage_files=(None, None, None), with_compared=False):
     """calculate_snp_distances when the differing sites of some pairs are asked for: the symbols are uploaded and packed once; the
     matrix is computed once, and only when a tree, a threshold or a table needs it; the packed matrix stays on the device until
     every pair list has been answered from it.  The n x n matrix comes to the host for -p / -m alone."""
@@ -609,10 +695,14 @@ def _distances_with_sites(device_of, file_ids, sym, lens, snp_list_file, pairwis
             write_pairwise(pairwise_file, ids, mat)
         if matrix_file:
             write_matrix(matrix_file, ids, mat)
+        pairs_compared = tree_compared = None
+        if with_compared:                                      # (not done: reuse of the kept packed matrix — one more upload and pack)
+            pairs_compared, tree_compared = compared_columns(dev, rows if n else None, filter_pairs(csr[0], csr[1], csr[2], max_pair_distance) if close_file else None,
+                                                             tree if mst_file else None)
         if close_file or clusters_file:
-            write_pairs_and_clusters(dev, ids, csr[0], csr[1], csr[2], close_file, max_pair_distance, clusters_file, thresholds)
+            write_pairs_and_clusters(dev, ids, csr[0], csr[1], csr[2], close_file, max_pair_distance, clusters_file, thresholds, pairs_compared)
         if mst_file:
-            write_mst(mst_file, ids, *tree)
+            write_mst(mst_file, ids, *tree, compared=tree_compared)
         if dendrogram_file:
             write_dendrogram(dendrogram_file, ids, *tree)
         if close_sites_file:
