@@ -953,6 +953,56 @@ int  snpgpu_write_pair_rows_tsv(const char *path, const char *a_ids, const uint6
                                 const uint64_t *b_id_off, uint32_t n_b, const uint32_t *a, const uint32_t *b,
                                 const int32_t *dist, const int32_t *compared, uint64_t n_rows);
 
+/* ---- per-site allele counts and cluster-defining SNPs (csrc/cluster_snps.hip) --------------------------------------------
+ * Additive entries of ABI 7.  A byte is a base iff, after upper-casing, it is one of ACGT (the distance's predicate); the bases
+ * are numbered A0 C1 G2 T3.  d_packed is the packed matrix of snpgpu_pack_matrix_dev (rows of snpgpu_packed_row_bytes(n_sites)
+ * bytes, 16-byte aligned); every call reads it once.
+ *
+ * snpgpu_site_counts_dev: d_counts[4 s + b] (int32) = the rows that hold base b at column s, in either case; exactly 4 n_sites
+ * elements are written (n_rows - their sum is what a column holds besides bases).  n_rows == 0 gives zeros, n_sites == 0
+ * nothing.  Integer atomic adds into the counts: the sums do not depend on their order.  Enqueued on the context's stream;
+ * nothing waits.  (The host form is not called snpgpu_site_counts: that is the per-position record of the call kernels.) */
+int  snpgpu_site_counts_dev(snpgpu_ctx *ctx, const void *d_packed, uint32_t n_rows, uint32_t n_sites, int32_t *d_counts);
+/* Host form: uploads and packs the symbols (as snpgpu_distance), calls the above and copies the counts back. */
+int  snpgpu_site_counts_host(snpgpu_ctx *ctx, const uint8_t *symbols, uint32_t n_rows, uint32_t n_sites, int32_t *out_counts);
+/* snpgpu_cluster_snps_dev: d_labels[n_rows] names every row's cluster, 1 ... n_clusters (a number without rows is legal).
+ * (cluster c, column s, base b) is an entry iff at least one member of c holds b at s, no member holds another base there
+ * (members without a base at s are allowed), and no row outside c holds b at s.  The entries come by cluster ascending, then
+ * column ascending — at most four clusters have an entry at a column —: d_cluster_off[n_clusters + 1] (uint64) the offsets of
+ * the clusters, d_site[] the 0-based columns, d_base[] 0..3, d_members[] how many members of the cluster hold the base.  No
+ * atomic decides a position or an order-dependent value: the same input gives the same bytes.  The capacity protocol of
+ * snpgpu_pair_sites_dev: *out_n (host) is always set; when it exceeds `capacity` nothing else is written; capacity 0 only
+ * counts.  The call waits for the stream: for the check of the labels, for the count, and at its end (it frees its workspace).
+ * SNPGPU_E_ARG, with *out_n 0 and nothing written, when a label is 0 or above n_clusters.  n_rows == 0, n_sites == 0 and
+ * n_clusters == 0 are legal and give no entry. */
+int  snpgpu_cluster_snps_dev(snpgpu_ctx *ctx, const void *d_packed, uint32_t n_rows, uint32_t n_sites, const uint32_t *d_labels,
+                             uint32_t n_clusters, uint64_t capacity, uint64_t *d_cluster_off, uint32_t *d_site, uint8_t *d_base,
+                             uint32_t *d_members, uint64_t *out_n);
+/* Host form: one upload and pack of the symbols, one count of the sites, then one labelling after another: labels[t][n_rows]
+ * with n_clusters[t] clusters, t < n_labellings.  The entries of the labellings follow one another; out_cluster_off holds
+ * n_clusters[t] + 1 offsets per labelling, one block after another, each counting from the first entry of the call (so a
+ * block's first offset is the number of entries before its labelling).  The capacity protocol above over the sum; the labels
+ * are checked on the host. */
+int  snpgpu_cluster_snps(snpgpu_ctx *ctx, const uint8_t *symbols, uint32_t n_rows, uint32_t n_sites, const uint32_t *labels,
+                         const uint32_t *n_clusters, uint32_t n_labellings, uint64_t capacity, uint64_t *out_cluster_off,
+                         uint32_t *out_site, uint8_t *out_base, uint32_t *out_members, uint64_t *out_n);
+/* The text (host code).  snpgpu_write_site_counts_tsv: "Site\tA\tC\tG\tT\tOther\n", then per column its 1-based number, the
+ * four counts[4 s + b] and n_rows minus their sum.  With a site table (chrom_names / chrom_off / chrom_of_site / pos_of_site as
+ * for snpgpu_write_pair_sites_tsv, one entry per column): "Chrom\tPos\tA\tC\tG\tT\tOther\n" and the contig name and position in
+ * place of the number.  SNPGPU_E_ARG when a column's counts are negative or sum to more than n_rows.
+ * snpgpu_write_cluster_snps_tsv: the HOST arrays of snpgpu_cluster_snps with thresholds[t] naming labelling t and
+ * sizes[] holding the sizes of the clusters, n_clusters[t] per labelling, one block after another:
+ * "Threshold\tCluster\tSite\tBase\tMembers\tSize\n", then per entry the threshold, the 1-based cluster, the 1-based column (or,
+ * with a site table, Chrom and Pos), the base as an upper-case letter, the members and the size.  n_sites: the columns of the
+ * matrix; SNPGPU_E_ARG for a site at or above it, a base above 3 or offsets that do not rise from 0.  SNPGPU_E_IO when the file
+ * cannot be created or written. */
+int  snpgpu_write_site_counts_tsv(const char *path, const int32_t *counts, uint32_t n_sites, uint32_t n_rows, const char *chrom_names,
+                                  const uint64_t *chrom_off, const uint32_t *chrom_of_site, const uint64_t *pos_of_site);
+int  snpgpu_write_cluster_snps_tsv(const char *path, const int32_t *thresholds, const uint32_t *n_clusters, uint32_t n_labellings,
+                                   const uint64_t *cluster_off, const uint32_t *sizes, const uint32_t *site, const uint8_t *base,
+                                   const uint32_t *members, uint32_t n_sites, const char *chrom_names, const uint64_t *chrom_off,
+                                   const uint32_t *chrom_of_site, const uint64_t *pos_of_site);
+
 /* ---- the exchange steps of the sharded path: RCCL over xGMI, one process per GPU ------------------------
  * The reference fans out one process per sample (run.py:704-718, `run_array` with `max_processes`) over a shared file system
  * and has no exchange step; sharded over GPUs the hot path has three: C1, the all-gather of the per-rank SNP site keys

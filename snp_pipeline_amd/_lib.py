@@ -232,6 +232,12 @@ SIGNATURES = {
     "snpgpu_compared": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, _P]),
     "snpgpu_compared_pairs": (C.c_int, [_P, _P, C.c_uint32, _P, C.c_uint32, C.c_uint32, _P, _P, C.c_uint64, _P]),
     "snpgpu_write_pair_rows_tsv": (C.c_int, [C.c_char_p, _P, _P, C.c_uint32, _P, _P, C.c_uint32, _P, _P, _P, _P, C.c_uint64]),
+    "snpgpu_site_counts_dev": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, _P]),
+    "snpgpu_site_counts_host": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, _P]),
+    "snpgpu_cluster_snps_dev": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, _P, C.c_uint32, C.c_uint64, _P, _P, _P, _P, C.POINTER(C.c_uint64)]),
+    "snpgpu_cluster_snps": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, _P, _P, C.c_uint32, C.c_uint64, _P, _P, _P, _P, C.POINTER(C.c_uint64)]),
+    "snpgpu_write_site_counts_tsv": (C.c_int, [C.c_char_p, _P, C.c_uint32, C.c_uint32, _P, _P, _P, _P]),
+    "snpgpu_write_cluster_snps_tsv": (C.c_int, [C.c_char_p, _P, _P, C.c_uint32, _P, _P, _P, _P, _P, C.c_uint32, _P, _P, _P, _P]),
     "snpgpu_dense_windows": (C.c_int, [_P, _P, _P, C.c_uint32, _P, _P, C.c_uint32, _P, _P, _P, C.POINTER(C.c_uint32)]),
     "snpgpu_merge_regions": (C.c_int, [_P, _P, _P, _P, C.c_uint32, _P, _P, _P, C.POINTER(C.c_uint32)]),
     "snpgpu_in_regions": (C.c_int, [_P, _P, _P, C.c_uint32, _P, _P, _P, C.c_uint32, _P]),

@@ -226,6 +226,8 @@ def parse_argument_list(argv):
     sub.add_argument("--amdNearest", dest="amdNearestFile", type=str, default=None, metavar="FILE", help="Extension of this build: output file with one Seq1 / Seq2 / Distance row per query sample of --amdQuery and sample of the snp matrix within --amdMaxPairDistance (when given), per query in ascending distance, ties in the order of the snp matrix's sorted ids, at most --amdNearestCount rows per query.  Computed on the device query by database: the matrix over all samples is not computed.")
     sub.add_argument("--amdNearestCount", dest="amdNearestCount", type=int, default=None, metavar="INT", help="Extension of this build: the largest number of rows per query in the --amdNearest file; 0, the default, keeps every row.")
     sub.add_argument("--amdComparedMatrix", dest="amdComparedMatrixFile", type=str, default=None, metavar="FILE", help="Extension of this build: output file in the layout of --matrix whose entries are not distances but Compared: at how many columns both samples of the pair hold one of A, C, G, T (either case), the only columns the distance counts; the diagonal is each sample's own count.")
+    sub.add_argument("--amdSiteCounts", dest="amdSiteCountsFile", type=str, default=None, metavar="FILE", help="Extension of this build: output file with one Site / A / C / G / T / Other row per column of the snp matrix: how many samples hold each base there (either case) and how many hold anything else; with --amdSnpList, Chrom and Pos in place of Site.")
+    sub.add_argument("--amdClusterSnps", dest="amdClusterSnpsFile", type=str, default=None, metavar="FILE", help="Extension of this build: output file with the SNPs that define the single-linkage clusters of --amdClusters at each threshold of --amdClusterThresholds: one Threshold / Cluster / Site / Base / Members / Size row per column and base that at least one member of the cluster holds, no member contradicts with another base and no sample outside the cluster holds; Members of the Size members hold it, the others hold no base there.  With --amdSnpList, Chrom and Pos in place of Site.")
     sub.add_argument("--amdCompared", dest="amdCompared", action="store_true", help="Extension of this build: the files of --amdClosePairs, --amdMst and --amdNearest carry a fourth column Compared, the number of columns at which both samples of the row hold one of A, C, G, T; the first three columns and the order of the rows stay as they are.")
     _common(sub)
     sub.set_defaults(func=distance.calculate_snp_distances, excepthook=utils.handle_global_exception)

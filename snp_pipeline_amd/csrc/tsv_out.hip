@@ -550,6 +550,99 @@ extern "C" int snpgpu_write_pair_sites_tsv(const char *path, const char *ids, co
     return write_row_blocks(path, (uint32_t)n_pairs, n_entries, pair_off, header_bytes, header, size_rows, format);
 }
 
+// ---- per-site allele counts and cluster-defining SNPs (additive: the arrays of csrc/cluster_snps.hip as text) ----
+namespace {
+struct SiteTable {
+    const char *names;
+    const uint64_t *off;
+    const uint32_t *chrom_of;
+    const uint64_t *pos_of;
+    bool given, ok;
+    SiteTable(const char *n, const uint64_t *o, const uint32_t *c, const uint64_t *p) : names(n), off(o), chrom_of(c), pos_of(p) {
+        given = n || o || c || p;
+        ok = !given || (o && c && p);
+    }
+    // the column as the files name it: its 1-based number, or contig name and position
+    void put(FileOut &o, uint32_t s) const {
+        if (!given) { put_u64(o, (uint64_t)s + 1); return; }
+        const uint32_t c = chrom_of[s];
+        o.put(names + off[c], (size_t)(off[c + 1] - off[c])); o.put('\t');
+        put_u64(o, pos_of[s]);
+    }
+};
+}  // namespace
+
+extern "C" int snpgpu_write_site_counts_tsv(const char *path, const int32_t *counts, uint32_t n_sites, uint32_t n_rows, const char *chrom_names, const uint64_t *chrom_off,
+                                            const uint32_t *chrom_of_site, const uint64_t *pos_of_site) {
+    const SiteTable table(chrom_names, chrom_off, chrom_of_site, pos_of_site);
+    if (!path || (n_sites && !counts) || !table.ok || (table.given && n_sites && !chrom_names)) return SNPGPU_E_ARG;
+    for (uint32_t s = 0; s < n_sites; ++s) {
+        uint64_t sum = 0;
+        for (int b = 0; b < 4; ++b) {
+            if (counts[4 * (size_t)s + b] < 0) return SNPGPU_E_ARG;
+            sum += (uint64_t)counts[4 * (size_t)s + b];
+        }
+        if (sum > n_rows) return SNPGPU_E_ARG;
+    }
+    FileOut o(path);
+    if (o.failed) return SNPGPU_E_IO;
+    if (table.given) o.put("Chrom\tPos\tA\tC\tG\tT\tOther\n", 24);
+    else o.put("Site\tA\tC\tG\tT\tOther\n", 19);
+    for (uint32_t s = 0; s < n_sites && !o.failed; ++s) {
+        table.put(o, s);
+        uint64_t sum = 0;
+        for (int b = 0; b < 4; ++b) {
+            o.put('\t');
+            put_u64(o, (uint64_t)counts[4 * (size_t)s + b]);
+            sum += (uint64_t)counts[4 * (size_t)s + b];
+        }
+        o.put('\t');
+        put_u64(o, n_rows - sum);
+        o.put('\n');
+    }
+    return o.finish();
+}
+
+extern "C" int snpgpu_write_cluster_snps_tsv(const char *path, const int32_t *thresholds, const uint32_t *n_clusters, uint32_t n_labellings, const uint64_t *cluster_off,
+                                             const uint32_t *sizes, const uint32_t *site, const uint8_t *base, const uint32_t *members, uint32_t n_sites,
+                                             const char *chrom_names, const uint64_t *chrom_off, const uint32_t *chrom_of_site, const uint64_t *pos_of_site) {
+    const SiteTable table(chrom_names, chrom_off, chrom_of_site, pos_of_site);
+    if (!path || !table.ok || (n_labellings && (!thresholds || !n_clusters || !cluster_off))) return SNPGPU_E_ARG;
+    uint64_t at = 0;                                                 // the offsets rise from 0 through every block
+    size_t o_off = 0, o_size = 0;
+    for (uint32_t t = 0; t < n_labellings; ++t) {
+        if (n_clusters[t] && !sizes) return SNPGPU_E_ARG;
+        if (cluster_off[o_off] != at) return SNPGPU_E_ARG;
+        for (uint32_t c = 0; c < n_clusters[t]; ++c) {
+            if (cluster_off[o_off + c + 1] < cluster_off[o_off + c]) return SNPGPU_E_ARG;
+        }
+        at = cluster_off[o_off + n_clusters[t]];
+        o_off += (size_t)n_clusters[t] + 1;
+    }
+    if (at && (!site || !base || !members || (table.given && !chrom_names))) return SNPGPU_E_ARG;
+    for (uint64_t e = 0; e < at; ++e)
+        if (site[e] >= n_sites || base[e] > 3) return SNPGPU_E_ARG;
+    FileOut o(path);
+    if (o.failed) return SNPGPU_E_IO;
+    if (table.given) o.put("Threshold\tCluster\tChrom\tPos\tBase\tMembers\tSize\n", 46);
+    else o.put("Threshold\tCluster\tSite\tBase\tMembers\tSize\n", 41);
+    o_off = 0;
+    for (uint32_t t = 0; t < n_labellings; ++t) {
+        for (uint32_t c = 0; c < n_clusters[t] && !o.failed; ++c)
+            for (uint64_t e = cluster_off[o_off + c]; e < cluster_off[o_off + c + 1]; ++e) {
+                o.put_i32(thresholds[t]); o.put('\t');
+                put_u64(o, (uint64_t)c + 1); o.put('\t');
+                table.put(o, site[e]); o.put('\t');
+                o.put("ACGT"[base[e]]); o.put('\t');
+                put_u64(o, members[e]); o.put('\t');
+                put_u64(o, sizes[o_size + c]); o.put('\n');
+            }
+        o_off += (size_t)n_clusters[t] + 1;
+        o_size += n_clusters[t];
+    }
+    return o.finish();
+}
+
 // ---- complete- and average-linkage trees (additive: the merges of csrc/linkage.hip as text; the arithmetic is linkage_host.h) ----
 namespace {
 // millionths as the integer part and, when the fraction is not zero, "." and its six digits without trailing zeros

@@ -1412,6 +1412,68 @@ class Device(object):
         self._check(self.lib.snpgpu_compared_pairs(self.ctx, opt(sa), sa.shape[0], opt(sb), n_b, sa.shape[1], opt(a), opt(b), len(a), opt(out)))
         return out
 
+    # ---- per-site allele counts and cluster-defining SNPs (additive to distance.py:93-106) --------
+    def site_counts_dev(self, d_packed, n_rows, n_sites, d_counts):
+        """d_counts[n_sites][4] (int32) = how many rows of a device packed matrix hold A, C, G, T (either case) at each column;
+        enqueued, nothing waits."""
+        opt = lambda v: C.c_void_p(int(v)) if v else None     # noqa: E731
+        self._check(self.lib.snpgpu_site_counts_dev(self.ctx, opt(d_packed), int(n_rows), int(n_sites), opt(d_counts)))
+
+    def site_counts(self, symbols):
+        """symbols: (n, s) uint8 array of sequence bytes.  Returns (s, 4) int32: the rows that hold A, C, G, T at each column."""
+        sym = np.ascontiguousarray(symbols, dtype=np.uint8)
+        n, s = sym.shape
+        out = np.zeros((s, 4), dtype=np.int32)
+        self._check(self.lib.snpgpu_site_counts_host(self.ctx, _ptr(sym) if sym.size else None, n, s, _ptr(out) if s else None))
+        return out
+
+    def cluster_snps_dev(self, d_packed, n_rows, n_sites, d_labels, n_clusters, capacity=0, d_cluster_off=0, d_site=0, d_base=0, d_members=0):
+        """The cluster-defining SNPs of one labelling (d_labels: uint32 [n_rows], 1 ... n_clusters) of the rows of a device packed
+        matrix: the (cluster, column, base) at which some member holds the base, no member another, and no row outside the cluster
+        the same — by cluster, then column: d_cluster_off[n_clusters + 1] (uint64), d_site[] (uint32), d_base[] (uint8, A0 C1 G2
+        T3), d_members[] (uint32).  Returns the number of entries; the four device arrays are written only when 0 < capacity and
+        the number fits."""
+        opt = lambda v: C.c_void_p(int(v)) if v else None     # noqa: E731
+        out_n = C.c_uint64(0)
+        self._check(self.lib.snpgpu_cluster_snps_dev(self.ctx, opt(d_packed), int(n_rows), int(n_sites), opt(d_labels), int(n_clusters), int(capacity),
+                                                     opt(d_cluster_off), opt(d_site), opt(d_base), opt(d_members), C.byref(out_n)))
+        return int(out_n.value)
+
+    def cluster_snps(self, symbols, labels, n_clusters=None, expect=None):
+        """symbols: (n, s) uint8 array of sequence bytes; labels: (T, n) — or (n,), one labelling — cluster numbers from 1;
+        n_clusters: the number of clusters of each labelling (None: its largest label).  One upload and pack for all labellings.
+        Returns (cluster_off, site, base, members) as ``cluster_snps_dev`` lays them out, the labellings one after another:
+        cluster_off is a list of T uint64 arrays [n_clusters[t] + 1] of offsets into the three entry arrays.  expect: the
+        number of entries when the caller knows it; without it a first call counts and a second emits."""
+        sym = np.ascontiguousarray(symbols, dtype=np.uint8)
+        n, s = sym.shape
+        lab = np.ascontiguousarray(labels, dtype=np.uint32)
+        if lab.ndim == 1:
+            lab = lab.reshape(1, -1)
+        if lab.ndim != 2 or lab.shape[1] != n:
+            raise ValueError("labels hold one cluster number per row of the matrix")
+        t = lab.shape[0]
+        if n_clusters is None:
+            n_clusters = lab.max(axis=1) if n else np.zeros(t, dtype=np.uint32)
+        ncl = np.ascontiguousarray(np.atleast_1d(n_clusters), dtype=np.uint32)
+        if ncl.shape != (t,):
+            raise ValueError("n_clusters holds one count per labelling")
+        if n and t and ((lab == 0).any() or (lab > ncl[:, None]).any()):
+            raise ValueError("a label lies outside 1 ... the number of clusters of its labelling")
+        off = np.zeros(int(ncl.sum(dtype=np.int64)) + t, dtype=np.uint64)
+        opt = lambda x: _ptr(x) if x.size else None           # noqa: E731
+        cap = int(expect) if expect else 0
+        while True:
+            site, base, members = np.zeros(max(cap, 1), dtype=np.uint32), np.zeros(max(cap, 1), dtype=np.uint8), np.zeros(max(cap, 1), dtype=np.uint32)
+            out_n = C.c_uint64(0)
+            self._check(self.lib.snpgpu_cluster_snps(self.ctx, opt(sym), n, s, opt(lab), opt(ncl), t, cap, opt(off), _ptr(site), _ptr(base), _ptr(members), C.byref(out_n)))
+            total = int(out_n.value)
+            if (cap and total <= cap) or t == 0:
+                break
+            cap = max(total, 1)
+        ends = np.cumsum(ncl.astype(np.int64) + 1)
+        return [off[e - int(c) - 1:e] for e, c in zip(ends, ncl)], site[:total], base[:total], members[:total]
+
     # ---- filter_regions ------------------------------------------------------------------------
     def dense_windows(self, positions, seg_off, max_snps, windows):
         pos = np.ascontiguousarray(positions, dtype=np.int64)

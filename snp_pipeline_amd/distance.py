@@ -6,6 +6,8 @@ orders the ids and writes the two TSV layouts.
 """
 from __future__ import print_function
 
+import os
+
 import numpy as np
 
 from . import snp_matrix
@@ -159,15 +161,19 @@ def write_clusters(path, ids, thresholds, numbers):
         raise RuntimeError("snpgpu_write_clusters_tsv failed (%d)" % rc)
 
 
-def write_pairs_and_clusters(dev, ids, row_off, col, dist, pairs_file, max_pair_distance, clusters_file, thresholds, pairs_compared=None):
+def write_pairs_and_clusters(dev, ids, row_off, col, dist, pairs_file, max_pair_distance, clusters_file, thresholds, pairs_compared=None, want_numbers=False):
     """The two additive outputs from one CSR that holds at least every entry within the largest threshold asked for;
-    pairs_compared: the fourth column of the pairs file, one count per entry within max_pair_distance."""
+    pairs_compared: the fourth column of the pairs file, one count per entry within max_pair_distance.  Returns the cluster
+    numbers (len(cluster_thresholds(thresholds)), n) when a clusters file or want_numbers asked for them, else None."""
     if pairs_file:
         write_close_pairs(pairs_file, ids, *filter_pairs(row_off, col, dist, max_pair_distance), compared=pairs_compared)
-    if clusters_file:
+    numbers = None
+    if clusters_file or want_numbers:
         thresholds = cluster_thresholds(thresholds)
         numbers, _ = dev.clusters(len(ids), row_off, col, dist, thresholds)
+    if clusters_file:
         write_clusters(clusters_file, ids, thresholds, numbers)
+    return numbers
 
 
 def mst_of_matrix(dev, file_ids, sym, lens, want_matrix=False, pairs_within=None):
@@ -371,6 +377,74 @@ def write_pair_sites(path, ids, a, b, pair_off, site, bases, snp_list=None):
         raise RuntimeError("snpgpu_write_pair_sites_tsv failed (%d)" % rc)
 
 
+def _site_table_args(snp_list, columns):
+    """The last four arguments of the site writers: all None without a list; (arrays to keep alive, arguments) otherwise."""
+    if snp_list is None:
+        return None, (None, None, None, None)
+    if len(snp_list) != columns:
+        raise ValueError("the site list names %d sites, the matrix has %d columns" % (len(snp_list), columns))
+    keep = site_table(snp_list)
+    if columns == 0:                                           # a list without columns: the writer still wants to see a table
+        keep = keep[:2] + (np.zeros(1, dtype=np.uint32), np.zeros(1, dtype=np.uint64))
+    return keep, (keep[0], keep[1].ctypes.data, keep[2].ctypes.data, keep[3].ctypes.data)
+
+
+def write_site_counts(path, counts, n_rows, snp_list=None):
+    """"Site\tA\tC\tG\tT\tOther" and one row per column of counts ((s, 4): the rows that hold A, C, G, T), Other = n_rows minus
+    the four (csrc/tsv_out.hip); 1-based columns, or — snp_list: the (chrom, pos) of every column — Chrom and Pos in their place."""
+    from . import _lib as L
+    c = np.ascontiguousarray(counts, dtype=np.int32).reshape(-1, 4)
+    keep, table = _site_table_args(snp_list, len(c))
+    rc = L.load().snpgpu_write_site_counts_tsv(path.encode(), c.ctypes.data if len(c) else None, len(c), int(n_rows), *table)
+    if rc == L.E_IO:
+        raise IOError("cannot write %s" % path)
+    if rc == L.E_ARG:
+        raise ValueError("the counts of a column are negative or exceed the %d rows" % int(n_rows))
+    if rc != 0:
+        raise RuntimeError("snpgpu_write_site_counts_tsv failed (%d)" % rc)
+
+
+def write_cluster_snps(path, thresholds, sizes, cluster_off, site, base, members, columns, snp_list=None):
+    """"Threshold\tCluster\tSite\tBase\tMembers\tSize" and one row per entry of Device.cluster_snps, labelling t under
+    thresholds[t]: sizes and cluster_off are lists with one array per labelling (the sizes of its clusters; their offsets and
+    one more).  columns: the width of the matrix.  snp_list as for write_site_counts."""
+    from . import _lib as L
+    thr = np.ascontiguousarray(thresholds, dtype=np.int32)
+    if not len(thr) == len(sizes) == len(cluster_off) or any(len(o) != len(z) + 1 for o, z in zip(cluster_off, sizes)):
+        raise ValueError("one array of sizes and one of offsets (one more) per threshold")
+    ncl = np.asarray([len(z) for z in sizes], dtype=np.uint32)
+    sz = np.ascontiguousarray(np.concatenate([np.asarray(z, dtype=np.uint32) for z in sizes]) if len(sizes) else np.zeros(0), dtype=np.uint32)
+    off = np.ascontiguousarray(np.concatenate([np.asarray(o, dtype=np.uint64) for o in cluster_off]) if len(sizes) else np.zeros(0), dtype=np.uint64)
+    st = np.ascontiguousarray(site, dtype=np.uint32)
+    bs = np.ascontiguousarray(base, dtype=np.uint8)
+    mb = np.ascontiguousarray(members, dtype=np.uint32)
+    if not len(st) == len(bs) == len(mb) or (len(off) and int(off[-1]) != len(st)):
+        raise ValueError("site, base and members hold one entry per offset")
+    keep, table = _site_table_args(snp_list, int(columns))
+    opt = lambda x: x.ctypes.data if len(x) else None          # noqa: E731
+    rc = L.load().snpgpu_write_cluster_snps_tsv(path.encode(), opt(thr), opt(ncl), len(thr), opt(off), opt(sz), opt(st), opt(bs), opt(mb), int(columns), *table)
+    if rc == L.E_IO:
+        raise IOError("cannot write %s" % path)
+    if rc == L.E_ARG:
+        raise ValueError("an entry names a site beyond the %d columns or a base above 3, or the offsets do not rise from 0" % int(columns))
+    if rc != 0:
+        raise RuntimeError("snpgpu_write_cluster_snps_tsv failed (%d)" % rc)
+
+
+def write_cluster_snps_of_numbers(device_of, path, rows, thresholds, numbers, snp_list=None):
+    """--amdClusterSnps: the file for the cluster numbers (len(thresholds), n) of --amdClusters over the sorted rows (None:
+    no record).  One more upload and pack of the rows; nothing but the labels and the entries crosses the host link besides."""
+    numbers = np.asarray(numbers, dtype=np.uint32).reshape(len(thresholds), -1)
+    n = numbers.shape[1]
+    columns = 0 if rows is None else rows.shape[1]
+    sizes = [np.bincount(row, minlength=1)[1:].astype(np.uint32) for row in numbers]
+    if n == 0 or columns == 0:
+        got = ([np.zeros(len(z) + 1, dtype=np.uint64) for z in sizes], np.zeros(0, dtype=np.uint32), np.zeros(0, dtype=np.uint8), np.zeros(0, dtype=np.uint32))
+    else:
+        got = device_of().cluster_snps(rows, numbers, n_clusters=[len(z) for z in sizes])
+    write_cluster_snps(path, thresholds, sizes, *got, columns=columns, snp_list=snp_list)
+
+
 def read_pair_list(path, ids):
     """The pairs of a user's two-column TSV of ids as indices into ids: (a, b).  Further columns are ignored and so is a first
     line "Seq1\tSeq2...", so a close-pairs or tree file of this step can be handed back as it is.  An id the matrix does not
@@ -528,6 +602,8 @@ def calculate_snp_distances(args):
     nearest_count = getattr(args, "amdNearestCount", None)
     compared_matrix_file = getattr(args, "amdComparedMatrixFile", None)
     with_compared = bool(getattr(args, "amdCompared", False))
+    site_counts_file = getattr(args, "amdSiteCountsFile", None)
+    cluster_snps_file = getattr(args, "amdClusterSnpsFile", None)
     if utils.verify_existing_input_files("SNP matrix file", [input_file]) > 0:
         utils.global_error("Error: cannot calculate sequence distances without the snp matrix file.")
     if close_file and max_pair_distance is None:
@@ -538,6 +614,10 @@ def calculate_snp_distances(args):
         utils.global_error("Error: --amdPairSitesPairs and --amdPairSitesOut go together.")
     if user_pairs_file and utils.verify_existing_input_files("pair list file", [user_pairs_file]) > 0:
         utils.global_error("Error: cannot list the differing sites without the pair list file.")
+    if cluster_snps_file and not thresholds:
+        utils.global_error("Error: --amdClusterSnps needs at least one threshold in --amdClusterThresholds.")
+    if snp_list_file and (site_counts_file or cluster_snps_file) and not os.path.isfile(snp_list_file):
+        utils.global_error("Error: --amdSnpList: cannot name the sites of --amdSiteCounts and --amdClusterSnps without the snplist file %s." % snp_list_file)
     if snp_list_file and utils.verify_existing_input_files("snplist file", [snp_list_file]) > 0:
         utils.global_error("Error: cannot name the differing sites without the snplist file.")
     if clusters_file and not thresholds:
@@ -561,11 +641,12 @@ def calculate_snp_distances(args):
     if with_compared and not (close_file or mst_file or nearest_file):
         utils.global_error("Error: --amdCompared needs at least one of --amdClosePairs, --amdMst and --amdNearest.")
     outputs = [f for f in (pairwise_file, matrix_file, close_file, clusters_file, mst_file, dendrogram_file, close_sites_file, mst_sites_file, user_sites_file, nearest_file,
-                           compared_matrix_file) + linkage_files if f]
+                           compared_matrix_file, site_counts_file, cluster_snps_file) + linkage_files if f]
     if not outputs:
         utils.global_error("Error: no output file specified.")
 
-    sources = [input_file] + [f for f in (user_pairs_file, snp_list_file) if f and (close_sites_file or mst_sites_file or user_sites_file)] + ([query_file] if query_file else [])
+    sources = [input_file] + [f for f in (user_pairs_file, snp_list_file) if f and (close_sites_file or mst_sites_file or user_sites_file)] + \
+        ([snp_list_file] if snp_list_file and (site_counts_file or cluster_snps_file) and not (close_sites_file or mst_sites_file or user_sites_file) else []) + ([query_file] if query_file else [])
     if not (args.forceFlag or any(utils.target_needs_rebuild(sources, f) for f in outputs)):
         utils.verbose_print("Distance files have already been freshly built.  Use the -f option to force a rebuild.")
         return
@@ -573,7 +654,20 @@ def calculate_snp_distances(args):
     file_ids, sym, lens = snp_matrix.load_matrix(input_file)
     utils.verbose_print("# %s %s" % (utils.timestamp(), "Calculating all pairwise distances"))
     from .device import default_device
+    named_sites = None
+    if snp_list_file and (site_counts_file or cluster_snps_file):
+        named_sites = utils.read_snp_position_list(snp_list_file)
+        columns = _sorted_rows(file_ids, sym, lens)[1]
+        columns = 0 if columns is None else columns.shape[1]
+        if len(named_sites) != columns:
+            utils.global_error("Error: %s lists %d sites, the snp matrix has %d columns." % (snp_list_file, len(named_sites), columns))
     on_their_own = 0
+    if site_counts_file:
+        # on its own, as the two below: one more upload and pack beside the other outputs; no matrix is computed for it
+        ids, rows = _sorted_rows(file_ids, sym, lens)
+        counts = default_device().site_counts(rows) if rows is not None and rows.size else np.zeros((0 if rows is None else rows.shape[1], 4), dtype=np.int32)
+        write_site_counts(site_counts_file, counts, len(ids), snp_list=named_sites)
+        on_their_own += 1
     if nearest_file:
         # the queries against the database, on their own: this first form uploads and packs the database itself, whatever else is
         # asked for, and the other outputs are computed as without it
@@ -587,25 +681,27 @@ def calculate_snp_distances(args):
         return
     if close_sites_file or mst_sites_file or user_sites_file:
         _distances_with_sites(default_device, file_ids, sym, lens, snp_list_file, pairwise_file, matrix_file, close_file, max_pair_distance, clusters_file, thresholds,
-                              mst_file, dendrogram_file, close_sites_file, mst_sites_file, user_pairs_file, user_sites_file, linkage_kind, linkage_files, with_compared)
+                              mst_file, dendrogram_file, close_sites_file, mst_sites_file, user_pairs_file, user_sites_file, linkage_kind, linkage_files, with_compared,
+                              cluster_snps_file, named_sites)
         return
     dev = default_device()
     mat = None
     tree = None
+    want_clusters = bool(clusters_file or cluster_snps_file)   # the cluster SNPs take the numbers of the clusters file, from the same pairs
     if mst_file or dendrogram_file:
         # the tree is built where the matrix is computed: n - 1 edges come to the host — with them, from that one computation, the
         # pairs within the widest threshold and the matrix itself when those outputs are asked for too
-        widest = max(([max_pair_distance] if close_file else []) + (thresholds if clusters_file else [])) if (close_file or clusters_file) else None
+        widest = max(([max_pair_distance] if close_file else []) + (thresholds if want_clusters else [])) if (close_file or want_clusters) else None
         got = mst_of_matrix(dev, file_ids, sym, lens, want_matrix=bool(pairwise_file or matrix_file), pairs_within=widest)
         ids, tree = got[0], got[1:4]
         got = got[4:]
         if widest is not None:
             (row_off, col, dist), got = got[0], got[1:]
         mat = got[0] if got else None
-    elif close_file or clusters_file:
+    elif close_file or want_clusters:
         # the matrix is thresholded where it is computed: only the pairs within the largest threshold come to the host — and the
         # matrix of that same computation when the two tables are asked for too
-        widest = max(([max_pair_distance] if close_file else []) + (thresholds if clusters_file else []))
+        widest = max(([max_pair_distance] if close_file else []) + (thresholds if want_clusters else []))
         got = close_pairs_of_matrix(dev, file_ids, sym, lens, widest, want_matrix=bool(pairwise_file or matrix_file))
         ids, row_off, col, dist = got[:4]
         mat = got[4] if len(got) > 4 else None
@@ -628,12 +724,15 @@ def calculate_snp_distances(args):
     if with_compared:
         pairs_compared, tree_compared = compared_columns(dev, _sorted_rows(file_ids, sym, lens)[1], filter_pairs(row_off, col, dist, max_pair_distance) if close_file else None,
                                                          tree if mst_file else None)
-    if close_file or clusters_file:
-        write_pairs_and_clusters(dev, ids, row_off, col, dist, close_file, max_pair_distance, clusters_file, thresholds, pairs_compared)
+    if close_file or want_clusters:
+        numbers = write_pairs_and_clusters(dev, ids, row_off, col, dist, close_file, max_pair_distance, clusters_file, thresholds, pairs_compared,
+                                           want_numbers=bool(cluster_snps_file))
     if mst_file:
         write_mst(mst_file, ids, *tree, compared=tree_compared)
     if dendrogram_file:
         write_dendrogram(dendrogram_file, ids, *tree)
+    if cluster_snps_file:
+        write_cluster_snps_of_numbers(lambda: dev, cluster_snps_file, _sorted_rows(file_ids, sym, lens)[1], cluster_thresholds(thresholds), numbers, snp_list=named_sites)
 
 
 def _write_nearest_output(device_of, file_ids, sym, lens, query_file, nearest_file, count, max_pair_distance, with_compared=False):
@@ -654,7 +753,7 @@ def _write_nearest_output(device_of, file_ids, sym, lens, query_file, nearest_fi
 
 def _distances_with_sites(device_of, file_ids, sym, lens, snp_list_file, pairwise_file, matrix_file, close_file, max_pair_distance, clusters_file, thresholds,
                           mst_file, dendrogram_file, close_sites_file, mst_sites_file, user_pairs_file, user_sites_file, linkage_kind=None,
-                          linkage_files=(None, None, None), with_compared=False):
+                          linkage_files=(None, None, None), with_compared=False, cluster_snps_file=None, named_sites=None):
     """calculate_snp_distances when the differing sites of some pairs are asked for: the symbols are uploaded and packed once; the
     matrix is computed once, and only when a tree, a threshold or a table needs it; the packed matrix stays on the device until
     every pair list has been answered from it.  The n x n matrix comes to the host for -p / -m alone."""
@@ -671,7 +770,7 @@ def _distances_with_sites(device_of, file_ids, sym, lens, snp_list_file, pairwis
     dev = device_of()                                          # (the inputs have been checked: only now is a device needed)
     want_tree = bool(mst_file or dendrogram_file or mst_sites_file)
     want_matrix = bool(pairwise_file or matrix_file)
-    within = ([max_pair_distance] if (close_file or close_sites_file) else []) + (thresholds if clusters_file else [])
+    within = ([max_pair_distance] if (close_file or close_sites_file) else []) + (thresholds if (clusters_file or cluster_snps_file) else [])
     widest = max(within) if within else None
     tree = csr = mat = None
     kept = False
@@ -699,8 +798,11 @@ def _distances_with_sites(device_of, file_ids, sym, lens, snp_list_file, pairwis
         if with_compared:                                      # (not done: reuse of the kept packed matrix — one more upload and pack)
             pairs_compared, tree_compared = compared_columns(dev, rows if n else None, filter_pairs(csr[0], csr[1], csr[2], max_pair_distance) if close_file else None,
                                                              tree if mst_file else None)
-        if close_file or clusters_file:
-            write_pairs_and_clusters(dev, ids, csr[0], csr[1], csr[2], close_file, max_pair_distance, clusters_file, thresholds, pairs_compared)
+        if close_file or clusters_file or cluster_snps_file:
+            numbers = write_pairs_and_clusters(dev, ids, csr[0], csr[1], csr[2], close_file, max_pair_distance, clusters_file, thresholds, pairs_compared,
+                                               want_numbers=bool(cluster_snps_file))
+        if cluster_snps_file:                                  # (not done: reuse of the kept packed matrix — one more upload and pack)
+            write_cluster_snps_of_numbers(lambda: dev, cluster_snps_file, rows if n else None, cluster_thresholds(thresholds), numbers, snp_list=named_sites)
         if mst_file:
             write_mst(mst_file, ids, *tree, compared=tree_compared)
         if dendrogram_file:
