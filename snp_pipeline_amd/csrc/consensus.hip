@@ -495,7 +495,41 @@ struct Planes {
     }
     __device__ __forceinline__ uint32_t upper() const { return p6 & ~p5; }                               // 0x40-0x5F
     __device__ __forceinline__ uint32_t lower() const { return p6 & p5; }                                // 0x60-0x7F
+    // str.split()'s separators 9..13, 28..32 and the line terminator candidates 10..13 (the window tokeniser of k_call_lanes<128>)
+    __device__ __forceinline__ uint32_t term() const { return ~p6 & ~p5 & ~p4 & p3 & (p2 ^ p1); }        // 0x0A-0x0D
+    __device__ __forceinline__ uint32_t space() const {
+        const uint32_t lo = ~p6 & ~p5;
+        return (lo & ~p4 & p3 & (p2 | p1 | p0) & ~(p2 & p1)) | (lo & p4 & p3 & p2) | (~p6 & p5 & ~(p4 | p3 | p2 | p1 | p0));   // 9-13, 28-31, 32
+    }
 };
+
+// Thirty-two bytes (eight dwords) as their eight plane words, p[b]: bit b of every byte, one mask bit per byte.  It is a 32 x 8 bit
+// transpose done as index exchanges: a 4 x 4 byte transpose over the dwords 8 bytes apart (v_perm_b32) puts bits 4-3 of the byte index
+// into the byte position, then three masked exchanges between registers (shift + v_bfi each way) trade the register index — bits 0, 1,
+// 2 of the byte index — for bits 0, 1, 2 of the bit position.  64 VALU for 32 bytes; tests/test_call_window_planes_cpu.py states it.
+__device__ __forceinline__ void planes_of_32_bytes(const uint32_t (&d)[8], uint32_t (&p)[8]) {
+    uint32_t r[4][2];                                            // r[k][h]: bytes 8 m + 4 h + k (m = 0..3) in byte m
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const uint32_t u0 = __builtin_amdgcn_perm(d[2 + h], d[h], 0x05010400u), u1 = __builtin_amdgcn_perm(d[2 + h], d[h], 0x07030602u);
+        const uint32_t u2 = __builtin_amdgcn_perm(d[6 + h], d[4 + h], 0x05010400u), u3 = __builtin_amdgcn_perm(d[6 + h], d[4 + h], 0x07030602u);
+        r[0][h] = __builtin_amdgcn_perm(u2, u0, 0x05040100u); r[1][h] = __builtin_amdgcn_perm(u2, u0, 0x07060302u);
+        r[2][h] = __builtin_amdgcn_perm(u3, u1, 0x05040100u); r[3][h] = __builtin_amdgcn_perm(u3, u1, 0x07060302u);
+    }
+    // exchange(a, b, s, m): bit position bit log2(s) of the pair (a, b) against which of the two registers it is
+    auto exchange = [](uint32_t &a, uint32_t &b, uint32_t s, uint32_t m) {
+        const uint32_t na = (a & m) | ((b << s) & ~m), nb = ((a >> s) & m) | (b & ~m);
+        a = na; b = nb;
+    };
+#pragma unroll
+    for (int h = 0; h < 2; ++h) { exchange(r[0][h], r[1][h], 1, 0x55555555u); exchange(r[2][h], r[3][h], 1, 0x55555555u); }
+#pragma unroll
+    for (int h = 0; h < 2; ++h) { exchange(r[0][h], r[2][h], 2, 0x33333333u); exchange(r[1][h], r[3][h], 2, 0x33333333u); }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) exchange(r[k][0], r[k][1], 4, 0x0F0F0F0Fu);
+#pragma unroll
+    for (int b = 0; b < 8; ++b) p[b] = r[b & 3][b >> 2];
+}
 
 // ------------------------------------------------------------------------------------------------
 //                         K2 fast path: one LANE per site, 64 sites per wave
@@ -525,6 +559,9 @@ __global__ __launch_bounds__(kWaves * 64, kWin == 128 ? 3 : 1) void k_call_lanes
     constexpr int LANES_WAVES = kWaves;
     constexpr uint32_t kBits = 64u * kWords;      // mask width = longest bases field in bytes ...
     constexpr uint32_t kMaxField = kBits > 255u ? 255u : kBits;   // ... but the counts live in byte lanes
+    constexpr bool kPlanes = kWin == 128;         // tokeniser, field planes and quality test from one bit-plane gather of the window (the wider
+                                                  // windows keep the byte-wise forms: thirty-two plane words per 128 bytes do not fit their registers)
+    static_assert(!kPlanes || kWords == 1, "the window planes feed a 64-bit field mask");
     typedef BM<kWords> M;
     __shared__ LanesLds<kWin, kWaves> S;
     const bool deep = a.deep && *a.deep != 0;
@@ -649,8 +686,60 @@ __global__ __launch_bounds__(kWaves * 64, kWin == 128 ? 3 : 1) void k_call_lanes
 #pragma unroll
         for (int q = 0; q < LANES_WIN / 64; ++q) { Wm[q] = 0; Tm[q] = 0; }
         bool done = !has;
+        // The 128-byte window instead goes through its bit planes, gathered once: pw[b][q] holds bit b of the window's bytes 32 q ..
+        // 32 q + 31.  Separators, terminator candidates and (below) the quality test are boolean functions of them, and the bases
+        // field's planes are these shifted.  The edge rules are masks: bytes before the line start are separators, and so is the
+        // second half of a window whose first half holds a terminator candidate (as the loop below leaves it).  A byte >= 0x80 is
+        // no separator; the scan rejects such a file.
+        uint32_t pw[kPlanes ? 8 : 1][LANES_WIN / 32];
+        uint32_t qge[LANES_WIN / 32];                          // byte >= 33 + minq, one bit per byte of the window
+        if constexpr (kPlanes) {
 #pragma unroll
-        for (int blk = 0; blk < LANES_WIN / 64; ++blk) {
+            for (int q = 0; q < LANES_WIN / 32; ++q) {
+                uint32_t d[8], p[8];
+#pragma unroll
+                for (int j = 0; j < 8; ++j) d[j] = slot[8 * q + j];
+                planes_of_32_bytes(d, p);
+#pragma unroll
+                for (int b = 0; b < 8; ++b) pw[b][q] = p[b];
+            }
+            uint32_t sp[LANES_WIN / 32], tm[LANES_WIN / 32];
+#pragma unroll
+            for (int q = 0; q < LANES_WIN / 32; ++q) {
+                const Planes p{pw[0][q], pw[1][q], pw[2][q], pw[3][q], pw[4][q], pw[5][q], pw[6][q]};
+                sp[q] = p.space() & ~pw[7][q];
+                tm[q] = p.term() & ~pw[7][q];
+            }
+            const uint32_t before = (1u << o) - 1u;            // o <= 15
+            sp[0] |= before;
+            tm[0] &= ~before;
+#pragma unroll
+            for (int blk = 0; blk < LANES_WIN / 64; ++blk) {
+                Wm[blk] = done ? ~0ull : (uint64_t)sp[2 * blk] | ((uint64_t)sp[2 * blk + 1] << 32);
+                Tm[blk] = done ? 0ull : (uint64_t)tm[2 * blk] | ((uint64_t)tm[2 * blk + 1] << 32);
+                done = done || Tm[blk] != 0;
+            }
+            // the quality threshold as a magnitude comparator on the planes, least significant bit first: with the bits below
+            // bit b compared, byte >= thr is (bit b of the byte) & (so far) where thr has the bit, | where it has not
+            const int thr = 33 + minq;
+            if (thr > 0 && thr <= 128) {
+#pragma unroll
+                for (int q = 0; q < LANES_WIN / 32; ++q) {
+                    uint32_t ge = ~0u;
+#pragma unroll
+                    for (int b = 0; b < 8; ++b) {
+                        const uint32_t tb = 0u - (((uint32_t)thr >> b) & 1u);          // all ones or zero, wave-uniform
+                        ge = __builtin_amdgcn_bitop3_b32(pw[b][q], ge, tb, 0xD4);      // (p & ge) | (~tb & (p | ge)), kept one instruction
+                    }
+                    qge[q] = ge;
+                }
+            } else {
+#pragma unroll
+                for (int q = 0; q < LANES_WIN / 32; ++q) qge[q] = ~0u;
+            }
+        }
+#pragma unroll
+        for (int blk = 0; blk < (kPlanes ? 0 : LANES_WIN / 64); ++blk) {
             if (!__ballot(!done)) break;
             if (blk >= 2 && (blk & 1) == 0) { stage_half(blk / 2, !done); __builtin_amdgcn_wave_barrier(); }   // only the lines that are still open
             const bool open = !done;                             // (the slots of the others hold stale bytes up there)
@@ -696,7 +785,30 @@ __global__ __launch_bounds__(kWaves * 64, kWin == 128 ? 3 : 1) void k_call_lanes
         };
         const uint32_t line_end = scan_from(Tm, false, 0);      // candidates are bytes 10..13; 11 and 12 are checked below
         uint32_t nf = 0, f_s[6], f_e[6];
-        {
+        if constexpr (kPlanes) {
+            // The fields' first bytes and ends are the places where the separator mask changes, in rising order (a separator stands
+            // before byte 0, so the first change is a field's first byte): twelve steps of find-lowest / clear-lowest on 128 bits
+            // instead of twelve masked scans.  Of the name and the position only their presence counts, and they are there
+            // when the third field is (fewer than four fields: the site is handed on below, whatever the number).
+            typedef unsigned __int128 u128;
+            const u128 W = (u128)Wm[0] | ((u128)Wm[1] << 64);
+            u128 E = W ^ ((W << 1) | 1u);
+            auto next_edge = [&]() -> uint32_t {
+                const uint64_t lo = (uint64_t)E, hi = (uint64_t)(E >> 64);
+                const uint32_t r = lo ? (uint32_t)__builtin_ctzll(lo) : hi ? 64u + (uint32_t)__builtin_ctzll(hi) : (uint32_t)LANES_WIN;
+                E &= E - 1u;
+                return r;
+            };
+#pragma unroll
+            for (int k = 0; k < 4; ++k) E &= E - 1u;
+            f_s[0] = f_e[0] = f_s[1] = f_e[1] = 0;
+#pragma unroll
+            for (int k = 2; k < 6; ++k) {
+                f_s[k] = next_edge();
+                f_e[k] = next_edge();
+                nf += f_s[k] < line_end ? (k == 2 ? 3u : 1u) : 0u;
+            }
+        } else {
             uint32_t pos = o;
 #pragma unroll
             for (int k = 0; k < 6; ++k) {
@@ -736,10 +848,13 @@ __global__ __launch_bounds__(kWaves * 64, kWin == 128 ? 3 : 1) void k_call_lanes
         if (parse && fe(4) - fs(4) > kMaxField) { punt = true; parse = false; }
         {
             const uint32_t bs = parse ? fs(4) : 0u, L0 = parse ? fe(4) - fs(4) : 0u, qs = fs(5), qlen = parse ? fe(5) - fs(5) : 0u;
-            uint32_t maxL = L0;
-            for (int off = 32; off; off >>= 1) maxL = max(maxL, (uint32_t)__shfl_xor((int)maxL, off));
-            maxL = __builtin_amdgcn_readfirstlane(maxL);
-            const uint32_t nd = (maxL + 3) >> 2;                 // dwords of the longest field in the wave
+            auto longest_field_dwords = [&]() -> uint32_t {      // dwords of the longest field in the wave (called by the whole wave)
+                uint32_t maxL = L0;
+                for (int off = 32; off; off >>= 1) maxL = max(maxL, (uint32_t)__shfl_xor((int)maxL, off));
+                return (__builtin_amdgcn_readfirstlane(maxL) + 3) >> 2;
+            };
+            uint32_t nd = 0;
+            if constexpr (!kPlanes) nd = longest_field_dwords();
             const M V = m_below<kWords>(L0);
             // -- bit planes of the field: pl[b] holds bit b of every byte, one mask bit per byte, in field coordinates (the layout
             //    of BM<kWords>).  Two dwords give one mask byte per plane: the plane's bit of each byte, two dot4 that gather the
@@ -749,7 +864,17 @@ __global__ __launch_bounds__(kWaves * 64, kWin == 128 ? 3 : 1) void k_call_lanes
             for (int b = 0; b < 7; ++b)
 #pragma unroll
                 for (int q = 0; q < 2 * kWords; ++q) pl[b][q] = 0;
-            {
+            if constexpr (kPlanes) {
+                // the window's planes from byte bs on: a 128-bit funnel shift to 64 bits, the dwords chosen by bs >> 5 (past the window: zero)
+                const bool k1 = (bs & 32u) != 0, k2 = (bs & 64u) != 0;
+#pragma unroll
+                for (int b = 0; b < 7; ++b) {
+                    const uint32_t y0 = k2 ? pw[b][2] : pw[b][0], y1 = k2 ? pw[b][3] : pw[b][1], y2 = k2 ? 0u : pw[b][2], y3 = k2 ? 0u : pw[b][3];
+                    const uint32_t z0 = k1 ? y1 : y0, z1 = k1 ? y2 : y1, z2 = k1 ? y3 : y2;
+                    pl[b][0] = __builtin_amdgcn_alignbit(z1, z0, bs & 31u);
+                    pl[b][1] = __builtin_amdgcn_alignbit(z2, z1, bs & 31u);
+                }
+            } else {
                 const uint32_t sh = bs & 3u;
                 uint32_t lo = slot[bs >> 2];
 #pragma unroll
@@ -840,7 +965,12 @@ __global__ __launch_bounds__(kWaves * 64, kWin == 128 ? 3 : 1) void k_call_lanes
             bool allq = kept_total <= qlen;
             if (thr > 0) {
                 if (thr > 128) allq = allq && kept_total == 0;
-                else {
+                else if constexpr (kPlanes) {
+                    // no byte below thr among the qualities that matter: the comparator's word under the mask of their range
+                    const uint32_t need = kept_total < qlen ? kept_total : qlen;      // (not parsed: qlen == 0; else qs + qlen <= the window)
+                    const BM<2> R = m_andn(m_below<2>(qs + need), m_below<2>(qs));
+                    allq = allq && ((R.w[0] & ~((uint64_t)qge[0] | ((uint64_t)qge[1] << 32))) | (R.w[1] & ~((uint64_t)qge[2] | ((uint64_t)qge[3] << 32)))) == 0;
+                } else {
                     const uint32_t addc = (uint32_t)(128 - thr) * 0x01010101u;       // bit 7 of a byte after the add: byte >= thr
                     const uint32_t shq = qs & 3u;
                     uint32_t lo = slot[(qs >> 2) & (LANES_WIN / 4 - 1u)];
@@ -890,6 +1020,7 @@ __global__ __launch_bounds__(kWaves * 64, kWin == 128 ? 3 : 1) void k_call_lanes
             } else {
                 // Some lane of the wave has a failing or a missing quality: the kept bytes are walked one by one, each paired with
                 // its quality (zip truncation, pileup.py:248-250).
+                if constexpr (kPlanes) nd = longest_field_dwords();
                 const uint32_t sh = bs & 3u;
                 uint32_t lo = slot[bs >> 2];
                 uint32_t kept = 0;
