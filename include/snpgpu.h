@@ -822,6 +822,61 @@ int  snpgpu_write_linkage_newick(const char *path, const char *ids, const uint64
                                  const uint32_t *a, const uint32_t *b, const uint32_t *size_a, const uint32_t *size_b,
                                  const uint64_t *num, uint32_t n_merges);
 
+/* ---- neighbour-joining tree (csrc/nj.hip) ------------------------------------------------------------------------------------
+ * Additive entries of ABI 7, like the ones above: the standard distance-based phylogeny (Saitou & Nei's method with the
+ * Studier-Keppler criterion), which assumes no molecular clock and on an additive matrix returns the true tree with its branch
+ * lengths.  In floating point the method depends on summation order and breaks ties by rounding noise; here it is stated in
+ * integers, in fixed point, so every sum is associative, any reduction order gives the same value and THE tree is unique.
+ *
+ * Samples are 0 ... n-1.  F = 20 fractional bits; working values are w(i,k) = matrix[i][k] << F, signed 64 bits.  A node lives
+ * in a slot; slot i starts as sample i and a joined node keeps the smaller of its two slots, so a node's slot is its smallest
+ * sample.  r is the number of live slots.  While r > 3, one round: R(i) = the sum of w(i,k) over live k != i; for live i < j,
+ * Q(i,j) = (r-2) w(i,j) - R(i) - R(j); the pair that is least in the order (Q, i, j), call it a < b, is joined with the branch
+ * lengths La = floor(((r-2) w(a,b) + R(a) - R(b)) / (2 (r-2))) (towards minus infinity) and Lb = w(a,b) - La; the new node takes
+ * slot a, and for every other live k, w(a,k) = w(k,a) = floor((w(a,k) + w(b,k) - w(a,b)) / 2); slot b retires; the record is
+ * (a, b, La, Lb).  Lengths and distances may be negative and are kept as they are: nothing is clamped.  The last three live
+ * slots a < b < c are the star: La = floor((w(a,b) + w(a,c) - w(b,c)) / 2), Lb = w(a,b) - La, Lc = w(a,c) - La.  n = 2: the star
+ * is (0, 1, none) with L0 = floor(w / 2), L1 = w - L0.  n <= 1: nothing.  So there are max(n - 3, 0) merges, in round order
+ * (nothing is sorted afterwards), and at most one star.  The floors cost at most 2^-20 SNP per level of the tree.
+ *
+ * Range: with L = floor(2^61 / max(n, 1)), every |Q| stays below 2^63 while every |w| <= L.  A matrix that holds a negative
+ * entry, or whose (largest entry) << F exceeds L, is refused with SNPGPU_E_ARG before the first round and before any record is
+ * written (n beyond 1024 at entries of 2^31 - 1; at 10 000 samples entries up to 219 million pass).  A sticky device flag is
+ * raised when a round produces a |w| above L; it is read once after the last round, and then the call returns SNPGPU_E_ARG and
+ * the outputs are unspecified.  In the Python statement of the tests no random, tied, planted or additive matrix grew beyond its
+ * initial largest value, so that flag is a guard no test reaches on the device.
+ *
+ * snpgpu_nj_dev: the tree of the symmetric device int32 matrix (row i at d_matrix + i * row_stride elements, row_stride >= n,
+ * 4-byte aligned; the diagonal and columns >= n are never read; the matrix is not modified).  d_a, d_b (uint32), d_len_a,
+ * d_len_b (int64), room for n - 3 each (may be null for n <= 3), receive the merges; out_star[3] (host; 0xFFFFFFFF for none),
+ * out_star_len[3] (host) the star; *out_n_merges (host) the number of merges.  All n - 3 rounds are enqueued on the context's
+ * stream without a host wait in between: the call waits once before the first round, for the refusal, and once at the end, for the
+ * star and the flag.  Needs 8 n^2 bytes of device memory, the n x n working matrix (SNPGPU_E_NOMEM): when an eighth of the stored
+ * slots have retired the live columns of every row are moved together in place, in their order. */
+int  snpgpu_nj_dev(snpgpu_ctx *ctx, const int32_t *d_matrix, uint32_t n, uint64_t row_stride, uint32_t *d_a, uint32_t *d_b,
+                   int64_t *d_len_a, int64_t *d_len_b, uint32_t *out_star, int64_t *out_star_len, uint32_t *out_n_merges);
+/* Host form (as snpgpu_linkage): packs the symbols, computes the matrix and builds the tree on the device; the four host arrays
+ * hold n_rows - 3 merges.  With out_matrix null the n x n matrix never crosses the host link; not null: it is copied there too,
+ * from the same computation. */
+int  snpgpu_nj(snpgpu_ctx *ctx, const uint8_t *symbols, uint32_t n_rows, uint32_t n_sites, uint32_t *out_a, uint32_t *out_b,
+               int64_t *out_len_a, int64_t *out_len_b, int32_t *out_matrix, uint32_t *out_star, int64_t *out_star_len,
+               uint32_t *out_n_merges);
+/* Host form for a caller that has the matrix already (a table was asked for): uploads the HOST int32 matrix and builds the tree. */
+int  snpgpu_nj_of_matrix(snpgpu_ctx *ctx, const int32_t *matrix, uint32_t n, uint64_t row_stride, uint32_t *out_a, uint32_t *out_b,
+                         int64_t *out_len_a, int64_t *out_len_b, uint32_t *out_star, int64_t *out_star_len,
+                         uint32_t *out_n_merges);
+/* The text (host code): one Newick line in the grammar of snpgpu_write_linkage_newick / snpgpu_write_dendrogram_newick (same
+ * quoting of ids, no recursion).  Inside a node the child whose smallest sample is smaller comes first; the star is a
+ * trifurcation at the top, "(A:la,B:lb,C:lc);\n", its three children in the same order; n = 2: "(id0:l0,id1:l1);\n"; n = 1:
+ * "id;\n"; n = 0: ";\n".  A length x is written from integer millionths m = floor((2 x 10^6 + 2^F) / 2^(F+1)), computed in 128
+ * bits (half up): "-" when m < 0, the integer part of |m|, then, when the fraction is not zero, "." and its six digits without
+ * trailing zeros ("7", "7.5", "-0.0625", "0").  SNPGPU_E_ARG unless the records are a tree of the n samples: a < b < n, both
+ * live, max(n - 3, 0) merges, and a star of exactly the live slots that are left, ascending.  SNPGPU_E_IO when the file cannot be
+ * created or written. */
+int  snpgpu_write_nj_newick(const char *path, const char *ids, const uint64_t *id_off, uint32_t n, const uint32_t *a,
+                            const uint32_t *b, const int64_t *len_a, const int64_t *len_b, uint32_t n_merges,
+                            const uint32_t *star, const int64_t *star_len);
+
 /* ---- the differing sites of pairs (csrc/pair_sites.hip) -----------------------------------------------------------------
  * Additive entries of ABI 7, like the ones above: by which columns two samples differ.  Column s of pair (a, b) differs iff
  * both bytes, after upper-casing, are in {A,C,G,T} and are not equal (utils.py:1135-1165, what the distance kernel counts), so

@@ -213,6 +213,10 @@ SIGNATURES = {
     "snpgpu_linkage_cut": (C.c_int, [C.c_int, C.c_uint32, _P, _P, _P, _P, _P, C.c_uint32, _P, C.c_uint32, _P, _P]),
     "snpgpu_write_linkage_tsv": (C.c_int, [C.c_char_p, _P, _P, C.c_uint32, C.c_int, _P, _P, _P, _P, _P, C.c_uint32]),
     "snpgpu_write_linkage_newick": (C.c_int, [C.c_char_p, _P, _P, C.c_uint32, C.c_int, _P, _P, _P, _P, _P, C.c_uint32]),
+    "snpgpu_nj_dev": (C.c_int, [_P, _P, C.c_uint32, C.c_uint64, _P, _P, _P, _P, _P, _P, C.POINTER(C.c_uint32)]),
+    "snpgpu_nj": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, _P, _P, _P, _P, _P, _P, _P, C.POINTER(C.c_uint32)]),
+    "snpgpu_nj_of_matrix": (C.c_int, [_P, _P, C.c_uint32, C.c_uint64, _P, _P, _P, _P, _P, _P, C.POINTER(C.c_uint32)]),
+    "snpgpu_write_nj_newick": (C.c_int, [C.c_char_p, _P, _P, C.c_uint32, _P, _P, _P, _P, C.c_uint32, _P, _P]),
     "snpgpu_pair_sites_dev": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, _P, _P, C.c_uint64, C.c_uint64, _P, _P, _P, C.POINTER(C.c_uint64)]),
     "snpgpu_pair_sites": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, _P, _P, C.c_uint64, C.c_uint64, _P, _P, _P, C.POINTER(C.c_uint64)]),
     "snpgpu_distance_outputs": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, C.c_int, _P, _P, _P, _P, C.c_int, C.c_int32, C.c_uint64, _P, _P, _P, C.POINTER(C.c_uint64),

@@ -14,6 +14,7 @@
 
 #include "internal.h"
 #include "linkage_host.h"
+#include "nj_host.h"
 
 namespace {
 
@@ -725,5 +726,15 @@ extern "C" int snpgpu_write_linkage_newick(const char *path, const char *ids, co
         }
     }
     o.put(";\n", 2);
+    return o.finish();
+}
+
+// ---- neighbour-joining tree (additive: the records of csrc/nj.hip as text; the check and the writer are nj_host.h) ----
+extern "C" int snpgpu_write_nj_newick(const char *path, const char *ids, const uint64_t *id_off, uint32_t n, const uint32_t *a, const uint32_t *b,
+                                      const int64_t *len_a, const int64_t *len_b, uint32_t n_merges, const uint32_t *star, const int64_t *star_len) {
+    if (!path || (n && (!ids || !id_off)) || !nj_records_ok(n, a, b, len_a, len_b, n_merges, star, star_len)) return SNPGPU_E_ARG;
+    FileOut o(path);
+    if (o.failed) return SNPGPU_E_IO;
+    nj_put_newick(o, ids, id_off, n, a, b, len_a, len_b, n_merges, star, star_len);
     return o.finish();
 }

@@ -1224,6 +1224,60 @@ class Device(object):
             self.ctx, _ptr(mat) if mat.size else None, n, n, k, a, b, sa, sb, num, nm, nr))
         return got + ((rounds,) if want_rounds else ())
 
+    # ---- neighbour-joining tree (additive to distance.py:93-106) ---------------------------------
+    NJ_FRACTION_BITS = 20
+    NJ_NONE = 0xFFFFFFFF
+
+    @staticmethod
+    def _nj_star(star, star_len):
+        return tuple(None if int(s) == Device.NJ_NONE else int(s) for s in star), tuple(int(x) for x in star_len)
+
+    def nj_dev(self, d_matrix, n, row_stride, d_a=0, d_b=0, d_len_a=0, d_len_b=0):
+        """The neighbour-joining tree of a symmetric device int32 matrix (columns < n, the diagonal left out), in fixed point with
+        NJ_FRACTION_BITS fractional bits: the max(n - 3, 0) merges (a, b, length of a's branch, length of b's) in round order into
+        d_a / d_b (uint32) and d_len_a / d_len_b (int64), room for n - 3 each.  Returns (number of merges, star, star_len): the
+        slots of the star at the top (three ints; None where there is none: n < 3) and the lengths of their branches."""
+        opt = lambda v: C.c_void_p(int(v)) if v else None     # noqa: E731
+        n_merges = C.c_uint32(0)
+        star, star_len = np.zeros(3, dtype=np.uint32), np.zeros(3, dtype=np.int64)
+        self._check(self.lib.snpgpu_nj_dev(self.ctx, opt(d_matrix), int(n), int(row_stride), opt(d_a), opt(d_b), opt(d_len_a), opt(d_len_b), _ptr(star),
+                                           _ptr(star_len), C.byref(n_merges)))
+        return (int(n_merges.value),) + self._nj_star(star, star_len)
+
+    def _nj_host(self, n, call):
+        m = max(n - 3, 0)
+        a, b = (np.zeros(m, dtype=np.uint32) for _ in range(2))
+        la, lb = (np.zeros(m, dtype=np.int64) for _ in range(2))
+        star, star_len = np.zeros(3, dtype=np.uint32), np.zeros(3, dtype=np.int64)
+        opt = lambda x: _ptr(x) if x.size else None           # noqa: E731
+        n_merges = C.c_uint32(0)
+        self._check(call(opt(a), opt(b), opt(la), opt(lb), _ptr(star), _ptr(star_len), C.byref(n_merges)))
+        if int(n_merges.value) != m:
+            raise RuntimeError("the neighbour-joining tree of %d samples has %d merges" % (n, int(n_merges.value)))
+        return (a, b, la, lb) + self._nj_star(star, star_len)
+
+    def nj(self, symbols, want_matrix=False):
+        """symbols: (n, s) uint8 array of sequence bytes.  Returns (a, b uint32, len_a, len_b int64, star, star_len): the n - 3
+        merges of the neighbour-joining tree of the distance matrix in round order, a < b the slots (smallest samples) of the two
+        nodes and the lengths of their branches in fixed point (NJ_FRACTION_BITS fractional bits), then the star as ``nj_dev``
+        gives it.  The matrix stays on the device — unless want_matrix, which adds the (n, n) int32 matrix of ``distance`` from
+        the same computation."""
+        sym = np.ascontiguousarray(symbols, dtype=np.uint8)
+        n, s = sym.shape
+        mat = np.zeros((n, n), dtype=np.int32) if want_matrix else None
+        got = self._nj_host(n, lambda a, b, la, lb, star, star_len, nm: self.lib.snpgpu_nj(
+            self.ctx, _ptr(sym) if sym.size else None, n, s, a, b, la, lb, _ptr(mat) if want_matrix and mat.size else None, star, star_len, nm))
+        return got + ((mat,) if want_matrix else ())
+
+    def nj_of_matrix(self, matrix):
+        """As ``nj`` for an (n, n) host int32 matrix a caller already has."""
+        mat = np.ascontiguousarray(matrix, dtype=np.int32)
+        if mat.ndim != 2 or mat.shape[0] != mat.shape[1]:
+            raise ValueError("the matrix is square")
+        n = mat.shape[0]
+        return self._nj_host(n, lambda a, b, la, lb, star, star_len, nm: self.lib.snpgpu_nj_of_matrix(
+            self.ctx, _ptr(mat) if mat.size else None, n, n, a, b, la, lb, star, star_len, nm))
+
     # ---- the differing sites of pairs (additive to distance.py:93-106) ---------------------------
     def pair_sites_dev(self, d_packed, n_rows, n_sites, d_a, d_b, n_pairs, capacity=0, d_pair_off=0, d_site=0, d_bases=0):
         """The columns at which the pairs (d_a[p], d_b[p]) of rows of a device packed matrix differ, pair by pair, ascending:

@@ -306,6 +306,37 @@ def write_linkage_outputs(ids, kind, merges, merges_file, dendrogram_file, clust
         write_clusters(clusters_file, ids, thresholds, numbers)
 
 
+def nj_of_symbols(dev, file_ids, sym, lens):
+    """As linkage_of_symbols, but what comes back is the neighbour-joining tree of the samples: (ids, tree), tree the six values
+    of Device.nj; built on the device, where the matrix stays."""
+    ids, rows = _sorted_rows(file_ids, sym, lens)
+    if rows is None:
+        rows = np.zeros((0, 0), dtype=np.uint8)
+    return ids, tuple(dev.nj(rows))
+
+
+def write_nj(path, ids, a, b, len_a, len_b, star, star_len):
+    """The neighbour-joining tree (the values of Device.nj) as one Newick line: a trifurcation at the top, lengths in SNPs written
+    from integer millionths (csrc/nj_host.h)."""
+    from . import _lib as L
+    blob, off = _id_table(ids)
+    a, b = (np.ascontiguousarray(x, dtype=np.uint32) for x in (a, b))
+    len_a, len_b = (np.ascontiguousarray(x, dtype=np.int64) for x in (len_a, len_b))
+    if not len(a) == len(b) == len(len_a) == len(len_b) or len(star) != 3 or len(star_len) != 3:
+        raise ValueError("a, b, len_a and len_b hold one entry per merge, the star three slots and three lengths")
+    star = np.asarray([0xFFFFFFFF if s is None else int(s) for s in star], dtype=np.uint32)
+    star_len = np.asarray([int(x) for x in star_len], dtype=np.int64)
+    opt = lambda x: x.ctypes.data if x.size else None          # noqa: E731
+    rc = L.load().snpgpu_write_nj_newick(path.encode(), blob, off.ctypes.data, len(ids), opt(a), opt(b), opt(len_a), opt(len_b), len(a), star.ctypes.data,
+                                         star_len.ctypes.data)
+    if rc == L.E_IO:
+        raise IOError("cannot write %s" % path)
+    if rc == L.E_ARG:
+        raise ValueError("the merges and the star are not a neighbour-joining tree of the %d ids" % len(ids))
+    if rc != 0:
+        raise RuntimeError("snpgpu_write_nj_newick failed (%d)" % rc)
+
+
 def pairs_of_csr(row_off, col, dist, threshold):
     """The entries i < j, d <= threshold of a CSR in its order: (a, b, d) — each unordered pair of the close-pairs file once."""
     row_off = np.asarray(row_off, dtype=np.int64)
@@ -604,6 +635,7 @@ def calculate_snp_distances(args):
     with_compared = bool(getattr(args, "amdCompared", False))
     site_counts_file = getattr(args, "amdSiteCountsFile", None)
     cluster_snps_file = getattr(args, "amdClusterSnpsFile", None)
+    nj_file = getattr(args, "amdNjFile", None)
     if utils.verify_existing_input_files("SNP matrix file", [input_file]) > 0:
         utils.global_error("Error: cannot calculate sequence distances without the snp matrix file.")
     if close_file and max_pair_distance is None:
@@ -641,7 +673,7 @@ def calculate_snp_distances(args):
     if with_compared and not (close_file or mst_file or nearest_file):
         utils.global_error("Error: --amdCompared needs at least one of --amdClosePairs, --amdMst and --amdNearest.")
     outputs = [f for f in (pairwise_file, matrix_file, close_file, clusters_file, mst_file, dendrogram_file, close_sites_file, mst_sites_file, user_sites_file, nearest_file,
-                           compared_matrix_file, site_counts_file, cluster_snps_file) + linkage_files if f]
+                           compared_matrix_file, site_counts_file, cluster_snps_file, nj_file) + linkage_files if f]
     if not outputs:
         utils.global_error("Error: no output file specified.")
 
@@ -682,7 +714,7 @@ def calculate_snp_distances(args):
     if close_sites_file or mst_sites_file or user_sites_file:
         _distances_with_sites(default_device, file_ids, sym, lens, snp_list_file, pairwise_file, matrix_file, close_file, max_pair_distance, clusters_file, thresholds,
                               mst_file, dendrogram_file, close_sites_file, mst_sites_file, user_pairs_file, user_sites_file, linkage_kind, linkage_files, with_compared,
-                              cluster_snps_file, named_sites)
+                              cluster_snps_file, named_sites, nj_file)
         return
     dev = default_device()
     mat = None
@@ -716,6 +748,14 @@ def calculate_snp_distances(args):
             got = linkage_of_symbols(dev, file_ids, sym, lens, linkage_kind)
             ids, merges = got[0], got[1:]
         write_linkage_outputs(ids, linkage_kind, merges, linkage_files[0], linkage_files[1], linkage_files[2], thresholds)
+    if nj_file:
+        # as the linkage tree: from the matrix a table brought to the host, else built where the matrix is computed — alone, the
+        # n x n matrix never comes to the host; beside a tree, a threshold or a linkage that is one more computation of the matrix
+        if mat is not None:
+            nj_tree = dev.nj_of_matrix(mat)
+        else:
+            ids, nj_tree = nj_of_symbols(dev, file_ids, sym, lens)
+        write_nj(nj_file, ids, *nj_tree)
     if pairwise_file:
         write_pairwise(pairwise_file, ids, mat)
     if matrix_file:
@@ -753,7 +793,7 @@ def _write_nearest_output(device_of, file_ids, sym, lens, query_file, nearest_fi
 
 def _distances_with_sites(device_of, file_ids, sym, lens, snp_list_file, pairwise_file, matrix_file, close_file, max_pair_distance, clusters_file, thresholds,
                           mst_file, dendrogram_file, close_sites_file, mst_sites_file, user_pairs_file, user_sites_file, linkage_kind=None,
-                          linkage_files=(None, None, None), with_compared=False, cluster_snps_file=None, named_sites=None):
+                          linkage_files=(None, None, None), with_compared=False, cluster_snps_file=None, named_sites=None, nj_file=None):
     """calculate_snp_distances when the differing sites of some pairs are asked for: the symbols are uploaded and packed once; the
     matrix is computed once, and only when a tree, a threshold or a table needs it; the packed matrix stays on the device until
     every pair list has been answered from it.  The n x n matrix comes to the host for -p / -m alone."""
@@ -790,6 +830,8 @@ def _distances_with_sites(device_of, file_ids, sym, lens, snp_list_file, pairwis
         if linkage_kind:
             merges = dev.linkage_of_matrix(mat, linkage_kind) if mat is not None else dev.linkage(rows, linkage_kind)
             write_linkage_outputs(ids, linkage_kind, merges, linkage_files[0], linkage_files[1], linkage_files[2], thresholds)
+        if nj_file:
+            write_nj(nj_file, ids, *(dev.nj_of_matrix(mat) if mat is not None else dev.nj(rows)))
         if pairwise_file:
             write_pairwise(pairwise_file, ids, mat)
         if matrix_file:

@@ -246,6 +246,10 @@ class _Job(object):
             if self.cluster_thresholds:
                 self.outputs.update(linkage_clusters=os.path.join(work_dir, "snp_linkage_clusters.tsv"),
                                     linkage_clusters_p=os.path.join(work_dir, "snp_linkage_clusters_preserved.tsv"))
+        # --nj (additive to the distance step): the neighbour-joining tree as a Newick line
+        self.nj = bool(getattr(args, "nj", False))
+        if self.nj:
+            self.outputs.update(nj=os.path.join(work_dir, "snp_nj.nwk"), nj_p=os.path.join(work_dir, "snp_nj_preserved.nwk"))
         # --pairSites (additive to the distance step): the sites at which the close pairs / the tree's edges differ
         self.pair_sites = bool(getattr(args, "pairSites", False))
         if self.pair_sites and self.close_pairs is None and not self.mst:
@@ -1233,6 +1237,21 @@ def linkage_on_rank_0(torch, dev, comm, bands, dmat, full, n, kind):
     return tuple(w[:k].cpu().numpy().view(np.uint32) for w in words) + (num[:k].cpu().numpy().view(np.uint64),)
 
 
+def nj_on_rank_0(torch, dev, comm, bands, dmat, full, n):
+    """The neighbour-joining tree of the sorted samples, on rank 0 (None elsewhere), as Device.nj gives it: from the device matrix
+    when this is the only rank, else from the complete matrix rank 0 has gathered for the tables — exactly where
+    linkage_on_rank_0 gets its matrix.  The rounds work on one matrix, which is not distributed over the ranks."""
+    if comm.rank != 0:
+        return None
+    if comm.dist and n:
+        return dev.nj_of_matrix(full)
+    m = max(n - 3, 1)
+    a, b = (torch.zeros(m, dtype=torch.int32, device="cuda") for _ in range(2))
+    la, lb = (torch.zeros(m, dtype=torch.int64, device="cuda") for _ in range(2))
+    k, star, star_len = dev.nj_dev(dmat.data_ptr(), n, max(bands.n_padded, 1), a.data_ptr(), b.data_ptr(), la.data_ptr(), lb.data_ptr())
+    return a[:k].cpu().numpy().view(np.uint32), b[:k].cpu().numpy().view(np.uint32), la[:k].cpu().numpy(), lb[:k].cpu().numpy(), star, star_len
+
+
 def mst_over_ranks(torch, dev, comm, bands, dmat, band, n):
     """The minimum spanning tree of the whole n x n distance matrix as (u, v, dist) on rank 0, None on the others.  With one rank:
     from `dmat` (pitch bands.n_padded, n columns: the zero padding is never an edge).  With several: each rank builds the forest of
@@ -1367,6 +1386,11 @@ def stage_matrices_and_distances(job):
                     sfx = "" if flow == 1 else "_p"
                     dmod.write_linkage_outputs(ids, job.linkage, merges, outputs["linkage" + sfx], outputs["linkage_nwk" + sfx],
                                                outputs["linkage_clusters" + sfx] if job.cluster_thresholds else None, job.cluster_thresholds)
+        with job.guard() as go:
+            if go and job.nj:
+                nj_tree = nj_on_rank_0(torch, dev, comm, bands, dmat, full, n)
+                if rank == 0:
+                    dmod.write_nj(outputs["nj" if flow == 1 else "nj_p"], ids, *nj_tree)
         with job.guard() as go:
             # every rank holds packed_sorted after the all-gather: rank 0 asks it for the sites behind the gathered pairs and edges
             if go and rank == 0 and job.pair_sites:
@@ -1602,6 +1626,7 @@ def add_arguments(sub):
     sub.add_argument("--clusters", dest="clusters", type=int, nargs="+", default=None, metavar="INT", help="Also write snp_clusters.tsv and snp_clusters_preserved.tsv into the work directory: every sample's single-linkage cluster number at each of the SNP thresholds (as distance --amdClusters --amdClusterThresholds)")
     sub.add_argument("--mst", dest="mst", action="store_true", help="Also write snp_mst.tsv, snp_mst_preserved.tsv, snp_dendrogram.nwk and snp_dendrogram_preserved.nwk into the work directory: the minimum spanning tree of the samples and their single-linkage dendrogram, built on the device (as distance --amdMst --amdDendrogram)")
     sub.add_argument("--linkage", dest="linkage", type=str, choices=["complete", "average"], default=None, help="Also write snp_linkage.tsv, snp_linkage_preserved.tsv, snp_linkage.nwk and snp_linkage_preserved.nwk into the work directory: the merges and the dendrogram of the complete- or average-linkage tree of the samples (as distance --amdLinkage --amdLinkageMerges --amdLinkageDendrogram), and with --clusters snp_linkage_clusters.tsv and snp_linkage_clusters_preserved.tsv: the tree cut at each of the thresholds (as --amdLinkageClusters).  Built on the device of rank 0 from the complete matrix it gathers for the tables; the linkage itself is not distributed over the ranks")
+    sub.add_argument("--nj", dest="nj", action="store_true", help="Also write snp_nj.nwk and snp_nj_preserved.nwk into the work directory: the neighbour-joining tree of the samples as one Newick line with branch lengths in SNPs (as distance --amdNj).  Built on the device of rank 0 from the matrix the linkage tree would be built from; the rounds are not distributed over the ranks")
     sub.add_argument("--pairSites", dest="pairSites", action="store_true", help="With --closePairs: also write snp_close_pair_sites.tsv and snp_close_pair_sites_preserved.tsv, with --mst: snp_mst_sites.tsv and snp_mst_sites_preserved.tsv, into the work directory: the sites (Chrom and Pos of the flow's snplist) at which the two samples of every close pair i < j / of every tree edge differ, and their bases, found on the device (as distance --amdClosePairSites / --amdMstSites --amdSnpList)")
     sub.add_argument("--noConsensusVcf", dest="noConsensusVcf", action="store_true", help="Do not write consensus.vcf / consensus_preserved.vcf")
     sub.add_argument("--residentBytes", dest="residentBytes", type=int, default=0, metavar="INT", help="Device memory for resident pileups (0 = what is free, less 24 GiB); files past it are streamed twice in site calling mode device only: in modes existing and varscan --pileupRoute auto streams every pileup once instead")
