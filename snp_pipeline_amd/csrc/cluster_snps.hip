@@ -425,20 +425,6 @@ int cluster_snps_of_labels(snpgpu_ctx *ctx, const void *d_packed, uint32_t n_row
     return SNPGPU_OK;
 }
 
-// Uploads and packs the symbols into one allocation (*d_block, the caller's to free); *d_packed inside it, null without a cell.
-int packed_of_symbols(snpgpu_ctx *ctx, const uint8_t *symbols, uint32_t n_rows, uint32_t n_sites, void **d_block, void **d_packed) {
-    *d_block = *d_packed = nullptr;
-    const size_t sym_bytes = (size_t)n_rows * n_sites;
-    if (!sym_bytes) return SNPGPU_OK;
-    const size_t o_pack = up256(sym_bytes);
-    const hipError_t he = hipMalloc(d_block, o_pack + snpgpu_packed_row_bytes(n_sites) * n_rows + 256);
-    if (he != hipSuccess) return snpgpu_set_error(ctx, SNPGPU_E_NOMEM, "hipMalloc failed: %s", hipGetErrorString(he));
-    char *bytes = (char *)*d_block;
-    *d_packed = bytes + o_pack;
-    HIP_TRY(ctx, hipMemcpyAsync(bytes, symbols, sym_bytes, hipMemcpyHostToDevice, ctx->stream));
-    return snpgpu_pack_matrix_dev(ctx, (const uint8_t *)bytes, n_rows, n_sites, n_sites, *d_packed);
-}
-
 }  // namespace
 
 extern "C" {
@@ -465,18 +451,12 @@ int snpgpu_site_counts_host(snpgpu_ctx *ctx, const uint8_t *symbols, uint32_t n_
         return SNPGPU_OK;
     }
     HIP_TRY(ctx, snpgpu_enter(ctx));
-    void *d_block = nullptr, *d_packed = nullptr, *d_counts = nullptr;
-    hipError_t he = hipMalloc(&d_counts, (size_t)n_sites * 16);
-    if (he != hipSuccess) return snpgpu_set_error(ctx, SNPGPU_E_NOMEM, "hipMalloc failed: %s", hipGetErrorString(he));
-    int rc = packed_of_symbols(ctx, symbols, n_rows, n_sites, &d_block, &d_packed);
-    if (rc == SNPGPU_OK) rc = enqueue_site_counts(ctx, d_packed, n_rows, n_sites, (int32_t *)d_counts);
-    if (rc == SNPGPU_OK) he = hipMemcpyAsync(out_counts, d_counts, (size_t)n_sites * 16, hipMemcpyDeviceToHost, ctx->stream);
-    const hipError_t hs = hipStreamSynchronize(ctx->stream);
-    if (he == hipSuccess) he = hs;
-    (void)hipFree(d_block);
-    (void)hipFree(d_counts);
+    DevSymbols dev;                                             // the counts behind the symbols
+    int rc = dev.open(ctx, symbols, n_rows, n_sites, 0, nullptr, (size_t)n_sites * 16);
+    if (rc == SNPGPU_OK) rc = enqueue_site_counts(ctx, dev.packed(), n_rows, n_sites, (int32_t *)dev.extra());
     if (rc != SNPGPU_OK) return rc;
-    if (he != hipSuccess) return snpgpu_set_error(ctx, SNPGPU_E_HIP, "site counts failed: %s", hipGetErrorString(he));
+    HIP_TRY(ctx, hipMemcpyAsync(out_counts, dev.extra(), (size_t)n_sites * 16, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return SNPGPU_OK;
 }
 
@@ -510,7 +490,8 @@ int snpgpu_cluster_snps(snpgpu_ctx *ctx, const uint8_t *symbols, uint32_t n_rows
     if (capacity && (!out_cluster_off || !out_site || !out_base || !out_members)) return snpgpu_set_error(ctx, SNPGPU_E_ARG, "null cluster-SNPs output");
     HIP_TRY(ctx, snpgpu_enter(ctx));
     hipStream_t st = ctx->stream;
-    void *d_block = nullptr, *d_packed = nullptr, *d_lists = nullptr, *d_out = nullptr;
+    DevSymbols dev;
+    void *d_lists = nullptr, *d_out = nullptr;
     // labels of one labelling, the site counts (counted once), the offsets of every labelling; the entries when there is room
     const size_t b_labels = up256((size_t)n_rows * 4), b_counts = up256((size_t)n_sites * 16), b_coff = up256(n_offsets * 8);
     const size_t b_site = up256((size_t)capacity * 4);
@@ -525,7 +506,8 @@ int snpgpu_cluster_snps(snpgpu_ctx *ctx, const uint8_t *symbols, uint32_t n_rows
     uint64_t *d_coff = (uint64_t *)((char *)d_lists + b_labels + b_counts);
     uint32_t *d_site = (uint32_t *)d_out, *d_members = (uint32_t *)((char *)d_out + b_site);
     uint8_t *d_base = (uint8_t *)d_out + 2 * b_site;
-    int rc = packed_of_symbols(ctx, symbols, n_rows, n_sites, &d_block, &d_packed);
+    int rc = dev.open(ctx, symbols, n_rows, n_sites);
+    const void *d_packed = dev.packed();
     if (rc == SNPGPU_OK) he = hipMemsetAsync(d_coff, 0, n_offsets * 8, st);      // a labelling without room for an entry has none: its offsets stay 0
     const bool cells = n_rows && n_sites;
     if (rc == SNPGPU_OK && cells) rc = enqueue_site_counts(ctx, d_packed, n_rows, n_sites, d_counts);
@@ -552,7 +534,6 @@ int snpgpu_cluster_snps(snpgpu_ctx *ctx, const uint8_t *symbols, uint32_t n_rows
     }
     const hipError_t hs = hipStreamSynchronize(st);
     if (he == hipSuccess) he = hs;
-    (void)hipFree(d_block);
     (void)hipFree(d_lists);
     (void)hipFree(d_out);
     if (rc != SNPGPU_OK) return rc;

@@ -200,6 +200,34 @@ int close_pairs_emit(snpgpu_ctx *ctx, const int32_t *d_matrix, uint32_t n, uint6
 
 }  // namespace
 
+int snpgpu_close_pairs_to_host(snpgpu_ctx *ctx, const int32_t *d_matrix, uint32_t n, int32_t threshold, uint64_t capacity, uint64_t *out_row_off, uint32_t *out_col,
+                               int32_t *out_dist, uint64_t *out_n) {
+    uint64_t *d_off = nullptr, total = 0;
+    int rc = close_pairs_count(ctx, d_matrix, n, n, 0, n, threshold, &d_off, &total);
+    if (rc != SNPGPU_OK) return rc;
+    *out_n = total;
+    if (capacity == 0 || total > capacity) return SNPGPU_OK;
+    if (!out_row_off || (total && (!out_col || !out_dist))) return snpgpu_set_error(ctx, SNPGPU_E_ARG, "null close-pairs output");
+    void *d_csr = nullptr;                                          // only the CSR crosses the host link, never the matrix
+    if (total) {
+        const hipError_t hm = hipMalloc(&d_csr, total * 8);
+        if (hm != hipSuccess) return snpgpu_set_error(ctx, SNPGPU_E_NOMEM, "hipMalloc failed: %s", hipGetErrorString(hm));
+    }
+    uint32_t *d_col = (uint32_t *)d_csr;
+    int32_t *d_dist = (int32_t *)d_csr + total;
+    hipStream_t st = ctx->stream;
+    hipError_t he = hipSuccess;
+    rc = close_pairs_emit(ctx, d_matrix, n, n, 0, n, threshold, d_off, d_col, d_dist);
+    if (rc == SNPGPU_OK) he = hipMemcpyAsync(out_row_off, d_off, ((size_t)n + 1) * 8, hipMemcpyDeviceToHost, st);
+    if (rc == SNPGPU_OK && he == hipSuccess && total) he = hipMemcpyAsync(out_col, d_col, total * 4, hipMemcpyDeviceToHost, st);
+    if (rc == SNPGPU_OK && he == hipSuccess && total) he = hipMemcpyAsync(out_dist, d_dist, total * 4, hipMemcpyDeviceToHost, st);
+    const hipError_t hs = hipStreamSynchronize(st);
+    if (he == hipSuccess) he = hs;
+    (void)hipFree(d_csr);
+    if (he != hipSuccess) return snpgpu_set_error(ctx, SNPGPU_E_HIP, "close pairs failed: %s", hipGetErrorString(he));
+    return rc;
+}
+
 extern "C" {
 
 int snpgpu_close_pairs_dev(snpgpu_ctx *ctx, const int32_t *d_matrix, uint32_t n, uint64_t row_stride, uint32_t row_lo, uint32_t row_hi, int32_t threshold,
@@ -220,52 +248,9 @@ int snpgpu_close_pairs_dev(snpgpu_ctx *ctx, const int32_t *d_matrix, uint32_t n,
 
 int snpgpu_close_pairs(snpgpu_ctx *ctx, const uint8_t *symbols, uint32_t n_rows, uint32_t n_sites, int32_t threshold, uint64_t capacity,
                        uint64_t *out_row_off, uint32_t *out_col, int32_t *out_dist, uint64_t *out_n, int32_t *out_matrix) {
-    if (!ctx) return SNPGPU_E_ARG;
-    if (!out_n || (n_rows && n_sites && !symbols)) return snpgpu_set_error(ctx, SNPGPU_E_ARG, "null close-pairs argument");
-    HIP_TRY(ctx, snpgpu_enter(ctx));
-    *out_n = 0;
-    if (n_rows == 0) {
-        if (capacity && out_row_off) out_row_off[0] = 0;
-        return SNPGPU_OK;
-    }
-    const size_t sym_bytes = (size_t)n_rows * n_sites;
-    const size_t o_pack = (sym_bytes + 255) / 256 * 256;
-    const size_t o_mat = o_pack + (snpgpu_packed_row_bytes(n_sites) * n_rows + 255) / 256 * 256;
-    void *d = nullptr, *d_csr = nullptr;
-    hipError_t he = hipMalloc(&d, o_mat + (size_t)n_rows * n_rows * 4 + 256);
-    if (he != hipSuccess) return snpgpu_set_error(ctx, SNPGPU_E_NOMEM, "hipMalloc failed: %s", hipGetErrorString(he));
-    char *b = (char *)d;
-    hipStream_t st = ctx->stream;
-    int rc = SNPGPU_OK;
-    uint64_t *d_off = nullptr, total = 0;
-    if (sym_bytes) he = hipMemcpyAsync(b, symbols, sym_bytes, hipMemcpyHostToDevice, st);
-    if (he == hipSuccess && n_sites) rc = snpgpu_pack_matrix_dev(ctx, (const uint8_t *)b, n_rows, n_sites, n_sites, b + o_pack);
-    if (he == hipSuccess && rc == SNPGPU_OK) rc = snpgpu_distance_packed_dev(ctx, b + o_pack, n_rows, n_sites, 0, 1, (int32_t *)(b + o_mat));
-    if (he == hipSuccess && rc == SNPGPU_OK && out_matrix)        // the caller writes the reference's tables too: one matrix for both
-        he = hipMemcpyAsync(out_matrix, b + o_mat, (size_t)n_rows * n_rows * 4, hipMemcpyDeviceToHost, st);
-    if (he == hipSuccess && rc == SNPGPU_OK) rc = close_pairs_count(ctx, (const int32_t *)(b + o_mat), n_rows, n_rows, 0, n_rows, threshold, &d_off, &total);
-    if (he == hipSuccess && rc == SNPGPU_OK) {
-        *out_n = total;
-        if (capacity && total <= capacity) {                       // only the CSR crosses the host link, never the matrix
-            if (!out_row_off || (total && (!out_col || !out_dist))) rc = snpgpu_set_error(ctx, SNPGPU_E_ARG, "null close-pairs output");
-            if (rc == SNPGPU_OK && total) {
-                const hipError_t hm = hipMalloc(&d_csr, total * 8);
-                if (hm != hipSuccess) rc = snpgpu_set_error(ctx, SNPGPU_E_NOMEM, "hipMalloc failed: %s", hipGetErrorString(hm));
-            }
-            uint32_t *d_col = (uint32_t *)d_csr;
-            int32_t *d_dist = (int32_t *)d_csr + total;
-            if (rc == SNPGPU_OK) rc = close_pairs_emit(ctx, (const int32_t *)(b + o_mat), n_rows, n_rows, 0, n_rows, threshold, d_off, d_col, d_dist);
-            if (rc == SNPGPU_OK) he = hipMemcpyAsync(out_row_off, d_off, ((size_t)n_rows + 1) * 8, hipMemcpyDeviceToHost, st);
-            if (rc == SNPGPU_OK && he == hipSuccess && total) he = hipMemcpyAsync(out_col, d_col, total * 4, hipMemcpyDeviceToHost, st);
-            if (rc == SNPGPU_OK && he == hipSuccess && total) he = hipMemcpyAsync(out_dist, d_dist, total * 4, hipMemcpyDeviceToHost, st);
-        }
-    }
-    const hipError_t hs = hipStreamSynchronize(st);
-    if (he == hipSuccess) he = hs;
-    (void)hipFree(d_csr);
-    (void)hipFree(d);
-    if (he != hipSuccess) return snpgpu_set_error(ctx, SNPGPU_E_HIP, "close pairs failed: %s", hipGetErrorString(he));
-    return rc;
+    if (ctx && !out_n) return snpgpu_set_error(ctx, SNPGPU_E_ARG, "null close-pairs argument");
+    return snpgpu_distance_outputs(ctx, symbols, n_rows, n_sites, 0, nullptr, nullptr, nullptr, out_matrix, 1, threshold, capacity, out_row_off, out_col, out_dist,
+                                   out_n, 0);
 }
 
 int snpgpu_clusters_dev(snpgpu_ctx *ctx, uint32_t n, const uint64_t *d_row_off, const uint32_t *d_col, const int32_t *d_dist, uint64_t n_edges,

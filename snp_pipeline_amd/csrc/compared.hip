@@ -183,24 +183,6 @@ __global__ __launch_bounds__(CMP_THREADS) void k_compared_pairs(const uint4 *pa,
     }
 }
 
-inline size_t up256(size_t x) { return (x + 255) / 256 * 256; }
-
-// Uploads and packs the symbols (n x n_sites, both not 0) and extracts the plane, all enqueued on the context's stream: *d_block
-// is the allocation (the caller's to free once the stream has passed its work), *d_plane the plane inside it.
-int plane_of_symbols(snpgpu_ctx *ctx, const uint8_t *symbols, uint32_t n, uint32_t n_sites, void **d_block, void **d_plane) {
-    const size_t b_sym = up256((size_t)n * n_sites), b_pack = up256(snpgpu_packed_row_bytes(n_sites) * n);
-    void *d = nullptr;
-    const hipError_t he = hipMalloc(&d, b_sym + b_pack + snpgpu_valid_plane_row_bytes(n_sites) * n + 256);
-    if (he != hipSuccess) return snpgpu_set_error(ctx, SNPGPU_E_NOMEM, "hipMalloc failed: %s", hipGetErrorString(he));
-    *d_block = d;
-    char *b = (char *)d;
-    *d_plane = b + b_sym + b_pack;
-    HIP_TRY(ctx, hipMemcpyAsync(b, symbols, (size_t)n * n_sites, hipMemcpyHostToDevice, ctx->stream));
-    int rc = snpgpu_pack_matrix_dev(ctx, (const uint8_t *)b, n, n_sites, n_sites, b + b_sym);
-    if (rc == SNPGPU_OK) rc = snpgpu_valid_plane_dev(ctx, b + b_sym, n, n_sites, *d_plane);
-    return rc;
-}
-
 }  // namespace
 
 extern "C" {
@@ -289,18 +271,12 @@ int snpgpu_compared(snpgpu_ctx *ctx, const uint8_t *symbols, uint32_t n, uint32_
     if (!out_matrix || (n_sites && !symbols)) return snpgpu_set_error(ctx, SNPGPU_E_ARG, "null compared argument");
     HIP_TRY(ctx, snpgpu_enter(ctx));
     const size_t out_bytes = (size_t)n * n * 4;
-    void *d_block = nullptr, *d_plane = nullptr, *d_out = nullptr;
-    hipError_t he = hipMalloc(&d_out, out_bytes);
-    if (he != hipSuccess) return snpgpu_set_error(ctx, SNPGPU_E_NOMEM, "hipMalloc failed: %s", hipGetErrorString(he));
-    int rc = n_sites ? plane_of_symbols(ctx, symbols, n, n_sites, &d_block, &d_plane) : SNPGPU_OK;
-    if (rc == SNPGPU_OK) rc = snpgpu_compared_rect_dev(ctx, d_plane, n, d_plane, n, n_sites, (int32_t *)d_out, n);
-    if (rc == SNPGPU_OK) he = hipMemcpyAsync(out_matrix, d_out, out_bytes, hipMemcpyDeviceToHost, ctx->stream);
-    const hipError_t hs = hipStreamSynchronize(ctx->stream);
-    if (he == hipSuccess) he = hs;
-    (void)hipFree(d_block);
-    (void)hipFree(d_out);
+    DevSymbols dev;
+    int rc = dev.open(ctx, symbols, n, n_sites, DevSymbols::PLANE, nullptr, out_bytes);
+    if (rc == SNPGPU_OK) rc = snpgpu_compared_rect_dev(ctx, dev.plane(), n, dev.plane(), n, n_sites, (int32_t *)dev.extra(), n);
     if (rc != SNPGPU_OK) return rc;
-    if (he != hipSuccess) return snpgpu_set_error(ctx, SNPGPU_E_HIP, "compared failed: %s", hipGetErrorString(he));
+    HIP_TRY(ctx, hipMemcpyAsync(out_matrix, dev.extra(), out_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return SNPGPU_OK;
 }
 
@@ -320,25 +296,18 @@ int snpgpu_compared_pairs(snpgpu_ctx *ctx, const uint8_t *symbols_a, uint32_t n_
         return SNPGPU_OK;
     }
     hipStream_t st = ctx->stream;
-    void *d_block_a = nullptr, *d_block_b = nullptr, *d_plane_a = nullptr, *d_plane_b = nullptr, *d_lists = nullptr;
-    hipError_t he = hipMalloc(&d_lists, (size_t)n_pairs * 12);
-    if (he != hipSuccess) return snpgpu_set_error(ctx, SNPGPU_E_NOMEM, "hipMalloc failed: %s", hipGetErrorString(he));
-    uint32_t *d_a = (uint32_t *)d_lists, *d_b = d_a + n_pairs;
-    int32_t *d_out = (int32_t *)(d_b + n_pairs);
-    int rc = plane_of_symbols(ctx, symbols_a, n_a, n_sites, &d_block_a, &d_plane_a);
-    if (rc == SNPGPU_OK && symbols_b) rc = plane_of_symbols(ctx, symbols_b, n_b, n_sites, &d_block_b, &d_plane_b);
-    if (rc == SNPGPU_OK) he = hipMemcpyAsync(d_a, a, (size_t)n_pairs * 4, hipMemcpyHostToDevice, st);
-    if (rc == SNPGPU_OK && he == hipSuccess) he = hipMemcpyAsync(d_b, b, (size_t)n_pairs * 4, hipMemcpyHostToDevice, st);
-    if (rc == SNPGPU_OK && he == hipSuccess)
-        rc = snpgpu_compared_pairs_dev(ctx, d_plane_a, n_a, symbols_b ? d_plane_b : d_plane_a, n_b, n_sites, d_a, d_b, n_pairs, d_out);
-    if (rc == SNPGPU_OK && he == hipSuccess) he = hipMemcpyAsync(out, d_out, (size_t)n_pairs * 4, hipMemcpyDeviceToHost, st);
-    const hipError_t hs = hipStreamSynchronize(st);
-    if (he == hipSuccess) he = hs;
-    (void)hipFree(d_block_a);
-    (void)hipFree(d_block_b);
-    (void)hipFree(d_lists);
+    DevSymbols dev_a, dev_b;                                    // the lists and the counts behind the first plane
+    int rc = dev_a.open(ctx, symbols_a, n_a, n_sites, DevSymbols::PLANE, nullptr, (size_t)n_pairs * 12);
+    if (rc == SNPGPU_OK && symbols_b) rc = dev_b.open(ctx, symbols_b, n_b, n_sites, DevSymbols::PLANE);
     if (rc != SNPGPU_OK) return rc;
-    if (he != hipSuccess) return snpgpu_set_error(ctx, SNPGPU_E_HIP, "compared pairs failed: %s", hipGetErrorString(he));
+    uint32_t *d_a = (uint32_t *)dev_a.extra(), *d_b = d_a + n_pairs;
+    int32_t *d_out = (int32_t *)(d_b + n_pairs);
+    HIP_TRY(ctx, hipMemcpyAsync(d_a, a, (size_t)n_pairs * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(d_b, b, (size_t)n_pairs * 4, hipMemcpyHostToDevice, st));
+    rc = snpgpu_compared_pairs_dev(ctx, dev_a.plane(), n_a, symbols_b ? dev_b.plane() : dev_a.plane(), n_b, n_sites, d_a, d_b, n_pairs, d_out);
+    if (rc != SNPGPU_OK) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(out, d_out, (size_t)n_pairs * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
     return SNPGPU_OK;
 }
 

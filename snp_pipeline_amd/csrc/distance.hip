@@ -239,26 +239,51 @@ int snpgpu_distance(snpgpu_ctx *ctx, const uint8_t *symbols, uint32_t n_rows, ui
     if (n_rows == 0) return SNPGPU_OK;
     if (!out || (n_sites && !symbols)) return snpgpu_set_error(ctx, SNPGPU_E_ARG, "null distance argument");
     HIP_TRY(ctx, snpgpu_enter(ctx));
-    size_t sym_bytes = (size_t)n_rows * n_sites;
-    size_t o_pack = (sym_bytes + 255) / 256 * 256;
-    size_t pack_bytes = snpgpu_packed_row_bytes(n_sites) * n_rows;
-    size_t o_out = o_pack + (pack_bytes + 255) / 256 * 256;
-    size_t out_bytes = (size_t)n_rows * n_rows * 4;
-    void *d = nullptr;
-    hipError_t e = hipMalloc(&d, o_out + out_bytes + 256);
-    if (e != hipSuccess) return snpgpu_set_error(ctx, SNPGPU_E_NOMEM, "hipMalloc failed: %s", hipGetErrorString(e));
-    char *b = (char *)d;
-    hipStream_t st = ctx->stream;
-    int rc = SNPGPU_OK;
-    hipError_t he = hipSuccess;
-    if (sym_bytes) he = hipMemcpyAsync(b, symbols, sym_bytes, hipMemcpyHostToDevice, st);
-    if (he == hipSuccess && n_sites) rc = snpgpu_pack_matrix_dev(ctx, (const uint8_t *)b, n_rows, n_sites, n_sites, b + o_pack);
-    if (he == hipSuccess && rc == SNPGPU_OK) rc = snpgpu_distance_packed_dev(ctx, b + o_pack, n_rows, n_sites, 0, 1, (int32_t *)(b + o_out));
-    if (he == hipSuccess && rc == SNPGPU_OK) he = hipMemcpyAsync(out, b + o_out, out_bytes, hipMemcpyDeviceToHost, st);
-    if (he == hipSuccess) he = hipStreamSynchronize(st);
-    (void)hipFree(d);
-    if (he != hipSuccess) return snpgpu_set_error(ctx, SNPGPU_E_HIP, "distance failed: %s", hipGetErrorString(he));
-    return rc;
+    DevSymbols dev;
+    const int rc = dev.open(ctx, symbols, n_rows, n_sites, DevSymbols::MATRIX, out);
+    if (rc != SNPGPU_OK) return rc;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return SNPGPU_OK;
 }
 
 }  // extern "C"
+
+int DevSymbols::open(snpgpu_ctx *c, const uint8_t *symbols, uint32_t n_rows, uint32_t n_sites, int want, int32_t *out_matrix, size_t extra_bytes) {
+    ctx = c;
+    if (n_rows == 0) return SNPGPU_OK;
+    auto up = [](size_t x) { return (x + 255) / 256 * 256; };
+    const size_t sym_bytes = (size_t)n_rows * n_sites, mat_bytes = want & MATRIX ? (size_t)n_rows * n_rows * 4 : 0;
+    const size_t o_mat = up(sym_bytes), o_plane = o_mat + up(mat_bytes);
+    const size_t o_extra = o_plane + up(want & PLANE ? snpgpu_valid_plane_row_bytes(n_sites) * n_rows : 0);
+    hipError_t he = hipMalloc(&block, o_extra + extra_bytes + 256);
+    if (he == hipSuccess) he = hipMalloc(&pack, snpgpu_packed_row_bytes(n_sites) * n_rows + 256);   // (read with 16-byte loads past the last word)
+    if (he != hipSuccess) return snpgpu_set_error(ctx, SNPGPU_E_NOMEM, "hipMalloc failed: %s", hipGetErrorString(he));
+    char *b = (char *)block;
+    mat = (int32_t *)(b + o_mat);
+    pl = b + o_plane;
+    ext = b + o_extra;
+    int rc = SNPGPU_OK;
+    if (sym_bytes) {
+        HIP_TRY(ctx, hipMemcpyAsync(b, symbols, sym_bytes, hipMemcpyHostToDevice, ctx->stream));
+        rc = snpgpu_pack_matrix_dev(ctx, (const uint8_t *)b, n_rows, n_sites, n_sites, pack);
+    }
+    if (rc == SNPGPU_OK && (want & MATRIX)) {
+        rc = snpgpu_distance_packed_dev(ctx, pack, n_rows, n_sites, 0, 1, mat);
+        if (rc == SNPGPU_OK && out_matrix) HIP_TRY(ctx, hipMemcpyAsync(out_matrix, mat, mat_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    if (rc == SNPGPU_OK && (want & PLANE)) rc = snpgpu_valid_plane_dev(ctx, pack, n_rows, n_sites, pl);
+    return rc;
+}
+
+void *DevSymbols::release_packed() {
+    void *p = pack;
+    pack = nullptr;
+    return p;
+}
+
+DevSymbols::~DevSymbols() {
+    if (!block && !pack) return;
+    (void)hipStreamSynchronize(ctx->stream);
+    (void)hipFree(block);
+    (void)hipFree(pack);
+}

@@ -277,6 +277,35 @@ int snpgpu_scratch(snpgpu_ctx *ctx, size_t bytes, void **out);
                                     hipGetErrorString(e_), __FILE__, __LINE__);                         \
     } while (0)
 
+// The symbols of a host form on the device (distance.hip).  open() allocates, enqueues the upload and the pack on the context's
+// stream and, on request, k_distance into matrix() (ranks 0 of 1; copied to out_matrix where that is given) and the valid plane;
+// extra() is extra_bytes of the caller's own, 256-byte aligned.  Without a row nothing is allocated and every pointer is null;
+// without a column nothing is uploaded or packed and the matrix is still written.  The destructor waits for the stream, then
+// frees: a host form returns at any point and leaks nothing.  The packed matrix is an allocation of its own, so that
+// release_packed() can hand it on (the caller has waited for the stream).
+struct DevSymbols {
+    enum { MATRIX = 1, PLANE = 2 };
+    DevSymbols() = default;
+    DevSymbols(const DevSymbols &) = delete;
+    DevSymbols &operator=(const DevSymbols &) = delete;
+    ~DevSymbols();
+    int open(snpgpu_ctx *ctx, const uint8_t *symbols, uint32_t n_rows, uint32_t n_sites, int want = 0, int32_t *out_matrix = nullptr, size_t extra_bytes = 0);
+    const void *packed() const { return pack; }
+    int32_t *matrix() const { return mat; }
+    void *plane() const { return pl; }
+    char *extra() const { return ext; }
+    void *release_packed();
+private:
+    snpgpu_ctx *ctx = nullptr;
+    void *block = nullptr, *pack = nullptr;     // symbols | matrix | plane | extra, and the packed matrix
+    int32_t *mat = nullptr;
+    void *pl = nullptr;
+    char *ext = nullptr;
+};
+// clusters.hip: the close pairs of a device matrix as a CSR in HOST arrays: one count pass; the entries when capacity has room for them
+int snpgpu_close_pairs_to_host(snpgpu_ctx *ctx, const int32_t *d_matrix, uint32_t n, int32_t threshold, uint64_t capacity, uint64_t *out_row_off, uint32_t *out_col,
+                               int32_t *out_dist, uint64_t *out_n);
+
 // ---- byte classes -----------------------------------------------------------------------------
 // What str.split() treats as a separator, restricted to ASCII (pileup.py:206/424).
 __device__ __forceinline__ bool is_ws(uint32_t c) { return (c - 9u <= 4u) || (c - 28u <= 4u); }

@@ -324,70 +324,33 @@ int snpgpu_distance_outputs(snpgpu_ctx *ctx, const uint8_t *symbols, uint32_t n_
         if (want_pairs && capacity && out_row_off) out_row_off[0] = 0;
         return SNPGPU_OK;
     }
-    const size_t sym_bytes = (size_t)n_rows * n_sites;
-    const size_t o_mat = (sym_bytes + 255) / 256 * 256;
-    const size_t o_edges = o_mat + ((size_t)n_rows * n_rows * 4 + 255) / 256 * 256;
-    const size_t o_off = o_edges + ((size_t)n_rows * 12 + 255) / 256 * 256;
-    void *d = nullptr, *d_csr = nullptr, *d_pack = nullptr;      // the packed matrix apart: it may outlive the call
-    hipError_t he = hipMalloc(&d, o_off + ((size_t)n_rows + 1) * 8 + 256);
-    if (he == hipSuccess) he = hipMalloc(&d_pack, snpgpu_packed_row_bytes(n_sites) * n_rows + 256);
-    if (he != hipSuccess) {
-        (void)hipFree(d);
-        return snpgpu_set_error(ctx, SNPGPU_E_NOMEM, "hipMalloc failed: %s", hipGetErrorString(he));
-    }
-    char *b = (char *)d;
-    const int32_t *d_mat = (const int32_t *)(b + o_mat);
-    uint32_t *d_u = (uint32_t *)(b + o_edges), *d_v = d_u + n_rows;
-    int32_t *d_dist = (int32_t *)(d_v + n_rows);
-    uint64_t *d_off = (uint64_t *)(b + o_off);
+    DevSymbols dev;                                             // the tree's edges behind the matrix
+    int rc = dev.open(ctx, symbols, n_rows, n_sites, DevSymbols::MATRIX, out_matrix, (size_t)n_rows * 12);
+    if (rc != SNPGPU_OK) return rc;
     hipStream_t st = ctx->stream;
-    int rc = SNPGPU_OK;
-    uint32_t n_edges = 0, rounds = 0;
-    if (sym_bytes) he = hipMemcpyAsync(b, symbols, sym_bytes, hipMemcpyHostToDevice, st);
-    if (he == hipSuccess && n_sites) rc = snpgpu_pack_matrix_dev(ctx, (const uint8_t *)b, n_rows, n_sites, n_sites, d_pack);
-    if (he == hipSuccess && rc == SNPGPU_OK) rc = snpgpu_distance_packed_dev(ctx, d_pack, n_rows, n_sites, 0, 1, (int32_t *)(b + o_mat));
-    if (he == hipSuccess && rc == SNPGPU_OK && out_matrix)        // the caller writes the reference's tables too: one matrix for all
-        he = hipMemcpyAsync(out_matrix, d_mat, (size_t)n_rows * n_rows * 4, hipMemcpyDeviceToHost, st);
-    if (he == hipSuccess && rc == SNPGPU_OK && want_tree) rc = snpgpu_mst_dev(ctx, d_mat, n_rows, n_rows, 0, n_rows, d_u, d_v, d_dist, &n_edges, &rounds);
-    if (he == hipSuccess && rc == SNPGPU_OK && want_tree && n_edges != n_rows - 1) rc = snpgpu_set_error(ctx, SNPGPU_E_HIP, "the tree of %u samples has %u edges", n_rows, n_edges);
-    if (he == hipSuccess && rc == SNPGPU_OK && n_edges) {          // only the tree crosses the host link, never the matrix
-        he = hipMemcpyAsync(out_u, d_u, (size_t)n_edges * 4, hipMemcpyDeviceToHost, st);
-        if (he == hipSuccess) he = hipMemcpyAsync(out_v, d_v, (size_t)n_edges * 4, hipMemcpyDeviceToHost, st);
-        if (he == hipSuccess) he = hipMemcpyAsync(out_dist, d_dist, (size_t)n_edges * 4, hipMemcpyDeviceToHost, st);
-    }
-    if (he == hipSuccess && rc == SNPGPU_OK && want_pairs) {       // the close pairs of the same matrix: count, then (when they fit) the CSR
-        uint64_t total = 0;
-        rc = snpgpu_close_pairs_dev(ctx, d_mat, n_rows, n_rows, 0, n_rows, threshold, 0, nullptr, nullptr, nullptr, &total);
-        if (rc == SNPGPU_OK) {
-            *out_n = total;
-            if (capacity && total <= capacity) {
-                if (!out_row_off || (total && (!out_col || !out_pair_dist))) rc = snpgpu_set_error(ctx, SNPGPU_E_ARG, "null close-pairs output");
-                if (rc == SNPGPU_OK && total) {
-                    const hipError_t hm = hipMalloc(&d_csr, total * 8);
-                    if (hm != hipSuccess) rc = snpgpu_set_error(ctx, SNPGPU_E_NOMEM, "hipMalloc failed: %s", hipGetErrorString(hm));
-                }
-                uint32_t *d_col = (uint32_t *)d_csr;
-                int32_t *d_pd = (int32_t *)d_csr + total;
-                if (rc == SNPGPU_OK) rc = snpgpu_close_pairs_dev(ctx, d_mat, n_rows, n_rows, 0, n_rows, threshold, total ? total : 1, d_off, d_col, d_pd, &total);
-                if (rc == SNPGPU_OK) he = hipMemcpyAsync(out_row_off, d_off, ((size_t)n_rows + 1) * 8, hipMemcpyDeviceToHost, st);
-                if (rc == SNPGPU_OK && he == hipSuccess && total) he = hipMemcpyAsync(out_col, d_col, total * 4, hipMemcpyDeviceToHost, st);
-                if (rc == SNPGPU_OK && he == hipSuccess && total) he = hipMemcpyAsync(out_pair_dist, d_pd, total * 4, hipMemcpyDeviceToHost, st);
-            }
+    if (want_tree) {
+        uint32_t *d_u = (uint32_t *)dev.extra(), *d_v = d_u + n_rows, n_edges = 0, rounds = 0;
+        int32_t *d_dist = (int32_t *)(d_v + n_rows);
+        rc = snpgpu_mst_dev(ctx, dev.matrix(), n_rows, n_rows, 0, n_rows, d_u, d_v, d_dist, &n_edges, &rounds);
+        if (rc != SNPGPU_OK) return rc;
+        if (n_edges != n_rows - 1) return snpgpu_set_error(ctx, SNPGPU_E_HIP, "the tree of %u samples has %u edges", n_rows, n_edges);
+        if (n_edges) {                                          // only the tree crosses the host link, never the matrix
+            HIP_TRY(ctx, hipMemcpyAsync(out_u, d_u, (size_t)n_edges * 4, hipMemcpyDeviceToHost, st));
+            HIP_TRY(ctx, hipMemcpyAsync(out_v, d_v, (size_t)n_edges * 4, hipMemcpyDeviceToHost, st));
+            HIP_TRY(ctx, hipMemcpyAsync(out_dist, d_dist, (size_t)n_edges * 4, hipMemcpyDeviceToHost, st));
         }
     }
-    const hipError_t hs = hipStreamSynchronize(st);
-    if (he == hipSuccess) he = hs;
-    (void)hipFree(d_csr);
-    (void)hipFree(d);
-    if (keep_packed && he == hipSuccess && rc == SNPGPU_OK) {
-        ctx->kept_packed = d_pack;
+    if (want_pairs) {                                           // the close pairs of the same matrix
+        rc = snpgpu_close_pairs_to_host(ctx, dev.matrix(), n_rows, threshold, capacity, out_row_off, out_col, out_pair_dist, out_n);
+        if (rc != SNPGPU_OK) return rc;
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    if (keep_packed) {
+        ctx->kept_packed = dev.release_packed();
         ctx->kept_rows = n_rows;
         ctx->kept_sites = n_sites;
-    } else {
-        (void)hipFree(d_pack);
     }
-    if (he != hipSuccess) return snpgpu_set_error(ctx, SNPGPU_E_HIP, "mst failed: %s", hipGetErrorString(he));
-    return rc;
+    return SNPGPU_OK;
 }
 
 int snpgpu_mst_close_pairs(snpgpu_ctx *ctx, const uint8_t *symbols, uint32_t n_rows, uint32_t n_sites, uint32_t *out_u, uint32_t *out_v, int32_t *out_dist,

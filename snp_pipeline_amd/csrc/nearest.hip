@@ -446,31 +446,22 @@ int snpgpu_nearest(snpgpu_ctx *ctx, const uint8_t *q_symbols, uint32_t q, const 
     size_t free_b = 0, total_b = 0;
     HIP_TRY(ctx, hipMemGetInfo(&free_b, &total_b));
     const size_t row_b = snpgpu_packed_row_bytes(n_sites);
-    auto up = [](size_t x) { return (x + 255) / 256 * 256; };
-    const size_t b_dbs = up((size_t)n * n_sites), b_qs = up((size_t)q * n_sites), b_dbp = up(row_b * n), b_qp = up(row_b * q);
     if (band_rows == 0) {                                       // the largest band whose matrix stays within a quarter of the free memory
         const uint64_t fit = (uint64_t)(free_b / 4) / ((uint64_t)n * 4);
         band_rows = (uint32_t)(fit < 1 ? 1 : fit < q ? fit : q);
     }
     if (band_rows > q) band_rows = q;
-    const size_t b_mat = up((size_t)band_rows * n * 4);
-    void *d = nullptr, *d_csr = nullptr;
-    hipError_t he = hipMalloc(&d, b_dbs + b_qs + b_dbp + b_qp + b_mat + 256);
-    if (he != hipSuccess) return snpgpu_set_error(ctx, SNPGPU_E_NOMEM, "hipMalloc failed: %s", hipGetErrorString(he));
-    char *b = (char *)d;
-    uint8_t *d_dbs = (uint8_t *)b, *d_qs = d_dbs + b_dbs;
-    char *d_dbp = (char *)(d_qs + b_qs), *d_qp = d_dbp + b_dbp;
-    int32_t *d_mat = (int32_t *)(d_qp + b_qp);
+    DevSymbols dev_db, dev_q;                                   // both matrices are uploaded and packed once; the band's matrix behind the database
+    int rc = dev_db.open(ctx, db_symbols, n, n_sites, 0, nullptr, (size_t)band_rows * n * 4);
+    if (rc == SNPGPU_OK) rc = dev_q.open(ctx, q_symbols, q, n_sites);
+    if (rc != SNPGPU_OK) return rc;
+    const char *d_dbp = (const char *)dev_db.packed(), *d_qp = (const char *)dev_q.packed();
+    int32_t *d_mat = (int32_t *)dev_db.extra();
+    void *d_csr = nullptr;
+    hipError_t he = hipSuccess;
     hipStream_t st = ctx->stream;
-    int rc = SNPGPU_OK;
     uint64_t csr_room = 0, running = 0;
     std::vector<uint64_t> h_off((size_t)band_rows + 1);
-    if (n_sites) {                                              // both matrices are uploaded and packed once
-        he = hipMemcpyAsync(d_dbs, db_symbols, (size_t)n * n_sites, hipMemcpyHostToDevice, st);
-        if (he == hipSuccess) he = hipMemcpyAsync(d_qs, q_symbols, (size_t)q * n_sites, hipMemcpyHostToDevice, st);
-        if (he == hipSuccess) rc = snpgpu_pack_matrix_dev(ctx, d_dbs, n, n_sites, n_sites, d_dbp);
-        if (he == hipSuccess && rc == SNPGPU_OK) rc = snpgpu_pack_matrix_dev(ctx, d_qs, q, n_sites, n_sites, d_qp);
-    }
     if (capacity) out_row_off[0] = 0;
     for (uint32_t lo = 0; lo < q && he == hipSuccess && rc == SNPGPU_OK; lo += band_rows) {      // queries are independent: banding is exact
         const uint32_t rows = q - lo < band_rows ? q - lo : band_rows;
@@ -511,7 +502,6 @@ int snpgpu_nearest(snpgpu_ctx *ctx, const uint8_t *q_symbols, uint32_t q, const 
     const hipError_t hs = hipStreamSynchronize(st);
     if (he == hipSuccess) he = hs;
     (void)hipFree(d_csr);
-    (void)hipFree(d);
     if (he != hipSuccess) return snpgpu_set_error(ctx, SNPGPU_E_HIP, "nearest failed: %s", hipGetErrorString(he));
     if (rc == SNPGPU_OK) *out_n = running;
     return rc;

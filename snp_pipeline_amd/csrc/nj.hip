@@ -461,31 +461,12 @@ int snpgpu_nj(snpgpu_ctx *ctx, const uint8_t *symbols, uint32_t n_rows, uint32_t
     no_star(out_star, out_star_len);
     if (n_rows == 0) return SNPGPU_OK;
     HIP_TRY(ctx, snpgpu_enter(ctx));
-    const size_t sym_bytes = (size_t)n_rows * n_sites;
-    const size_t o_mat = (sym_bytes + 255) / 256 * 256, mat_bytes = (size_t)n_rows * n_rows * 4;
-    void *d = nullptr, *d_pack = nullptr;
-    hipError_t he = hipMalloc(&d, o_mat + mat_bytes + 256);
-    if (he == hipSuccess) he = hipMalloc(&d_pack, snpgpu_packed_row_bytes(n_sites) * n_rows + 256);
-    if (he != hipSuccess) {
-        (void)hipFree(d);
-        return snpgpu_set_error(ctx, SNPGPU_E_NOMEM, "hipMalloc failed: %s", hipGetErrorString(he));
-    }
-    char *b = (char *)d;
-    int32_t *d_mat = (int32_t *)(b + o_mat);
-    hipStream_t st = ctx->stream;
-    int rc = SNPGPU_OK;
-    if (sym_bytes) he = hipMemcpyAsync(b, symbols, sym_bytes, hipMemcpyHostToDevice, st);
-    if (he == hipSuccess && n_sites) rc = snpgpu_pack_matrix_dev(ctx, (const uint8_t *)b, n_rows, n_sites, n_sites, d_pack);
-    if (he == hipSuccess && rc == SNPGPU_OK) rc = snpgpu_distance_packed_dev(ctx, d_pack, n_rows, n_sites, 0, 1, d_mat);
-    if (he == hipSuccess && rc == SNPGPU_OK && out_matrix) he = hipMemcpyAsync(out_matrix, d_mat, mat_bytes, hipMemcpyDeviceToHost, st);
-    if (he == hipSuccess && rc == SNPGPU_OK && n_rows > 1)                                                        // only the tree crosses the host link
-        rc = nj_run_to_host(ctx, d_mat, n_rows, n_rows, out_a, out_b, out_len_a, out_len_b, out_star, out_star_len);
-    const hipError_t hs = hipStreamSynchronize(st);
-    if (he == hipSuccess) he = hs;
-    (void)hipFree(d);
-    (void)hipFree(d_pack);
-    if (he != hipSuccess) return snpgpu_set_error(ctx, SNPGPU_E_HIP, "neighbour joining failed: %s", hipGetErrorString(he));
+    DevSymbols dev;
+    int rc = dev.open(ctx, symbols, n_rows, n_sites, DevSymbols::MATRIX, out_matrix);
+    if (rc == SNPGPU_OK && n_rows > 1)                                                                            // only the tree crosses the host link
+        rc = nj_run_to_host(ctx, dev.matrix(), n_rows, n_rows, out_a, out_b, out_len_a, out_len_b, out_star, out_star_len);
     if (rc != SNPGPU_OK) { no_star(out_star, out_star_len); return rc; }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     *out_n_merges = n_rows > 3 ? n_rows - 3 : 0;
     return SNPGPU_OK;
 }

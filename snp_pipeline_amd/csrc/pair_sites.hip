@@ -200,22 +200,12 @@ int snpgpu_pair_sites(snpgpu_ctx *ctx, const uint8_t *symbols, uint32_t n_rows, 
     if (!ctx) return SNPGPU_E_ARG;
     if (!out_n || (n_rows && n_sites && !symbols) || (n_pairs && (!a || !b))) return snpgpu_set_error(ctx, SNPGPU_E_ARG, "null pair-sites argument");
     HIP_TRY(ctx, snpgpu_enter(ctx));
-    const size_t sym_bytes = (size_t)n_rows * n_sites;
-    const size_t o_pack = (sym_bytes + 255) / 256 * 256;
-    void *d = nullptr;
-    hipError_t he = hipMalloc(&d, o_pack + snpgpu_packed_row_bytes(n_sites) * n_rows + 256);
-    if (he != hipSuccess) return snpgpu_set_error(ctx, SNPGPU_E_NOMEM, "hipMalloc failed: %s", hipGetErrorString(he));
-    char *bytes = (char *)d;
-    int rc = SNPGPU_OK;
-    if (sym_bytes) he = hipMemcpyAsync(bytes, symbols, sym_bytes, hipMemcpyHostToDevice, ctx->stream);
-    if (he == hipSuccess && sym_bytes) rc = snpgpu_pack_matrix_dev(ctx, (const uint8_t *)bytes, n_rows, n_sites, n_sites, bytes + o_pack);
-    if (he == hipSuccess && rc == SNPGPU_OK)
-        rc = pair_sites_of_lists(ctx, bytes + o_pack, n_rows, n_sites, a, b, n_pairs, capacity, out_pair_off, out_site, out_bases, out_n);
-    const hipError_t hs = hipStreamSynchronize(ctx->stream);
-    if (he == hipSuccess) he = hs;
-    (void)hipFree(d);
-    if (he != hipSuccess) return snpgpu_set_error(ctx, SNPGPU_E_HIP, "pair sites failed: %s", hipGetErrorString(he));
-    return rc;
+    DevSymbols dev;
+    int rc = dev.open(ctx, symbols, n_rows, n_sites);
+    if (rc == SNPGPU_OK) rc = pair_sites_of_lists(ctx, dev.packed(), n_rows, n_sites, a, b, n_pairs, capacity, out_pair_off, out_site, out_bases, out_n);
+    if (rc != SNPGPU_OK) return rc;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return SNPGPU_OK;
 }
 
 int snpgpu_pair_sites_kept(snpgpu_ctx *ctx, const uint32_t *a, const uint32_t *b, uint64_t n_pairs, uint64_t capacity, uint64_t *out_pair_off, uint32_t *out_site,

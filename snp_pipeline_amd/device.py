@@ -1079,6 +1079,34 @@ class Device(object):
                                                     int(capacity), opt(d_row_off), opt(d_col), opt(d_dist), C.byref(out_n)))
         return int(out_n.value)
 
+    def _grow_to_fit(self, cap, dtypes, call):
+        """The capacity protocol of the CSR host forms: call(cap, arrays, out_n, first) with room for `cap` entries in one new
+        array per dtype; while the answer holds more, room for exactly that many and another call (first is then False: a matrix
+        is fetched by the first call only).  Returns the arrays cut to the entries."""
+        first = True
+        while True:
+            arrays = [np.zeros(max(cap, 1), dtype=t) for t in dtypes]
+            out_n = C.c_uint64(0)
+            self._check(call(cap, arrays, C.byref(out_n), first))
+            total = int(out_n.value)
+            if total <= cap:
+                return [x[:total] for x in arrays]
+            cap, first = total, False
+
+    def _count_then_emit(self, expect, dtypes, call):
+        """The protocol of the host forms whose answer has no bound worth allocating: call(cap, arrays, out_n) with room for
+        `expect` entries when the caller knows their number, else with none, which counts; a second call then emits.  Returns the
+        arrays cut to the entries."""
+        cap = int(expect) if expect else 0
+        while True:
+            arrays = [np.zeros(max(cap, 1), dtype=t) for t in dtypes]
+            out_n = C.c_uint64(0)
+            self._check(call(cap, arrays, C.byref(out_n)))
+            total = int(out_n.value)
+            if cap and total <= cap:
+                return [x[:total] for x in arrays]
+            cap = max(total, 1)
+
     def close_pairs(self, symbols, threshold, capacity=None, want_matrix=False):
         """symbols: (n, s) uint8 array of sequence bytes.  Returns (row_off uint64 [n + 1], col uint32, dist int32): per row of the
         distance matrix its entries <= threshold, columns ascending.  The matrix itself stays on the device — unless want_matrix,
@@ -1087,25 +1115,8 @@ class Device(object):
         The first call has room for every entry up to 2^26 of them (untouched pages of the two arrays cost nothing), so below
         8 192 samples there is never a second; beyond, an answer of more than max(64 n, 2^26) entries costs a second call, which
         uploads, packs and computes the matrix again."""
-        sym = np.ascontiguousarray(symbols, dtype=np.uint8)
-        n, s = sym.shape
-        row_off = np.zeros(n + 1, dtype=np.uint64)
-        mat = np.zeros((n, n), dtype=np.int32) if want_matrix else None
-        if n == 0:
-            empty = (row_off, np.zeros(0, np.uint32), np.zeros(0, np.int32))
-            return empty + (mat,) if want_matrix else empty
-        cap = int(capacity) if capacity else min(n * n, max(64 * n, 1 << 26))
-        have_matrix = False
-        while True:
-            col, dist = np.zeros(cap, dtype=np.uint32), np.zeros(cap, dtype=np.int32)
-            out_n = C.c_uint64(0)
-            self._check(self.lib.snpgpu_close_pairs(self.ctx, _ptr(sym) if sym.size else None, n, s, int(threshold), cap, _ptr(row_off), _ptr(col), _ptr(dist),
-                                                    C.byref(out_n), _ptr(mat) if want_matrix and not have_matrix else None))
-            have_matrix = True
-            if out_n.value <= cap:
-                csr = (row_off, col[:out_n.value], dist[:out_n.value])
-                return csr + (mat,) if want_matrix else csr
-            cap = int(out_n.value)
+        _, csr, mat = self.distance_outputs(symbols, want_matrix=want_matrix, pairs_within=threshold, capacity=capacity)
+        return csr + (mat,) if want_matrix else csr
 
     def clusters_dev(self, n, d_row_off, d_col, d_dist, n_edges, thresholds, d_out_numbers):
         """Single-linkage cluster numbers of a device CSR at every threshold into d_out_numbers[len(thresholds)][n] (uint32);
@@ -1147,28 +1158,8 @@ class Device(object):
         spanning tree of the distance matrix in ascending (d, u, v), u < v.  The matrix itself stays on the device — unless
         want_matrix, which adds the (n, n) int32 matrix of ``distance`` from the same computation.  pairs_within = T adds, from that
         computation too, the CSR of ``close_pairs(symbols, T)``: the result is then (u, v, dist, (row_off, col, dist)[, matrix])."""
-        sym = np.ascontiguousarray(symbols, dtype=np.uint8)
-        n, s = sym.shape
-        m = max(n - 1, 0)
-        u, v, dist = np.zeros(m, dtype=np.uint32), np.zeros(m, dtype=np.uint32), np.zeros(m, dtype=np.int32)
-        mat = np.zeros((n, n), dtype=np.int32) if want_matrix else None
-        opt = lambda a: _ptr(a) if a is not None and a.size else None     # noqa: E731
-        if pairs_within is None:
-            self._check(self.lib.snpgpu_mst(self.ctx, opt(sym), n, s, opt(u), opt(v), opt(dist), opt(mat)))
-            return (u, v, dist, mat) if want_matrix else (u, v, dist)
-        row_off = np.zeros(n + 1, dtype=np.uint64)
-        cap = max(min(n * n, max(64 * n, 1 << 26)), 1)
-        have_matrix = False
-        while True:                                           # (the capacity protocol of close_pairs: a second call only past max(64 n, 2^26) entries)
-            col, pd = np.zeros(cap, dtype=np.uint32), np.zeros(cap, dtype=np.int32)
-            out_n = C.c_uint64(0)
-            self._check(self.lib.snpgpu_mst_close_pairs(self.ctx, opt(sym), n, s, opt(u), opt(v), opt(dist), opt(mat) if not have_matrix else None, 1,
-                                                        int(pairs_within), cap, _ptr(row_off), _ptr(col), _ptr(pd), C.byref(out_n)))
-            have_matrix = True
-            if out_n.value <= cap:
-                csr = (row_off, col[:out_n.value], pd[:out_n.value])
-                return (u, v, dist, csr, mat) if want_matrix else (u, v, dist, csr)
-            cap = int(out_n.value)
+        tree, csr, mat = self.distance_outputs(symbols, want_tree=True, want_matrix=want_matrix, pairs_within=pairs_within)
+        return tree + (() if csr is None else (csr,)) + ((mat,) if want_matrix else ())
 
     # ---- complete- and average-linkage trees (additive to distance.py:93-106) -------------------
     @staticmethod
@@ -1298,15 +1289,9 @@ class Device(object):
         m = len(a)
         pair_off = np.zeros(m + 1, dtype=np.uint64)
         opt = lambda x: _ptr(x) if x.size else None           # noqa: E731
-        cap = int(expect) if expect else 0                    # no room known: count, then emit
-        while True:
-            site, bases = np.zeros(max(cap, 1), dtype=np.uint32), np.zeros(max(cap, 1), dtype=np.uint8)
-            out_n = C.c_uint64(0)
-            self._check(call(opt(a), opt(b), m, cap, _ptr(pair_off), _ptr(site), _ptr(bases), C.byref(out_n)))
-            total = int(out_n.value)
-            if cap and total <= cap:
-                return pair_off, site[:total], bases[:total]
-            cap = max(total, 1)
+        site, bases = self._count_then_emit(expect, (np.uint32, np.uint8), lambda cap, out, out_n: call(
+            opt(a), opt(b), m, cap, _ptr(pair_off), _ptr(out[0]), _ptr(out[1]), out_n))
+        return pair_off, site, bases
 
     def pair_sites(self, symbols, a, b, expect=None):
         """symbols: (n, s) uint8 array of sequence bytes; a, b: row indices of the pairs.  Returns (pair_off uint64 [m + 1], site
@@ -1323,10 +1308,11 @@ class Device(object):
     def packed_drop(self):
         self._check(self.lib.snpgpu_packed_drop(self.ctx))
 
-    def distance_outputs(self, symbols, want_tree=False, want_matrix=False, pairs_within=None, keep_packed=False):
+    def distance_outputs(self, symbols, want_tree=False, want_matrix=False, pairs_within=None, keep_packed=False, capacity=None):
         """One upload, pack and computation of the matrix for everything the distance step hands out.  Returns (tree, csr, matrix):
         the (u, v, dist) of ``mst``, the (row_off, col, dist) of ``close_pairs(symbols, pairs_within)``, the matrix of ``distance``
-        — each None when not asked for.  keep_packed leaves the packed matrix in the context for ``pair_sites_kept``."""
+        — each None when not asked for.  keep_packed leaves the packed matrix in the context for ``pair_sites_kept``.  capacity:
+        the entries of the close pairs the first call has room for (None: up to max(64 n, 2^26))."""
         sym = np.ascontiguousarray(symbols, dtype=np.uint8)
         n, s = sym.shape
         m = max(n - 1, 0) if want_tree else 0
@@ -1335,20 +1321,11 @@ class Device(object):
         opt = lambda x: _ptr(x) if x is not None and x.size else None     # noqa: E731
         row_off = np.zeros(n + 1, dtype=np.uint64)
         want_pairs = pairs_within is not None
-        cap = max(min(n * n, max(64 * n, 1 << 26)), 1) if want_pairs else 0
-        have_matrix = False
-        while True:                                           # (the capacity protocol of close_pairs)
-            col, pd = np.zeros(max(cap, 1), dtype=np.uint32), np.zeros(max(cap, 1), dtype=np.int32)
-            out_n = C.c_uint64(0)
-            self._check(self.lib.snpgpu_distance_outputs(self.ctx, opt(sym), n, s, int(bool(want_tree)), opt(u), opt(v), opt(dist),
-                                                         opt(mat) if not have_matrix else None, int(want_pairs), int(pairs_within or 0), cap, _ptr(row_off),
-                                                         _ptr(col), _ptr(pd), C.byref(out_n), int(bool(keep_packed))))
-            have_matrix = True
-            if out_n.value <= cap:
-                break
-            cap = int(out_n.value)
-        csr = (row_off, col[:out_n.value], pd[:out_n.value]) if want_pairs else None
-        return ((u, v, dist) if want_tree else None), csr, mat
+        cap = (int(capacity) if capacity else max(min(n * n, max(64 * n, 1 << 26)), 1)) if want_pairs else 0
+        col, pd = self._grow_to_fit(cap, (np.uint32, np.int32), lambda cap, out, out_n, first: self.lib.snpgpu_distance_outputs(
+            self.ctx, opt(sym), n, s, int(bool(want_tree)), opt(u), opt(v), opt(dist), opt(mat) if first else None, int(want_pairs), int(pairs_within or 0), cap,
+            _ptr(row_off), _ptr(out[0]), _ptr(out[1]), out_n, int(bool(keep_packed))))
+        return ((u, v, dist) if want_tree else None), ((row_off, col, pd) if want_pairs else None), mat
 
     # ---- query-against-database nearest neighbours (additive to distance.py:93-106) -------------
     ROUTES = {"auto": 0, "narrow": 1, "tile": 2, 0: 0, 1: 1, 2: 2}
@@ -1399,17 +1376,11 @@ class Device(object):
         mat = np.zeros((q, n), dtype=np.int32) if want_matrix else None
         opt = lambda x: _ptr(x) if x is not None and x.size else None     # noqa: E731
         cap = max(q * min(k, n) if k else min(q * n, max(64 * q, 1 << 26)), 1)
-        have_matrix = False
-        while True:                                           # (a second call only without k, past max(64 q, 2^26) entries)
-            col, dist = np.zeros(cap, dtype=np.uint32), np.zeros(cap, dtype=np.int32)
-            out_n = C.c_uint64(0)
-            self._check(self.lib.snpgpu_nearest(self.ctx, opt(qs), q, opt(db), n, s, k, thr, int(band_rows), self._route(route), cap, _ptr(row_off), _ptr(col),
-                                                _ptr(dist), C.byref(out_n), opt(mat) if not have_matrix else None))
-            have_matrix = True
-            if out_n.value <= cap:
-                csr = (row_off, col[:out_n.value], dist[:out_n.value])
-                return csr + (mat,) if want_matrix else csr
-            cap = int(out_n.value)
+        col, dist = self._grow_to_fit(cap, (np.uint32, np.int32), lambda cap, out, out_n, first: self.lib.snpgpu_nearest(   # (a second call only without k)
+            self.ctx, opt(qs), q, opt(db), n, s, k, thr, int(band_rows), self._route(route), cap, _ptr(row_off), _ptr(out[0]), _ptr(out[1]), out_n,
+            opt(mat) if first else None))
+        csr = (row_off, col, dist)
+        return csr + (mat,) if want_matrix else csr
 
     # ---- compared-site counts (additive to distance.py:93-106) ------------------------------------
     def valid_plane_row_bytes(self, n_sites):
@@ -1516,19 +1487,13 @@ class Device(object):
             raise ValueError("a label lies outside 1 ... the number of clusters of its labelling")
         off = np.zeros(int(ncl.sum(dtype=np.int64)) + t, dtype=np.uint64)
         opt = lambda x: _ptr(x) if x.size else None           # noqa: E731
-        cap = int(expect) if expect else 0
-        while True:
-            site, base, members = np.zeros(max(cap, 1), dtype=np.uint32), np.zeros(max(cap, 1), dtype=np.uint8), np.zeros(max(cap, 1), dtype=np.uint32)
-            out_n = C.c_uint64(0)
-            self._check(self.lib.snpgpu_cluster_snps(self.ctx, opt(sym), n, s, opt(lab), opt(ncl), t, cap, opt(off), _ptr(site), _ptr(base), _ptr(members), C.byref(out_n)))
-            total = int(out_n.value)
-            if (cap and total <= cap) or t == 0:
-                break
-            cap = max(total, 1)
+        site, base, members = np.zeros(0, dtype=np.uint32), np.zeros(0, dtype=np.uint8), np.zeros(0, dtype=np.uint32)
+        if t:
+            site, base, members = self._count_then_emit(expect, (np.uint32, np.uint8, np.uint32), lambda cap, out, out_n: self.lib.snpgpu_cluster_snps(
+                self.ctx, opt(sym), n, s, opt(lab), opt(ncl), t, cap, opt(off), _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), out_n))
         ends = np.cumsum(ncl.astype(np.int64) + 1)
-        return [off[e - int(c) - 1:e] for e, c in zip(ends, ncl)], site[:total], base[:total], members[:total]
+        return [off[e - int(c) - 1:e] for e, c in zip(ends, ncl)], site, base, members
 
-    # ---- filter_regions ------------------------------------------------------------------------
     def dense_windows(self, positions, seg_off, max_snps, windows):
         pos = np.ascontiguousarray(positions, dtype=np.int64)
         seg = np.ascontiguousarray(seg_off, dtype=np.uint32)

@@ -236,15 +236,6 @@ def write_dendrogram(path, ids, u, v, dist):
     _write_tree("snpgpu_write_dendrogram_newick", path, ids, u, v, dist)
 
 
-def linkage_of_symbols(dev, file_ids, sym, lens, kind):
-    """As mst_of_matrix, but what comes back is the complete- or average-linkage tree of the samples: (ids, a, b, size_a, size_b,
-    num), the n - 1 merges in ascending key order (Device.linkage); built on the device, where the matrix stays."""
-    ids, rows = _sorted_rows(file_ids, sym, lens)
-    if rows is None:
-        rows = np.zeros((0, 0), dtype=np.uint8)
-    return (ids,) + tuple(dev.linkage(rows, kind))
-
-
 def _merge_arrays(a, b, size_a, size_b, num):
     arrays = [np.ascontiguousarray(x, dtype=np.uint32) for x in (a, b, size_a, size_b)] + [np.ascontiguousarray(num, dtype=np.uint64)]
     if len(set(len(x) for x in arrays)) != 1:
@@ -304,15 +295,6 @@ def write_linkage_outputs(ids, kind, merges, merges_file, dendrogram_file, clust
         thresholds = cluster_thresholds(thresholds)
         numbers, _ = linkage_cut(kind, len(ids), *(tuple(merges) + (thresholds,)))
         write_clusters(clusters_file, ids, thresholds, numbers)
-
-
-def nj_of_symbols(dev, file_ids, sym, lens):
-    """As linkage_of_symbols, but what comes back is the neighbour-joining tree of the samples: (ids, tree), tree the six values
-    of Device.nj; built on the device, where the matrix stays."""
-    ids, rows = _sorted_rows(file_ids, sym, lens)
-    if rows is None:
-        rows = np.zeros((0, 0), dtype=np.uint8)
-    return ids, tuple(dev.nj(rows))
 
 
 def write_nj(path, ids, a, b, len_a, len_b, star, star_len):
@@ -516,18 +498,6 @@ def query_rows(q_file_ids, q_sym, q_lens, columns):
     return ids, np.ascontiguousarray(q_sym[rows])
 
 
-def nearest_of_matrices(dev, db_file_ids, db_sym, db_lens, q_file_ids, q_sym, q_lens, k, threshold, band_rows=0, route=0):
-    """The database samples closest to each query: (q_ids, db_ids, row_off, col, dist) — both id lists sorted (the database as
-    for every other output of the step, the queries by query_rows), per query the database samples within `threshold` SNPs (None:
-    any distance) in ascending (distance, database index), the first k of them (0: all).  The q x n distances are computed on
-    the device query band by query band and selected there; the (n + q)^2 matrix is never computed and only the lists come back."""
-    db_ids, db_rows = _sorted_rows(db_file_ids, db_sym, db_lens)
-    q_ids, q_rows = query_rows(q_file_ids, q_sym, q_lens, None if db_rows is None else db_rows.shape[1])
-    if db_rows is None:
-        db_rows = np.zeros((0, q_rows.shape[1]), dtype=np.uint8)
-    return (q_ids, db_ids) + tuple(dev.nearest(q_rows, db_rows, k=k, threshold=threshold, band_rows=band_rows, route=route))
-
-
 def write_nearest(path, q_ids, db_ids, row_off, col, dist, compared=None):
     """Header and "query id\tdatabase id\tdistance" rows of a CSR over the queries whose columns are database samples, query by
     query, through the library's host formatter (csrc/tsv_out.hip); compared (one count per entry): a fourth column."""
@@ -557,12 +527,9 @@ def _write_tsv(path, layout, ids, mat):
     """distance.py:100-114 through the library's host formatter (csrc/tsv_out.hip): at 10 000 samples the pairwise file has
     10^8 lines, ~35 s of Python string formatting for 38 ms of kernel."""
     from . import _lib as L
-    names = [i.encode("utf-8") for i in ids]
-    off = np.zeros(len(names) + 1, dtype=np.uint64)
-    np.cumsum([len(b) for b in names], out=off[1:])
-    blob = b"".join(names)
+    blob, off = _id_table(ids)
     m = np.ascontiguousarray(mat, dtype=np.int32)
-    rc = L.load().snpgpu_write_distance_tsv(path.encode(), layout, blob, off.ctypes.data, len(names), m.ctypes.data, m.shape[1] if m.ndim == 2 else 0)
+    rc = L.load().snpgpu_write_distance_tsv(path.encode(), layout, blob, off.ctypes.data, len(ids), m.ctypes.data, m.shape[1] if m.ndim == 2 else 0)
     if rc == L.E_IO:
         raise IOError("cannot write %s" % path)
     if rc != 0:
@@ -611,168 +578,210 @@ def calculate_snp_distances(args):
     utils.print_log_header()
     utils.print_arguments(args)
 
-    input_file = args.inputFile
-    pairwise_file = args.pairwiseFile
-    matrix_file = args.matrixFile
+    o = DistanceOptions()
+    o.input_file = args.inputFile
+    o.pairwise_file = args.pairwiseFile
+    o.matrix_file = args.matrixFile
     # extensions of this build (absent when the Namespace comes from the reference's own parser)
-    close_file = getattr(args, "amdClosePairsFile", None)
-    max_pair_distance = getattr(args, "amdMaxPairDistance", None)
-    clusters_file = getattr(args, "amdClustersFile", None)
-    thresholds = list(getattr(args, "amdClusterThresholds", None) or [])
-    mst_file = getattr(args, "amdMstFile", None)
-    dendrogram_file = getattr(args, "amdDendrogramFile", None)
-    close_sites_file = getattr(args, "amdClosePairSitesFile", None)
-    mst_sites_file = getattr(args, "amdMstSitesFile", None)
-    user_pairs_file = getattr(args, "amdPairSitesPairsFile", None)
-    user_sites_file = getattr(args, "amdPairSitesOutFile", None)
-    snp_list_file = getattr(args, "amdSnpListFile", None)
-    linkage_kind = getattr(args, "amdLinkage", None)
-    linkage_files = (getattr(args, "amdLinkageMergesFile", None), getattr(args, "amdLinkageDendrogramFile", None), getattr(args, "amdLinkageClustersFile", None))
-    query_file = getattr(args, "amdQueryFile", None)
-    nearest_file = getattr(args, "amdNearestFile", None)
-    nearest_count = getattr(args, "amdNearestCount", None)
-    compared_matrix_file = getattr(args, "amdComparedMatrixFile", None)
-    with_compared = bool(getattr(args, "amdCompared", False))
-    site_counts_file = getattr(args, "amdSiteCountsFile", None)
-    cluster_snps_file = getattr(args, "amdClusterSnpsFile", None)
-    nj_file = getattr(args, "amdNjFile", None)
-    if utils.verify_existing_input_files("SNP matrix file", [input_file]) > 0:
+    o.close_file = getattr(args, "amdClosePairsFile", None)
+    o.max_pair_distance = getattr(args, "amdMaxPairDistance", None)
+    o.clusters_file = getattr(args, "amdClustersFile", None)
+    o.thresholds = list(getattr(args, "amdClusterThresholds", None) or [])
+    o.mst_file = getattr(args, "amdMstFile", None)
+    o.dendrogram_file = getattr(args, "amdDendrogramFile", None)
+    o.close_sites_file = getattr(args, "amdClosePairSitesFile", None)
+    o.mst_sites_file = getattr(args, "amdMstSitesFile", None)
+    o.user_pairs_file = getattr(args, "amdPairSitesPairsFile", None)
+    o.user_sites_file = getattr(args, "amdPairSitesOutFile", None)
+    o.snp_list_file = getattr(args, "amdSnpListFile", None)
+    o.linkage_kind = getattr(args, "amdLinkage", None)
+    o.linkage_files = (getattr(args, "amdLinkageMergesFile", None), getattr(args, "amdLinkageDendrogramFile", None), getattr(args, "amdLinkageClustersFile", None))
+    o.query_file = getattr(args, "amdQueryFile", None)
+    o.nearest_file = getattr(args, "amdNearestFile", None)
+    o.nearest_count = getattr(args, "amdNearestCount", None)
+    o.compared_matrix_file = getattr(args, "amdComparedMatrixFile", None)
+    o.with_compared = bool(getattr(args, "amdCompared", False))
+    o.site_counts_file = getattr(args, "amdSiteCountsFile", None)
+    o.cluster_snps_file = getattr(args, "amdClusterSnpsFile", None)
+    o.nj_file = getattr(args, "amdNjFile", None)
+    if utils.verify_existing_input_files("SNP matrix file", [o.input_file]) > 0:
         utils.global_error("Error: cannot calculate sequence distances without the snp matrix file.")
-    if close_file and max_pair_distance is None:
+    if o.close_file and o.max_pair_distance is None:
         utils.global_error("Error: --amdClosePairs needs --amdMaxPairDistance.")
-    if close_sites_file and max_pair_distance is None:
+    if o.close_sites_file and o.max_pair_distance is None:
         utils.global_error("Error: --amdClosePairSites needs --amdMaxPairDistance.")
-    if bool(user_pairs_file) != bool(user_sites_file):
+    if bool(o.user_pairs_file) != bool(o.user_sites_file):
         utils.global_error("Error: --amdPairSitesPairs and --amdPairSitesOut go together.")
-    if user_pairs_file and utils.verify_existing_input_files("pair list file", [user_pairs_file]) > 0:
+    if o.user_pairs_file and utils.verify_existing_input_files("pair list file", [o.user_pairs_file]) > 0:
         utils.global_error("Error: cannot list the differing sites without the pair list file.")
-    if cluster_snps_file and not thresholds:
+    if o.cluster_snps_file and not o.thresholds:
         utils.global_error("Error: --amdClusterSnps needs at least one threshold in --amdClusterThresholds.")
-    if snp_list_file and (site_counts_file or cluster_snps_file) and not os.path.isfile(snp_list_file):
-        utils.global_error("Error: --amdSnpList: cannot name the sites of --amdSiteCounts and --amdClusterSnps without the snplist file %s." % snp_list_file)
-    if snp_list_file and utils.verify_existing_input_files("snplist file", [snp_list_file]) > 0:
+    if o.snp_list_file and (o.site_counts_file or o.cluster_snps_file) and not os.path.isfile(o.snp_list_file):
+        utils.global_error("Error: --amdSnpList: cannot name the sites of --amdSiteCounts and --amdClusterSnps without the snplist file %s." % o.snp_list_file)
+    if o.snp_list_file and utils.verify_existing_input_files("snplist file", [o.snp_list_file]) > 0:
         utils.global_error("Error: cannot name the differing sites without the snplist file.")
-    if clusters_file and not thresholds:
+    if o.clusters_file and not o.thresholds:
         utils.global_error("Error: --amdClusters needs at least one threshold in --amdClusterThresholds.")
-    if any(linkage_files) and not linkage_kind:
+    if any(o.linkage_files) and not o.linkage_kind:
         utils.global_error("Error: --amdLinkageMerges, --amdLinkageDendrogram and --amdLinkageClusters need --amdLinkage.")
-    if linkage_kind and not any(linkage_files):
+    if o.linkage_kind and not any(o.linkage_files):
         utils.global_error("Error: --amdLinkage needs at least one of --amdLinkageMerges, --amdLinkageDendrogram and --amdLinkageClusters.")
-    if linkage_files[2] and not thresholds:
+    if o.linkage_files[2] and not o.thresholds:
         utils.global_error("Error: --amdLinkageClusters needs at least one threshold in --amdClusterThresholds.")
-    if (max_pair_distance is not None and max_pair_distance < 0) or any(t < 0 for t in thresholds):
+    if (o.max_pair_distance is not None and o.max_pair_distance < 0) or any(t < 0 for t in o.thresholds):
         utils.global_error("Error: a distance threshold cannot be negative.")
-    if bool(query_file) != bool(nearest_file):
+    if bool(o.query_file) != bool(o.nearest_file):
         utils.global_error("Error: --amdQuery and --amdNearest go together.")
-    if nearest_count is not None and not nearest_file:
+    if o.nearest_count is not None and not o.nearest_file:
         utils.global_error("Error: --amdNearestCount needs --amdQuery and --amdNearest.")
-    if nearest_count is not None and nearest_count < 0:
+    if o.nearest_count is not None and o.nearest_count < 0:
         utils.global_error("Error: --amdNearestCount cannot be negative.")
-    if query_file and utils.verify_existing_input_files("query file", [query_file]) > 0:
+    if o.query_file and utils.verify_existing_input_files("query file", [o.query_file]) > 0:
         utils.global_error("Error: cannot find the nearest samples without the query file.")
-    if with_compared and not (close_file or mst_file or nearest_file):
+    if o.with_compared and not (o.close_file or o.mst_file or o.nearest_file):
         utils.global_error("Error: --amdCompared needs at least one of --amdClosePairs, --amdMst and --amdNearest.")
-    outputs = [f for f in (pairwise_file, matrix_file, close_file, clusters_file, mst_file, dendrogram_file, close_sites_file, mst_sites_file, user_sites_file, nearest_file,
-                           compared_matrix_file, site_counts_file, cluster_snps_file, nj_file) + linkage_files if f]
+    outputs = [f for f in (o.pairwise_file, o.matrix_file, o.close_file, o.clusters_file, o.mst_file, o.dendrogram_file, o.close_sites_file, o.mst_sites_file, o.user_sites_file, o.nearest_file,
+                           o.compared_matrix_file, o.site_counts_file, o.cluster_snps_file, o.nj_file) + o.linkage_files if f]
     if not outputs:
         utils.global_error("Error: no output file specified.")
 
-    sources = [input_file] + [f for f in (user_pairs_file, snp_list_file) if f and (close_sites_file or mst_sites_file or user_sites_file)] + \
-        ([snp_list_file] if snp_list_file and (site_counts_file or cluster_snps_file) and not (close_sites_file or mst_sites_file or user_sites_file) else []) + ([query_file] if query_file else [])
+    sources = [o.input_file] + [f for f in (o.user_pairs_file, o.snp_list_file) if f and (o.close_sites_file or o.mst_sites_file or o.user_sites_file)] + \
+        ([o.snp_list_file] if o.snp_list_file and (o.site_counts_file or o.cluster_snps_file) and not (o.close_sites_file or o.mst_sites_file or o.user_sites_file) else []) + ([o.query_file] if o.query_file else [])
     if not (args.forceFlag or any(utils.target_needs_rebuild(sources, f) for f in outputs)):
         utils.verbose_print("Distance files have already been freshly built.  Use the -f option to force a rebuild.")
         return
 
-    file_ids, sym, lens = snp_matrix.load_matrix(input_file)
+    file_ids, sym, lens = snp_matrix.load_matrix(o.input_file)
     utils.verbose_print("# %s %s" % (utils.timestamp(), "Calculating all pairwise distances"))
     from .device import default_device
     named_sites = None
-    if snp_list_file and (site_counts_file or cluster_snps_file):
-        named_sites = utils.read_snp_position_list(snp_list_file)
+    if o.snp_list_file and (o.site_counts_file or o.cluster_snps_file):
+        named_sites = utils.read_snp_position_list(o.snp_list_file)
         columns = _sorted_rows(file_ids, sym, lens)[1]
         columns = 0 if columns is None else columns.shape[1]
         if len(named_sites) != columns:
-            utils.global_error("Error: %s lists %d sites, the snp matrix has %d columns." % (snp_list_file, len(named_sites), columns))
+            utils.global_error("Error: %s lists %d sites, the snp matrix has %d columns." % (o.snp_list_file, len(named_sites), columns))
     on_their_own = 0
-    if site_counts_file:
+    if o.site_counts_file:
         # on its own, as the two below: one more upload and pack beside the other outputs; no matrix is computed for it
         ids, rows = _sorted_rows(file_ids, sym, lens)
         counts = default_device().site_counts(rows) if rows is not None and rows.size else np.zeros((0 if rows is None else rows.shape[1], 4), dtype=np.int32)
-        write_site_counts(site_counts_file, counts, len(ids), snp_list=named_sites)
+        write_site_counts(o.site_counts_file, counts, len(ids), snp_list=named_sites)
         on_their_own += 1
-    if nearest_file:
+    if o.nearest_file:
         # the queries against the database, on their own: this first form uploads and packs the database itself, whatever else is
         # asked for, and the other outputs are computed as without it
-        _write_nearest_output(default_device, file_ids, sym, lens, query_file, nearest_file, nearest_count or 0, max_pair_distance, with_compared)
+        _write_nearest_output(default_device, file_ids, sym, lens, o.query_file, o.nearest_file, o.nearest_count or 0, o.max_pair_distance, o.with_compared)
         on_their_own += 1
-    if compared_matrix_file:
+    if o.compared_matrix_file:
         # likewise on its own: one more upload and pack beside the other outputs, and the matrix in the layout of -m
-        write_matrix(compared_matrix_file, *compared_of_matrix(default_device, file_ids, sym, lens))
+        write_matrix(o.compared_matrix_file, *compared_of_matrix(default_device, file_ids, sym, lens))
         on_their_own += 1
     if len(outputs) == on_their_own:
         return
-    if close_sites_file or mst_sites_file or user_sites_file:
-        _distances_with_sites(default_device, file_ids, sym, lens, snp_list_file, pairwise_file, matrix_file, close_file, max_pair_distance, clusters_file, thresholds,
-                              mst_file, dendrogram_file, close_sites_file, mst_sites_file, user_pairs_file, user_sites_file, linkage_kind, linkage_files, with_compared,
-                              cluster_snps_file, named_sites, nj_file)
-        return
-    dev = default_device()
-    mat = None
-    tree = None
-    want_clusters = bool(clusters_file or cluster_snps_file)   # the cluster SNPs take the numbers of the clusters file, from the same pairs
-    if mst_file or dendrogram_file:
-        # the tree is built where the matrix is computed: n - 1 edges come to the host — with them, from that one computation, the
-        # pairs within the widest threshold and the matrix itself when those outputs are asked for too
-        widest = max(([max_pair_distance] if close_file else []) + (thresholds if want_clusters else [])) if (close_file or want_clusters) else None
-        got = mst_of_matrix(dev, file_ids, sym, lens, want_matrix=bool(pairwise_file or matrix_file), pairs_within=widest)
-        ids, tree = got[0], got[1:4]
-        got = got[4:]
-        if widest is not None:
-            (row_off, col, dist), got = got[0], got[1:]
-        mat = got[0] if got else None
-    elif close_file or want_clusters:
-        # the matrix is thresholded where it is computed: only the pairs within the largest threshold come to the host — and the
-        # matrix of that same computation when the two tables are asked for too
-        widest = max(([max_pair_distance] if close_file else []) + (thresholds if want_clusters else []))
-        got = close_pairs_of_matrix(dev, file_ids, sym, lens, widest, want_matrix=bool(pairwise_file or matrix_file))
-        ids, row_off, col, dist = got[:4]
-        mat = got[4] if len(got) > 4 else None
-    elif pairwise_file or matrix_file:
-        ids, mat = distance_of_matrix(dev, file_ids, sym, lens)
-    if linkage_kind:
-        # from the matrix of that computation when a table brought it to the host; else built where the matrix is computed, and
-        # only the n - 1 merges come to the host (beside a tree or a threshold that is one more computation of the matrix)
-        if mat is not None:
-            merges = dev.linkage_of_matrix(mat, linkage_kind)
-        else:
-            got = linkage_of_symbols(dev, file_ids, sym, lens, linkage_kind)
-            ids, merges = got[0], got[1:]
-        write_linkage_outputs(ids, linkage_kind, merges, linkage_files[0], linkage_files[1], linkage_files[2], thresholds)
-    if nj_file:
-        # as the linkage tree: from the matrix a table brought to the host, else built where the matrix is computed — alone, the
-        # n x n matrix never comes to the host; beside a tree, a threshold or a linkage that is one more computation of the matrix
-        if mat is not None:
-            nj_tree = dev.nj_of_matrix(mat)
-        else:
-            ids, nj_tree = nj_of_symbols(dev, file_ids, sym, lens)
-        write_nj(nj_file, ids, *nj_tree)
-    if pairwise_file:
-        write_pairwise(pairwise_file, ids, mat)
-    if matrix_file:
-        write_matrix(matrix_file, ids, mat)
-    pairs_compared = tree_compared = None
-    if with_compared:
-        pairs_compared, tree_compared = compared_columns(dev, _sorted_rows(file_ids, sym, lens)[1], filter_pairs(row_off, col, dist, max_pair_distance) if close_file else None,
-                                                         tree if mst_file else None)
-    if close_file or want_clusters:
-        numbers = write_pairs_and_clusters(dev, ids, row_off, col, dist, close_file, max_pair_distance, clusters_file, thresholds, pairs_compared,
-                                           want_numbers=bool(cluster_snps_file))
-    if mst_file:
-        write_mst(mst_file, ids, *tree, compared=tree_compared)
-    if dendrogram_file:
-        write_dendrogram(dendrogram_file, ids, *tree)
-    if cluster_snps_file:
-        write_cluster_snps_of_numbers(lambda: dev, cluster_snps_file, _sorted_rows(file_ids, sym, lens)[1], cluster_thresholds(thresholds), numbers, snp_list=named_sites)
+    _write_distance_outputs(default_device, o, file_ids, sym, lens, named_sites)
+
+
+class DistanceOptions(object):
+    """What calculate_snp_distances was asked for: the output paths and the values that go with them, as attributes."""
+
+
+class DistancePlan(object):
+    """How the outputs of one run share their device work (distance_plan)."""
+
+
+def distance_plan(o, n, columns):
+    """The plan of the outputs that share one matrix, from the options and the shape of the sorted rows alone — no device:
+        want_tree, want_matrix  the spanning tree / the n x n matrix on the host are needed
+        widest                  the largest threshold a CSR of pairs has to hold (close pairs, their sites, clusters, cluster
+                                SNPs), or None
+        compute                 the one ``Device.distance_outputs`` call is made
+        keep_packed             ... and leaves the packed matrix on the device for the site files
+        host_matrix             linkage and neighbour joining take the matrix the host has (``*_of_matrix``); else each computes
+                                its own where the matrix is built, and only its merges come to the host
+    The symbols are uploaded and packed once and the matrix is computed once, and only when a tree, a threshold or a table needs
+    it; the n x n matrix comes to the host for -p / -m alone."""
+    p = DistancePlan()
+    sites = bool(o.close_sites_file or o.mst_sites_file or o.user_sites_file)
+    p.want_tree = bool(o.mst_file or o.dendrogram_file or o.mst_sites_file)
+    p.want_matrix = bool(o.pairwise_file or o.matrix_file)
+    within = ([o.max_pair_distance] if (o.close_file or o.close_sites_file) else []) + (o.thresholds if (o.clusters_file or o.cluster_snps_file) else [])
+    p.widest = max(within) if within else None
+    # Degenerate shapes keep the calls they have always made (the table of tests/test_distance_plan_cpu.py): beside a site file
+    # no record means no call; without one a tree is asked for even of no record, and tables alone of no column are zeros
+    if sites:
+        p.compute = n > 0 and (p.want_tree or p.want_matrix or p.widest is not None)
+    else:
+        p.compute = p.want_tree or (n > 0 and (p.widest is not None or (p.want_matrix and columns > 0)))
+    p.keep_packed = sites and p.compute
+    p.host_matrix = p.want_matrix or (sites and n == 0)
+    return p
+
+
+def _write_distance_outputs(device_of, o, file_ids, sym, lens, named_sites):
+    """The outputs of calculate_snp_distances that share one matrix, by distance_plan.  The inputs are checked before a device
+    is asked for; the packed matrix stays on the device until every pair list has been answered from it."""
+    ids, rows = _sorted_rows(file_ids, sym, lens)
+    sorted_rows = rows                                         # (None without a record: nothing to upload)
+    if rows is None:
+        rows = np.zeros((0, 0), dtype=np.uint8)
+    n, columns = rows.shape
+    snp_list = None
+    if o.snp_list_file and (o.close_sites_file or o.mst_sites_file or o.user_sites_file):
+        snp_list = utils.read_snp_position_list(o.snp_list_file)
+        if len(snp_list) != columns:
+            utils.global_error("Error: %s lists %d sites, the snp matrix has %d columns." % (o.snp_list_file, len(snp_list), columns))
+    user_pairs = read_pair_list(o.user_pairs_file, ids) if o.user_sites_file else None
+    plan = distance_plan(o, n, columns)
+    dev = device_of()                                          # (the inputs have been checked: only now is a device needed)
+    if plan.compute:
+        tree, csr, mat = dev.distance_outputs(rows, want_tree=plan.want_tree, want_matrix=plan.want_matrix, pairs_within=plan.widest, keep_packed=plan.keep_packed)
+    else:                                                      # nothing asks for the matrix, or a shape that has no entry to compute
+        empty = np.zeros(0, dtype=np.uint32)
+        tree, csr = (empty, empty, np.zeros(0, dtype=np.int32)), (np.zeros(1, dtype=np.uint64), empty, np.zeros(0, dtype=np.int32))
+        mat = np.zeros((n, n), dtype=np.int32) if plan.host_matrix else None
+
+    def sites_of(a, b, expect):
+        if n == 0 or len(a) == 0:
+            return np.zeros(len(a) + 1, dtype=np.uint64), np.zeros(0, dtype=np.uint32), np.zeros(0, dtype=np.uint8)
+        return dev.pair_sites_kept(a, b, expect=expect) if plan.keep_packed else dev.pair_sites(rows, a, b, expect=expect)
+
+    try:
+        if o.linkage_kind:
+            merges = dev.linkage_of_matrix(mat, o.linkage_kind) if plan.host_matrix else dev.linkage(rows, o.linkage_kind)
+            write_linkage_outputs(ids, o.linkage_kind, merges, o.linkage_files[0], o.linkage_files[1], o.linkage_files[2], o.thresholds)
+        if o.nj_file:
+            write_nj(o.nj_file, ids, *(dev.nj_of_matrix(mat) if plan.host_matrix else dev.nj(rows)))
+        if o.pairwise_file:
+            write_pairwise(o.pairwise_file, ids, mat)
+        if o.matrix_file:
+            write_matrix(o.matrix_file, ids, mat)
+        pairs_compared = tree_compared = None
+        if o.with_compared:                                    # (not done: reuse of the kept packed matrix — one more upload and pack)
+            pairs_compared, tree_compared = compared_columns(dev, sorted_rows, filter_pairs(csr[0], csr[1], csr[2], o.max_pair_distance) if o.close_file else None,
+                                                             tree if o.mst_file else None)
+        if o.close_file or o.clusters_file or o.cluster_snps_file:
+            numbers = write_pairs_and_clusters(dev, ids, csr[0], csr[1], csr[2], o.close_file, o.max_pair_distance, o.clusters_file, o.thresholds, pairs_compared,
+                                               want_numbers=bool(o.cluster_snps_file))
+        if o.cluster_snps_file:                                # (not done: reuse of the kept packed matrix — one more upload and pack)
+            write_cluster_snps_of_numbers(lambda: dev, o.cluster_snps_file, sorted_rows, cluster_thresholds(o.thresholds), numbers, snp_list=named_sites)
+        if o.mst_file:
+            write_mst(o.mst_file, ids, *tree, compared=tree_compared)
+        if o.dendrogram_file:
+            write_dendrogram(o.dendrogram_file, ids, *tree)
+        if o.close_sites_file:
+            a, b, d = pairs_of_csr(csr[0], csr[1], csr[2], o.max_pair_distance)
+            write_pair_sites(o.close_sites_file, ids, a, b, *sites_of(a, b, int(d.sum(dtype=np.int64))), snp_list=snp_list)
+        if o.mst_sites_file:
+            u, v, d = tree
+            write_pair_sites(o.mst_sites_file, ids, u, v, *sites_of(u, v, int(np.asarray(d).sum(dtype=np.int64))), snp_list=snp_list)
+        if o.user_sites_file:
+            a, b = user_pairs
+            expect = int(mat[a.astype(np.int64), b.astype(np.int64)].sum(dtype=np.int64)) if (mat is not None and len(a)) else None
+            write_pair_sites(o.user_sites_file, ids, a, b, *sites_of(a, b, expect), snp_list=snp_list)
+    finally:
+        if plan.keep_packed:
+            dev.packed_drop()
 
 
 def _write_nearest_output(device_of, file_ids, sym, lens, query_file, nearest_file, count, max_pair_distance, with_compared=False):
@@ -789,76 +798,3 @@ def _write_nearest_output(device_of, file_ids, sym, lens, query_file, nearest_fi
     row_off, col, dist = dev.nearest(q_rows, db_rows, k=count, threshold=max_pair_distance)
     compared = dev.compared_pairs(q_rows, rows_of_csr(row_off), col, db_rows) if with_compared else None
     write_nearest(nearest_file, q_ids, db_ids, row_off, col, dist, compared=compared)
-
-
-def _distances_with_sites(device_of, file_ids, sym, lens, snp_list_file, pairwise_file, matrix_file, close_file, max_pair_distance, clusters_file, thresholds,
-                          mst_file, dendrogram_file, close_sites_file, mst_sites_file, user_pairs_file, user_sites_file, linkage_kind=None,
-                          linkage_files=(None, None, None), with_compared=False, cluster_snps_file=None, named_sites=None, nj_file=None):
-    """calculate_snp_distances when the differing sites of some pairs are asked for: the symbols are uploaded and packed once; the
-    matrix is computed once, and only when a tree, a threshold or a table needs it; the packed matrix stays on the device until
-    every pair list has been answered from it.  The n x n matrix comes to the host for -p / -m alone."""
-    ids, rows = _sorted_rows(file_ids, sym, lens)
-    if rows is None:
-        rows = np.zeros((0, 0), dtype=np.uint8)
-    n, columns = rows.shape
-    snp_list = None
-    if snp_list_file:
-        snp_list = utils.read_snp_position_list(snp_list_file)
-        if len(snp_list) != columns:
-            utils.global_error("Error: %s lists %d sites, the snp matrix has %d columns." % (snp_list_file, len(snp_list), columns))
-    user_pairs = read_pair_list(user_pairs_file, ids) if user_sites_file else None
-    dev = device_of()                                          # (the inputs have been checked: only now is a device needed)
-    want_tree = bool(mst_file or dendrogram_file or mst_sites_file)
-    want_matrix = bool(pairwise_file or matrix_file)
-    within = ([max_pair_distance] if (close_file or close_sites_file) else []) + (thresholds if (clusters_file or cluster_snps_file) else [])
-    widest = max(within) if within else None
-    tree = csr = mat = None
-    kept = False
-    if n and (want_tree or want_matrix or widest is not None):
-        tree, csr, mat = dev.distance_outputs(rows, want_tree=want_tree, want_matrix=want_matrix, pairs_within=widest, keep_packed=True)
-        kept = True
-    elif n == 0:
-        empty = np.zeros(0, dtype=np.uint32)
-        tree, csr, mat = (empty, empty, np.zeros(0, dtype=np.int32)), (np.zeros(1, dtype=np.uint64), empty, np.zeros(0, dtype=np.int32)), np.zeros((0, 0), dtype=np.int32)
-
-    def sites_of(a, b, expect):
-        if n == 0 or len(a) == 0:
-            return np.zeros(len(a) + 1, dtype=np.uint64), np.zeros(0, dtype=np.uint32), np.zeros(0, dtype=np.uint8)
-        return dev.pair_sites_kept(a, b, expect=expect) if kept else dev.pair_sites(rows, a, b, expect=expect)
-
-    try:
-        if linkage_kind:
-            merges = dev.linkage_of_matrix(mat, linkage_kind) if mat is not None else dev.linkage(rows, linkage_kind)
-            write_linkage_outputs(ids, linkage_kind, merges, linkage_files[0], linkage_files[1], linkage_files[2], thresholds)
-        if nj_file:
-            write_nj(nj_file, ids, *(dev.nj_of_matrix(mat) if mat is not None else dev.nj(rows)))
-        if pairwise_file:
-            write_pairwise(pairwise_file, ids, mat)
-        if matrix_file:
-            write_matrix(matrix_file, ids, mat)
-        pairs_compared = tree_compared = None
-        if with_compared:                                      # (not done: reuse of the kept packed matrix — one more upload and pack)
-            pairs_compared, tree_compared = compared_columns(dev, rows if n else None, filter_pairs(csr[0], csr[1], csr[2], max_pair_distance) if close_file else None,
-                                                             tree if mst_file else None)
-        if close_file or clusters_file or cluster_snps_file:
-            numbers = write_pairs_and_clusters(dev, ids, csr[0], csr[1], csr[2], close_file, max_pair_distance, clusters_file, thresholds, pairs_compared,
-                                               want_numbers=bool(cluster_snps_file))
-        if cluster_snps_file:                                  # (not done: reuse of the kept packed matrix — one more upload and pack)
-            write_cluster_snps_of_numbers(lambda: dev, cluster_snps_file, rows if n else None, cluster_thresholds(thresholds), numbers, snp_list=named_sites)
-        if mst_file:
-            write_mst(mst_file, ids, *tree, compared=tree_compared)
-        if dendrogram_file:
-            write_dendrogram(dendrogram_file, ids, *tree)
-        if close_sites_file:
-            a, b, d = pairs_of_csr(csr[0], csr[1], csr[2], max_pair_distance)
-            write_pair_sites(close_sites_file, ids, a, b, *sites_of(a, b, int(d.sum(dtype=np.int64))), snp_list=snp_list)
-        if mst_sites_file:
-            u, v, d = tree
-            write_pair_sites(mst_sites_file, ids, u, v, *sites_of(u, v, int(np.asarray(d).sum(dtype=np.int64))), snp_list=snp_list)
-        if user_sites_file:
-            a, b = user_pairs
-            expect = int(mat[a.astype(np.int64), b.astype(np.int64)].sum(dtype=np.int64)) if (mat is not None and len(a)) else None
-            write_pair_sites(user_sites_file, ids, a, b, *sites_of(a, b, expect), snp_list=snp_list)
-    finally:
-        if kept:
-            dev.packed_drop()
