@@ -289,7 +289,10 @@ VS_PARAMS = {m: sorted({tuple(sorted(kw.items())) for _, _, kw in tc.varscan_cas
 
 
 def _varscan_file(m, walk, seed):
-    """All VarScan cases for --min-avg-qual m: short lines (the LDS walk) or lines of 8.4-8.8 KiB, longer than the two tile slots a wave packs its lines into (the global-memory walk)."""
+    """All VarScan cases for --min-avg-qual m: short lines (the LDS walk, in the strips of the ring) or lines of 8.4-8.8 KiB (the
+    global-memory walk).  Those are walked byte-wise because the scan does not know their end: a line that does not end in the tile
+    after the one that owns it becomes a VS_W_LONG entry, which walk_in_strips never takes and the epilogue kernel walks with
+    walk_entry_global (route F1 of tests/varscan_walk_cases.py) - not because of the size of the ring, which holds 11 424 bytes."""
     rng = random.Random(seed)
     lines = []
     for i, (kind, spec, kw) in enumerate(tc.varscan_cases(m)):

@@ -50,8 +50,13 @@ def test_var_flt_vcf_equals_oracle(d, tmp_path, seed, eol):
 
 
 def test_deep_and_mixed_lines_take_the_other_code_paths(d, tmp_path):
-    """Blocks whose lines do not fit the LDS span are walked in global memory (depth 1500-4000), blocks of 128 and 64 lines
-    (mean line length), and a file that mixes 4 KiB lines with short ones: all equal to the restatement."""
+    """Deep lines (depth 1500-4000: 3 to 8 KB), files of lines of a few hundred bytes, and a file that mixes 6 KB lines with short
+    ones: all equal to the restatement.  The routes of today's scan (named in tests/varscan_walk_cases.py): a candidate whose end the
+    scan knows is packed into the strips of its wave's ring, one to three such lines per round (routes A to D); when a wave has more
+    than four rounds' worth of them the rest go over the shared list to the epilogue's strips (E) or, behind its 32 KiB, are walked
+    byte-wise (F2); a line that does not end in the tile after the one that owns it (some of the depth-4000 lines) has no known end
+    (VS_W_LONG) and is walked byte-wise in global memory by the epilogue (F1).  Which of these a line meets hangs on where it lies,
+    which this test does not control: tests/test_gpu_varscan_walk.py places lines on each route and asserts that they take it."""
     for seed, n, depths in ((21, 600, (1500, 2500, 4000, 30, 0)), (22, 3000, (150, 200, 120, 0)), (23, 3000, (300, 420, 8, 350)),
                             (24, 2500, (30, 30, 30, 30, 30, 30, 30, 3000))):
         data = fuzz.varscan_pileup(seed, n, depths=depths)
@@ -66,9 +71,13 @@ def test_deep_and_mixed_lines_take_the_other_code_paths(d, tmp_path):
 
 @pytest.mark.parametrize("seed", [1, 2, 3, 4])
 def test_arbitrary_read_base_text_walks_like_the_restatement(d, tmp_path, seed):
-    """Adversarial columns (fuzz.varscan_adversarial): the LDS walk, the global-memory walk and the restatement agree."""
+    """Adversarial columns (fuzz.varscan_adversarial) equal the restatement.  Their lines are short and their depth almost never
+    equals their quality length, so nearly all are parsed by varscan_parse_lds and walked in the strips of the ring (route B of
+    tests/varscan_walk_cases.py).  Seed 4 puts three lines of 72 KB between them: their end is unknown to the scan (VS_W_LONG) and
+    the epilogue kernel walks them byte-wise in global memory (route F1); the short lines around them keep their route.  The
+    VS_W_PLAIN shortcut and the byte-wise walk with adversarial tokens: tests/test_gpu_varscan_walk.py."""
     data = fuzz.varscan_adversarial(seed, 3000)
-    if seed == 4:                                               # the same lines between very long ones: blocks that walk global memory
+    if seed == 4:                                               # the same lines between three of 72 KB (VS_W_LONG: walked byte-wise by the epilogue)
         long_line = b"cL\t1\tA\t9000\t" + b".,Aa" * 9000 + b"\t" + b"I5" * 18000 + b"\n"
         lines = data.split(b"\n")
         data = b"\n".join(lines[:500]) + b"\n" + long_line * 3 + b"\n".join(lines[500:])
@@ -340,10 +349,15 @@ def test_empty_read_base_and_quality_columns_are_columns(d, tmp_path):
 
 
 def test_full_candidate_list_unaligned_text_and_lines_across_tiles(d, tmp_path):
-    """The index-free pass (k_varscan_scan): (1) more candidate lines than the list holds — depth-0 lines, which the
-    shortcut cannot vouch for, by the ten thousand — are looked at on the spot and the answer is the same; (2) text at every
-    alignment mod 16 in device memory (snpgpu_varscan_dev); (3) line terminators, TABs and whole lines placed on the edges of the
-    4 KiB tiles and of the ring of three tile slots, with LF / CR LF / lone CR ends."""
+    """The index-free pass (k_varscan_scan): (1) candidate lines by the ten thousand — depth-0 lines, which the shortcut cannot
+    vouch for — and the answer is the same.  They do NOT fill the list today: varscan_cand_cap has a floor of 2 x 16 384 x 64
+    entries, this 1.3 MB file has about 80 waves with a stretch of over 13 000 entries each, so every wave flushes into its own
+    stretch and walks its candidates from the ring's strips (route C of tests/varscan_walk_cases.py).  A list that is full, with
+    entries walked on the spot (route G) and flush() writing the shared list, is reached by
+    tests/test_gpu_varscan_walk.py::test_iv_a_shared_list_that_is_overfilled; (2) text at every alignment mod 16 in device memory
+    (snpgpu_varscan_dev); (3) line terminators, TABs and whole lines placed on the edges of the 4 KiB tiles, among them 8192 and
+    16384 where a wave's ring of TWO tile slots wraps around, with LF / CR LF / lone CR ends (the two-slot ring as the place the
+    candidates' lines are packed into: tests/test_gpu_varscan_walk.py)."""
     import torch
     from snp_pipeline_amd import varscan
     opts = varscan.Options("--min-var-freq 0.2 --min-reads2 2")
@@ -381,7 +395,7 @@ def test_full_candidate_list_unaligned_text_and_lines_across_tiles(d, tmp_path):
     variant = b"c1\t7\tA\t12\tGGGGGGgggggg\tIIIIIIIIIIII"
     plainl = b"c1\t6\tA\t12\t......,,,,,,\tIIIIIIIIIIII"
     for eol in (b"\n", b"\r\n", b"\r"):
-        for edge in (4096, 8192, 12288, 16384):                  # (12288: where a wave's ring of three tile slots wraps around)
+        for edge in (4096, 8192, 12288, 16384):                  # (8192, 16384: where a wave's ring of two tile slots wraps around)
             for delta in range(-len(variant) - 3, 4):
                 pad_total = edge + delta
                 head = []
