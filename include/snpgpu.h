@@ -877,6 +877,68 @@ int  snpgpu_write_nj_newick(const char *path, const char *ids, const uint64_t *i
                             const uint32_t *b, const int64_t *len_a, const int64_t *len_b, uint32_t n_merges,
                             const uint32_t *star, const int64_t *star_len);
 
+/* ---- bootstrap support of the neighbour-joining tree (csrc/nj_bootstrap.hip) ------------------------------------------------
+ * Additive entries of ABI 7, like the ones above: Felsenstein's bootstrap of the tree above, which of its branches the data
+ * supports.  Because the tree is stated in integers with a pinned tie-break, every replicate tree is unique and so are the
+ * counts: the support values are pinned byte for byte (tests/nj_bootstrap_cases.py restates all of this in Python).
+ *
+ * Samples are the rows 0 ... n-1, s the column count, B >= 1 the number of replicates, seed a 64-bit unsigned integer.  All
+ * arithmetic modulo 2^64:
+ *   G       = 0x9E3779B97F4A7C15
+ *   mix(z)  : z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;  z = (z ^ (z >> 27)) * 0x94D049BB133111EB;  return z ^ (z >> 31)
+ *   draw(seed, b, k) = mix(mix(seed + G (b + 1)) + G (k + 1))       replicate b = 0 ... B-1, position k = 0 ... s-1
+ *   c(b, k)          = floor(draw(seed, b, k) s / 2^64)             the high half of the 64 x 64-bit product
+ * Replicate b: its matrix is the distance over the multiset of columns {c(b,k)}: D_b(i,j) = the number of k at which both bytes
+ * of column c(b,k) are in ACGT after upper-casing and differ (the order of the columns does not enter); its tree is the
+ * neighbour-joining tree of D_b exactly as stated above.  A replicate the range guard refuses makes the whole call fail alike.
+ * Bipartitions: a tree of n >= 4 samples has n - 3 join records (a_t, b_t); record t defines the leaf set under the new node.
+ * Its canonical form is the side that does NOT hold sample 0 (the complement within the n samples when the leaf set holds it):
+ * n - 3 distinct non-trivial bipartitions per tree, each a bitset of W = ceil(n / 64) 64-bit words, bit i of word i / 64 sample
+ * i, bits >= n zero.  Support(t) of the main tree (of the unresampled matrix) is the number of replicates whose tree holds main
+ * bipartition t, 0 ... B; Percent(t) = floor((200 Support(t) + B) / (2 B)), half up, in integers.  n <= 3: nothing to count.
+ *
+ * snpgpu_bootstrap_columns_dev: d_cols[n_sites] (uint32) = c(replicate, .) in draw order.
+ * snpgpu_resample_packed_dev: d_out = the pack of sym[:, cols] from d_packed, the pack of sym (snpgpu_pack_matrix_dev: n_rows
+ * rows of snpgpu_packed_row_bytes(n_sites) bytes); d_out has rows of snpgpu_packed_row_bytes(n_cols) bytes and comes out
+ * byte-identical to snpgpu_pack_matrix_dev of the gathered symbols: all four planes, padding bits and words zero.  Any list,
+ * any order; a sorted one reads best.  The call first waits for the largest index of the list: one >= n_sites is refused with
+ * SNPGPU_E_ARG before anything is written.
+ * snpgpu_nj_splits_dev: from the device join records of n_trees trees of n samples (tree i at d_a / d_b + i (n - 3)),
+ * d_out[n_trees][n - 3][W] (uint64) in canonical form; n W words of workspace per tree are allocated (SNPGPU_E_NOMEM).  A record
+ * that names a slot >= n gives a zero row.  Nothing is written for n <= 3.
+ * snpgpu_split_support_dev: d_counts[i] = the number of the n_rep rows of d_rep equal to row i of d_main, on all n_words words;
+ * the n_main rows of d_main are distinct (equal ones: one of them gets the count).  No hash: the rows' indices are sorted by
+ * their words and every other row is looked up in that order. */
+int  snpgpu_bootstrap_columns_dev(snpgpu_ctx *ctx, uint64_t seed, uint32_t replicate, uint32_t n_sites, uint32_t *d_cols);
+/* ... the same columns ascending, as the host form below hands them to the resample: the draws and the library's merge sort in a
+ * workspace of its own (3 n_sites words), copied to d_cols; waits for the stream. */
+int  snpgpu_bootstrap_columns_sorted_dev(snpgpu_ctx *ctx, uint64_t seed, uint32_t replicate, uint32_t n_sites, uint32_t *d_cols);
+int  snpgpu_resample_packed_dev(snpgpu_ctx *ctx, const void *d_packed, uint32_t n_rows, uint32_t n_sites, const uint32_t *d_cols,
+                                uint32_t n_cols, void *d_out);
+int  snpgpu_nj_splits_dev(snpgpu_ctx *ctx, const uint32_t *d_a, const uint32_t *d_b, uint32_t n, uint32_t n_trees, uint64_t *d_out);
+int  snpgpu_split_support_dev(snpgpu_ctx *ctx, const uint64_t *d_main, uint32_t n_main, const uint64_t *d_rep, uint64_t n_rep,
+                              uint32_t n_words, uint32_t *d_counts);
+/* Host form on symbols: the outputs of snpgpu_nj, then out_support[n_rows - 3] (may be null for n_rows <= 3), the counts of the
+ * main tree's joins in round order.  replicates == 0 and null outputs are refused (SNPGPU_E_ARG) before any output is written.
+ * One upload and pack; per replicate the columns, their sort, the resample, the distance kernel and the NJ rounds, into one
+ * resampled pack and one n x n matrix; 8 bytes per join and replicate stay on the device; bipartitions and counts run over the
+ * replicates in bands sized from the free device memory.  Only the main tree and the counts cross the host link. */
+int  snpgpu_nj_bootstrap(snpgpu_ctx *ctx, const uint8_t *symbols, uint32_t n_rows, uint32_t n_sites, uint32_t replicates,
+                         uint64_t seed, uint32_t *out_a, uint32_t *out_b, int64_t *out_len_a, int64_t *out_len_b,
+                         int32_t *out_matrix, uint32_t *out_star, int64_t *out_star_len, uint32_t *out_n_merges,
+                         uint32_t *out_support);
+/* The text (host code).  snpgpu_write_nj_newick_support: the line of snpgpu_write_nj_newick with the node of merge e carrying
+ * Percent(e) as a decimal integer between its ")" and its ":", "((s1:1,s2:2)87:0.5,...);"; the trifurcation at the top carries
+ * none, so with n <= 3 the file is that of snpgpu_write_nj_newick.  snpgpu_write_nj_support: a table, header
+ * "Seq1\tSeq2\tSize\tSupport\tReplicates", one row per join in round order: the ids of slots a and b, the number of leaves
+ * under the new node, the count, B.  SNPGPU_E_ARG also for replicates == 0, a null support array beside a merge, a count above
+ * the replicates. */
+int  snpgpu_write_nj_newick_support(const char *path, const char *ids, const uint64_t *id_off, uint32_t n, const uint32_t *a,
+                                    const uint32_t *b, const int64_t *len_a, const int64_t *len_b, uint32_t n_merges,
+                                    const uint32_t *star, const int64_t *star_len, const uint32_t *support, uint32_t replicates);
+int  snpgpu_write_nj_support(const char *path, const char *ids, const uint64_t *id_off, uint32_t n, const uint32_t *a,
+                             const uint32_t *b, uint32_t n_merges, const uint32_t *support, uint32_t replicates);
+
 /* ---- the differing sites of pairs (csrc/pair_sites.hip) -----------------------------------------------------------------
  * Additive entries of ABI 7, like the ones above: by which columns two samples differ.  Column s of pair (a, b) differs iff
  * both bytes, after upper-casing, are in {A,C,G,T} and are not equal (utils.py:1135-1165, what the distance kernel counts), so

@@ -217,6 +217,14 @@ SIGNATURES = {
     "snpgpu_nj": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, _P, _P, _P, _P, _P, _P, _P, C.POINTER(C.c_uint32)]),
     "snpgpu_nj_of_matrix": (C.c_int, [_P, _P, C.c_uint32, C.c_uint64, _P, _P, _P, _P, _P, _P, C.POINTER(C.c_uint32)]),
     "snpgpu_write_nj_newick": (C.c_int, [C.c_char_p, _P, _P, C.c_uint32, _P, _P, _P, _P, C.c_uint32, _P, _P]),
+    "snpgpu_bootstrap_columns_dev": (C.c_int, [_P, C.c_uint64, C.c_uint32, C.c_uint32, _P]),
+    "snpgpu_bootstrap_columns_sorted_dev": (C.c_int, [_P, C.c_uint64, C.c_uint32, C.c_uint32, _P]),
+    "snpgpu_resample_packed_dev": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, _P, C.c_uint32, _P]),
+    "snpgpu_nj_splits_dev": (C.c_int, [_P, _P, _P, C.c_uint32, C.c_uint32, _P]),
+    "snpgpu_split_support_dev": (C.c_int, [_P, _P, C.c_uint32, _P, C.c_uint64, C.c_uint32, _P]),
+    "snpgpu_nj_bootstrap": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, _P, _P, _P, _P, _P, _P, _P, C.POINTER(C.c_uint32), _P]),
+    "snpgpu_write_nj_newick_support": (C.c_int, [C.c_char_p, _P, _P, C.c_uint32, _P, _P, _P, _P, C.c_uint32, _P, _P, _P, C.c_uint32]),
+    "snpgpu_write_nj_support": (C.c_int, [C.c_char_p, _P, _P, C.c_uint32, _P, _P, C.c_uint32, _P, C.c_uint32]),
     "snpgpu_pair_sites_dev": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, _P, _P, C.c_uint64, C.c_uint64, _P, _P, _P, C.POINTER(C.c_uint64)]),
     "snpgpu_pair_sites": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, _P, _P, C.c_uint64, C.c_uint64, _P, _P, _P, C.POINTER(C.c_uint64)]),
     "snpgpu_distance_outputs": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, C.c_int, _P, _P, _P, _P, C.c_int, C.c_int32, C.c_uint64, _P, _P, _P, C.POINTER(C.c_uint64),

@@ -218,6 +218,9 @@ def parse_argument_list(argv):
     sub.add_argument("--amdLinkageDendrogram", dest="amdLinkageDendrogramFile", type=str, default=None, metavar="FILE", help="Extension of this build: output file with the --amdLinkage tree as one Newick line in the form of --amdDendrogram: groups join at height distance / 2.")
     sub.add_argument("--amdLinkageClusters", dest="amdLinkageClustersFile", type=str, default=None, metavar="FILE", help="Extension of this build: output file in the format of --amdClusters with every sample's cluster number in the --amdLinkage tree cut at each threshold of --amdClusterThresholds (the merges whose distance is at most the threshold).")
     sub.add_argument("--amdNj", dest="amdNjFile", type=str, default=None, metavar="FILE", help="Extension of this build: output file with the neighbour-joining tree of the samples (Saitou & Nei's method with the Studier-Keppler criterion) as one Newick line with branch lengths in SNPs: an unrooted phylogeny that assumes no molecular clock, written as a trifurcation at the top.  Built on the device in 64-bit fixed point with 20 fractional bits, ties broken by the nodes' first samples, so the same matrix gives the same bytes; branch lengths may be negative and are written as they are.")
+    sub.add_argument("--amdNjBootstrap", dest="amdNjBootstrap", type=int, default=None, metavar="B", help="Extension of this build: bootstrap the --amdNj tree with B replicates (Felsenstein's bootstrap: each replicate draws as many columns as the matrix has, with replacement, and builds its own neighbour-joining tree on the device).  Every join node of the --amdNj line then carries, between its ')' and its ':', the percentage of replicates whose tree holds the same bipartition of the samples, rounded half up; topology and lengths are those of --amdNj alone.  The draws are a stated integer function of --amdNjSeed, so the same input gives the same bytes.  Needs --amdNj or --amdNjSupport.")
+    sub.add_argument("--amdNjSeed", dest="amdNjSeed", type=int, default=None, metavar="S", help="Extension of this build: the seed of --amdNjBootstrap, 0 ... 2^64 - 1.  Default 1.")
+    sub.add_argument("--amdNjSupport", dest="amdNjSupportFile", type=str, default=None, metavar="FILE", help="Extension of this build: output file with one row per join of the neighbour-joining tree in round order: Seq1 and Seq2 (the first samples of the two joined nodes), Size (the leaves under the new node), Support (in how many of the --amdNjBootstrap replicates the bipartition recurs) and Replicates.  Needs --amdNjBootstrap.")
     sub.add_argument("--amdClosePairSites", dest="amdClosePairSitesFile", type=str, default=None, metavar="FILE", help="Extension of this build: output file with the sites at which the two samples of every pair i < j within --amdMaxPairDistance differ, one Seq1 / Seq2 / Site / Base1 / Base2 row per site in ascending column order, the pairs in the pairwise file's order; a pair has as many rows as its distance.  Found on the device from the packed matrix; --amdClosePairs itself is not required and the full matrix is not written.")
     sub.add_argument("--amdMstSites", dest="amdMstSitesFile", type=str, default=None, metavar="FILE", help="Extension of this build: output file with the sites at which the two samples of every edge of the minimum spanning tree differ, in the order of the --amdMst file; rows as in --amdClosePairSites.")
     sub.add_argument("--amdPairSitesPairs", dest="amdPairSitesPairsFile", type=str, default=None, metavar="FILE", help="Extension of this build: input file with two tab-separated sample ids per line (further columns and a first line Seq1 / Seq2 are ignored); the sites at which each of these pairs differs go to --amdPairSitesOut.")

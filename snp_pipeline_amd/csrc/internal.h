@@ -305,6 +305,10 @@ private:
 // clusters.hip: the close pairs of a device matrix as a CSR in HOST arrays: one count pass; the entries when capacity has room for them
 int snpgpu_close_pairs_to_host(snpgpu_ctx *ctx, const int32_t *d_matrix, uint32_t n, int32_t threshold, uint64_t capacity, uint64_t *out_row_off, uint32_t *out_col,
                                int32_t *out_dist, uint64_t *out_n);
+// nj.hip: the neighbour-joining tree of a symmetric device int32 matrix, n >= 2: the n - 3 merges into DEVICE arrays (may be null
+// for n <= 3), the star to the host; waits for the stream.  nj_bootstrap.hip runs it once per replicate.
+int nj_run(snpgpu_ctx *ctx, const int32_t *d_matrix, uint32_t n, uint64_t row_stride, uint32_t *d_a, uint32_t *d_b, int64_t *d_len_a, int64_t *d_len_b,
+           uint32_t *out_star, int64_t *out_star_len);
 
 // ---- byte classes -----------------------------------------------------------------------------
 // What str.split() treats as a separator, restricted to ASCII (pileup.py:206/424).

@@ -313,7 +313,10 @@ __global__ void k_nj_star(const int64_t *W, uint32_t pitch, uint32_t m, const ui
     res->star_len[2] = wac - la;
 }
 
+}  // namespace
+
 // The tree of a device matrix: the merges into the DEVICE arrays d_a ... d_len_b (room for n - 3), the star to the host.  n >= 2.
+// (Declared in internal.h: csrc/nj_bootstrap.hip runs it once per replicate.)
 int nj_run(snpgpu_ctx *ctx, const int32_t *d_matrix, uint32_t n, uint64_t row_stride, uint32_t *d_a, uint32_t *d_b, int64_t *d_len_a, int64_t *d_len_b,
            uint32_t *out_star, int64_t *out_star_len) {
     hipStream_t st = ctx->stream;
@@ -376,6 +379,8 @@ int nj_run(snpgpu_ctx *ctx, const int32_t *d_matrix, uint32_t n, uint64_t row_st
     for (int s = 0; s < 3; ++s) { out_star[s] = got.star[s]; out_star_len[s] = got.star_len[s]; }
     return SNPGPU_OK;
 }
+
+namespace {
 
 void no_star(uint32_t *star, int64_t *star_len) {
     for (int s = 0; s < 3; ++s) { star[s] = NJ_NONE; star_len[s] = 0; }

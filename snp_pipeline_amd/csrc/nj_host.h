@@ -77,12 +77,44 @@ static inline bool nj_records_ok(uint32_t n, const uint32_t *a, const uint32_t *
     return true;
 }
 
+// Percent of the bootstrap (csrc/nj_bootstrap.hip): floor((200 count + B) / (2 B)), half up, in integers; B >= 1, count <= B
+static inline uint32_t nj_percent(uint32_t count, uint32_t replicates) { return (uint32_t)((200ull * count + replicates) / (2ull * replicates)); }
+
+template <typename Sink>
+static inline void nj_put_u32(Sink &o, uint32_t v) {
+    char tmp[12];
+    size_t at = sizeof(tmp);
+    do { tmp[--at] = (char)('0' + v % 10); v /= 10; } while (v);
+    o.put(tmp + at, sizeof(tmp) - at);
+}
+
+// support counts as they go with records nj_records_ok accepts: one per merge, none above the replicates, of which there is one at least
+static inline bool nj_support_ok(const uint32_t *support, uint32_t n_merges, uint32_t replicates) {
+    if (replicates == 0 || (n_merges && !support)) return false;
+    for (uint32_t e = 0; e < n_merges; ++e)
+        if (support[e] > replicates) return false;
+    return true;
+}
+
+// the merges alone as the joins of a tree of the n samples: max(n - 3, 0) of them, a < b < n, both live (b retires)
+static inline bool nj_joins_ok(uint32_t n, const uint32_t *a, const uint32_t *b, uint32_t n_merges) {
+    if (n_merges != (n > 3 ? n - 3 : 0u) || (n_merges && (!a || !b))) return false;
+    std::vector<uint8_t> live(n, 1);
+    for (uint32_t e = 0; e < n_merges; ++e) {
+        if (a[e] >= b[e] || b[e] >= n || !live[a[e]] || !live[b[e]]) return false;
+        live[b[e]] = 0;
+    }
+    return true;
+}
+
 // One Newick line of records nj_records_ok accepts.  Node k < n is leaf k, node n + e the join of merge e; inside a node the
 // child whose smallest sample is smaller (slot a) comes first; the star is a trifurcation at the top (two children for n = 2).
-// Written with an explicit stack: a chain of 10 000 nested joins is an ordinary tree here.
+// Written with an explicit stack: a chain of 10 000 nested joins is an ordinary tree here.  With support counts (nj_support_ok) the
+// node of merge e carries nj_percent(support[e], replicates) between its ')' and its ':'; the trifurcation at the top carries none.
 template <typename Sink>
 static inline void nj_put_newick(Sink &o, const char *ids, const uint64_t *id_off, uint32_t n, const uint32_t *a, const uint32_t *b, const int64_t *len_a,
-                                 const int64_t *len_b, uint32_t n_merges, const uint32_t *star, const int64_t *star_len) {
+                                 const int64_t *len_b, uint32_t n_merges, const uint32_t *star, const int64_t *star_len, const uint32_t *support = nullptr,
+                                 uint32_t replicates = 0) {
     auto label = [&](uint32_t i) { nj_put_label(o, ids + id_off[i], (size_t)(id_off[i + 1] - id_off[i])); };
     if (n == 1) label(0);
     if (n >= 2) {
@@ -114,7 +146,10 @@ static inline void nj_put_newick(Sink &o, const char *ids, const uint64_t *id_of
                     continue;
                 }
                 if (node < n) label(node);
-                else o.put(')');
+                else {
+                    o.put(')');
+                    if (support) nj_put_u32(o, nj_percent(support[node - n], replicates));
+                }
                 o.put(':');
                 nj_put_length(o, above[node]);
                 stack.pop_back();

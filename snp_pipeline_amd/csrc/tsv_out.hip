@@ -738,3 +738,33 @@ extern "C" int snpgpu_write_nj_newick(const char *path, const char *ids, const u
     nj_put_newick(o, ids, id_off, n, a, b, len_a, len_b, n_merges, star, star_len);
     return o.finish();
 }
+
+// ---- bootstrap support of that tree (additive: the counts of csrc/nj_bootstrap.hip as text; the checks and the writer are nj_host.h) ----
+extern "C" int snpgpu_write_nj_newick_support(const char *path, const char *ids, const uint64_t *id_off, uint32_t n, const uint32_t *a, const uint32_t *b,
+                                              const int64_t *len_a, const int64_t *len_b, uint32_t n_merges, const uint32_t *star, const int64_t *star_len,
+                                              const uint32_t *support, uint32_t replicates) {
+    if (!path || (n && (!ids || !id_off)) || !nj_records_ok(n, a, b, len_a, len_b, n_merges, star, star_len) || !nj_support_ok(support, n_merges, replicates))
+        return SNPGPU_E_ARG;
+    FileOut o(path);
+    if (o.failed) return SNPGPU_E_IO;
+    nj_put_newick(o, ids, id_off, n, a, b, len_a, len_b, n_merges, star, star_len, n_merges ? support : nullptr, replicates);
+    return o.finish();
+}
+
+extern "C" int snpgpu_write_nj_support(const char *path, const char *ids, const uint64_t *id_off, uint32_t n, const uint32_t *a, const uint32_t *b, uint32_t n_merges,
+                                       const uint32_t *support, uint32_t replicates) {
+    if (!path || (n && (!ids || !id_off)) || !nj_joins_ok(n, a, b, n_merges) || !nj_support_ok(support, n_merges, replicates)) return SNPGPU_E_ARG;
+    FileOut o(path);
+    if (o.failed) return SNPGPU_E_IO;
+    o.put("Seq1\tSeq2\tSize\tSupport\tReplicates\n", 34);
+    std::vector<uint32_t> size(n, 1);
+    for (uint32_t e = 0; e < n_merges && !o.failed; ++e) {
+        size[a[e]] += size[b[e]];
+        o.put(ids + id_off[a[e]], (size_t)(id_off[a[e] + 1] - id_off[a[e]])); o.put('\t');
+        o.put(ids + id_off[b[e]], (size_t)(id_off[b[e] + 1] - id_off[b[e]])); o.put('\t');
+        put_u64(o, size[a[e]]); o.put('\t');
+        put_u64(o, support[e]); o.put('\t');
+        put_u64(o, replicates); o.put('\n');
+    }
+    return o.finish();
+}

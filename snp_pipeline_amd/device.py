@@ -1269,6 +1269,50 @@ class Device(object):
         return self._nj_host(n, lambda a, b, la, lb, star, star_len, nm: self.lib.snpgpu_nj_of_matrix(
             self.ctx, _ptr(mat) if mat.size else None, n, n, a, b, la, lb, star, star_len, nm))
 
+    # ---- bootstrap support of the neighbour-joining tree (additive to distance.py:93-106) --------
+    def bootstrap_columns_dev(self, seed, replicate, n_sites, d_cols, ascending=False):
+        """c(replicate, 0 ... n_sites-1) of the bootstrap's statement (include/snpgpu.h) into the device uint32 array d_cols, in
+        draw order; ascending: sorted, as ``nj_bootstrap`` hands them to the resample."""
+        if not 0 <= int(seed) < 2 ** 64:
+            raise ValueError("the seed is a 64-bit unsigned integer")
+        call = self.lib.snpgpu_bootstrap_columns_sorted_dev if ascending else self.lib.snpgpu_bootstrap_columns_dev
+        self._check(call(self.ctx, int(seed), int(replicate), int(n_sites), C.c_void_p(int(d_cols)) if d_cols else None))
+
+    def resample_packed_dev(self, d_packed, n_rows, n_sites, d_cols, n_cols, d_out):
+        """The pack of sym[:, cols] into d_out (rows of packed_row_bytes(n_cols)) from d_packed, the pack of sym, and a device
+        uint32 list of n_cols columns: byte-identical to pack_matrix_dev of the gathered symbols.  A column >= n_sites is refused
+        before anything is written."""
+        opt = lambda v: C.c_void_p(int(v)) if v else None     # noqa: E731
+        self._check(self.lib.snpgpu_resample_packed_dev(self.ctx, opt(d_packed), int(n_rows), int(n_sites), opt(d_cols), int(n_cols), opt(d_out)))
+
+    def nj_splits_dev(self, d_a, d_b, n, n_trees, d_out):
+        """The canonical bipartitions (the side without sample 0) of the device join records of n_trees trees of n samples, tree i
+        at d_a / d_b + i (n - 3), into d_out[n_trees][n - 3][ceil(n / 64)] (uint64)."""
+        opt = lambda v: C.c_void_p(int(v)) if v else None     # noqa: E731
+        self._check(self.lib.snpgpu_nj_splits_dev(self.ctx, opt(d_a), opt(d_b), int(n), int(n_trees), opt(d_out)))
+
+    def split_support_dev(self, d_main, n_main, d_rep, n_rep, n_words, d_counts):
+        """d_counts[i] (uint32) = how many of the n_rep rows of d_rep equal row i of d_main, rows of n_words uint64 words."""
+        opt = lambda v: C.c_void_p(int(v)) if v else None     # noqa: E731
+        self._check(self.lib.snpgpu_split_support_dev(self.ctx, opt(d_main), int(n_main), opt(d_rep), int(n_rep), int(n_words), opt(d_counts)))
+
+    def nj_bootstrap(self, symbols, replicates, seed=1, want_matrix=False):
+        """symbols: (n, s) uint8 array of sequence bytes.  Returns the tuple of ``nj`` followed by the support array (uint32, one
+        count of 0 ... replicates per merge, in round order): in how many of the `replicates` bootstrap replicates of the columns
+        the bipartition of that join recurs.  Only the tree and the counts cross the host link."""
+        sym = np.ascontiguousarray(symbols, dtype=np.uint8)
+        n, s = sym.shape
+        if not 0 <= int(seed) < 2 ** 64:
+            raise ValueError("the seed is a 64-bit unsigned integer")
+        if not 0 <= int(replicates) < 2 ** 32:
+            raise ValueError("the number of replicates is a 32-bit unsigned integer")
+        mat = np.zeros((n, n), dtype=np.int32) if want_matrix else None
+        support = np.zeros(max(n - 3, 0), dtype=np.uint32)
+        got = self._nj_host(n, lambda a, b, la, lb, star, star_len, nm: self.lib.snpgpu_nj_bootstrap(
+            self.ctx, _ptr(sym) if sym.size else None, n, s, int(replicates), int(seed), a, b, la, lb, _ptr(mat) if want_matrix and mat.size else None, star, star_len,
+            nm, _ptr(support) if support.size else None))
+        return got + (support,) + ((mat,) if want_matrix else ())
+
     # ---- the differing sites of pairs (additive to distance.py:93-106) ---------------------------
     def pair_sites_dev(self, d_packed, n_rows, n_sites, d_a, d_b, n_pairs, capacity=0, d_pair_off=0, d_site=0, d_bases=0):
         """The columns at which the pairs (d_a[p], d_b[p]) of rows of a device packed matrix differ, pair by pair, ascending:

@@ -297,9 +297,19 @@ def write_linkage_outputs(ids, kind, merges, merges_file, dendrogram_file, clust
         write_clusters(clusters_file, ids, thresholds, numbers)
 
 
-def write_nj(path, ids, a, b, len_a, len_b, star, star_len):
+def _support_counts(support, replicates, merges):
+    support = np.ascontiguousarray(support, dtype=np.uint32)
+    if replicates is None or not 1 <= int(replicates) < 2 ** 32:
+        raise ValueError("support values need the number of replicates, 1 at least")
+    if len(support) != merges:
+        raise ValueError("one support count per merge")
+    return support
+
+
+def write_nj(path, ids, a, b, len_a, len_b, star, star_len, support=None, replicates=None):
     """The neighbour-joining tree (the values of Device.nj) as one Newick line: a trifurcation at the top, lengths in SNPs written
-    from integer millionths (csrc/nj_host.h)."""
+    from integer millionths (csrc/nj_host.h).  With support (the last value of Device.nj_bootstrap) and replicates every join node
+    carries floor((200 support + replicates) / (2 replicates)) between its ")" and its ":"."""
     from . import _lib as L
     blob, off = _id_table(ids)
     a, b = (np.ascontiguousarray(x, dtype=np.uint32) for x in (a, b))
@@ -309,14 +319,40 @@ def write_nj(path, ids, a, b, len_a, len_b, star, star_len):
     star = np.asarray([0xFFFFFFFF if s is None else int(s) for s in star], dtype=np.uint32)
     star_len = np.asarray([int(x) for x in star_len], dtype=np.int64)
     opt = lambda x: x.ctypes.data if x.size else None          # noqa: E731
-    rc = L.load().snpgpu_write_nj_newick(path.encode(), blob, off.ctypes.data, len(ids), opt(a), opt(b), opt(len_a), opt(len_b), len(a), star.ctypes.data,
-                                         star_len.ctypes.data)
+    if support is None:
+        name = "snpgpu_write_nj_newick"
+        rc = L.load().snpgpu_write_nj_newick(path.encode(), blob, off.ctypes.data, len(ids), opt(a), opt(b), opt(len_a), opt(len_b), len(a), star.ctypes.data,
+                                             star_len.ctypes.data)
+    else:
+        name = "snpgpu_write_nj_newick_support"
+        support = _support_counts(support, replicates, len(a))
+        rc = L.load().snpgpu_write_nj_newick_support(path.encode(), blob, off.ctypes.data, len(ids), opt(a), opt(b), opt(len_a), opt(len_b), len(a), star.ctypes.data,
+                                                     star_len.ctypes.data, opt(support), int(replicates))
     if rc == L.E_IO:
         raise IOError("cannot write %s" % path)
     if rc == L.E_ARG:
-        raise ValueError("the merges and the star are not a neighbour-joining tree of the %d ids" % len(ids))
+        raise ValueError("the merges and the star are not a neighbour-joining tree of the %d ids%s" % (len(ids), "" if support is None else ", or a count exceeds the replicates"))
     if rc != 0:
-        raise RuntimeError("snpgpu_write_nj_newick failed (%d)" % rc)
+        raise RuntimeError("%s failed (%d)" % (name, rc))
+
+
+def write_nj_support(path, ids, a, b, support, replicates):
+    """The support table of the joins (a, b of Device.nj_bootstrap, its counts) in round order: Seq1, Seq2 the ids of the two slots,
+    Size the leaves under the new node, Support the count, Replicates."""
+    from . import _lib as L
+    blob, off = _id_table(ids)
+    a, b = (np.ascontiguousarray(x, dtype=np.uint32) for x in (a, b))
+    if len(a) != len(b):
+        raise ValueError("a and b hold one entry per merge")
+    support = _support_counts(support, replicates, len(a))
+    opt = lambda x: x.ctypes.data if x.size else None          # noqa: E731
+    rc = L.load().snpgpu_write_nj_support(path.encode(), blob, off.ctypes.data, len(ids), opt(a), opt(b), len(a), opt(support), int(replicates))
+    if rc == L.E_IO:
+        raise IOError("cannot write %s" % path)
+    if rc == L.E_ARG:
+        raise ValueError("the merges are not the joins of a neighbour-joining tree of the %d ids, or a count exceeds the replicates" % len(ids))
+    if rc != 0:
+        raise RuntimeError("snpgpu_write_nj_support failed (%d)" % rc)
 
 
 def pairs_of_csr(row_off, col, dist, threshold):
@@ -604,6 +640,9 @@ def calculate_snp_distances(args):
     o.site_counts_file = getattr(args, "amdSiteCountsFile", None)
     o.cluster_snps_file = getattr(args, "amdClusterSnpsFile", None)
     o.nj_file = getattr(args, "amdNjFile", None)
+    o.nj_bootstrap = getattr(args, "amdNjBootstrap", None)
+    o.nj_seed = getattr(args, "amdNjSeed", None)
+    o.nj_support_file = getattr(args, "amdNjSupportFile", None)
     if utils.verify_existing_input_files("SNP matrix file", [o.input_file]) > 0:
         utils.global_error("Error: cannot calculate sequence distances without the snp matrix file.")
     if o.close_file and o.max_pair_distance is None:
@@ -640,8 +679,18 @@ def calculate_snp_distances(args):
         utils.global_error("Error: cannot find the nearest samples without the query file.")
     if o.with_compared and not (o.close_file or o.mst_file or o.nearest_file):
         utils.global_error("Error: --amdCompared needs at least one of --amdClosePairs, --amdMst and --amdNearest.")
+    if o.nj_support_file and o.nj_bootstrap is None:
+        utils.global_error("Error: --amdNjSupport needs --amdNjBootstrap.")
+    if o.nj_bootstrap is not None and not (o.nj_file or o.nj_support_file):
+        utils.global_error("Error: --amdNjBootstrap needs at least one of --amdNj and --amdNjSupport.")
+    if o.nj_seed is not None and o.nj_bootstrap is None:
+        utils.global_error("Error: --amdNjSeed needs --amdNjBootstrap.")
+    if o.nj_bootstrap is not None and not 1 <= o.nj_bootstrap < 2 ** 32:
+        utils.global_error("Error: --amdNjBootstrap takes a number of replicates of 1 at least (and below 2^32).")
+    if o.nj_seed is not None and not 0 <= o.nj_seed < 2 ** 64:
+        utils.global_error("Error: --amdNjSeed takes a seed of 0 ... 2^64 - 1.")
     outputs = [f for f in (o.pairwise_file, o.matrix_file, o.close_file, o.clusters_file, o.mst_file, o.dendrogram_file, o.close_sites_file, o.mst_sites_file, o.user_sites_file, o.nearest_file,
-                           o.compared_matrix_file, o.site_counts_file, o.cluster_snps_file, o.nj_file) + o.linkage_files if f]
+                           o.compared_matrix_file, o.site_counts_file, o.cluster_snps_file, o.nj_file, o.nj_support_file) + o.linkage_files if f]
     if not outputs:
         utils.global_error("Error: no output file specified.")
 
@@ -677,6 +726,19 @@ def calculate_snp_distances(args):
         # likewise on its own: one more upload and pack beside the other outputs, and the matrix in the layout of -m
         write_matrix(o.compared_matrix_file, *compared_of_matrix(default_device, file_ids, sym, lens))
         on_their_own += 1
+    if o.nj_bootstrap is not None:
+        # the bootstrap on its own too: one more upload and pack beside the other outputs; the tree is the one --amdNj alone writes,
+        # its join nodes carrying their support, and the shared path does not write it again
+        ids, rows = _sorted_rows(file_ids, sym, lens)
+        if rows is None:
+            rows = np.zeros((0, 0), dtype=np.uint8)
+        tree = default_device().nj_bootstrap(rows, o.nj_bootstrap, 1 if o.nj_seed is None else o.nj_seed)
+        if o.nj_file:
+            write_nj(o.nj_file, ids, *tree[:6], support=tree[6], replicates=o.nj_bootstrap)
+            on_their_own += 1
+        if o.nj_support_file:
+            write_nj_support(o.nj_support_file, ids, tree[0], tree[1], tree[6], o.nj_bootstrap)
+            on_their_own += 1
     if len(outputs) == on_their_own:
         return
     _write_distance_outputs(default_device, o, file_ids, sym, lens, named_sites)
@@ -750,7 +812,7 @@ def _write_distance_outputs(device_of, o, file_ids, sym, lens, named_sites):
         if o.linkage_kind:
             merges = dev.linkage_of_matrix(mat, o.linkage_kind) if plan.host_matrix else dev.linkage(rows, o.linkage_kind)
             write_linkage_outputs(ids, o.linkage_kind, merges, o.linkage_files[0], o.linkage_files[1], o.linkage_files[2], o.thresholds)
-        if o.nj_file:
+        if o.nj_file and o.nj_bootstrap is None:
             write_nj(o.nj_file, ids, *(dev.nj_of_matrix(mat) if plan.host_matrix else dev.nj(rows)))
         if o.pairwise_file:
             write_pairwise(o.pairwise_file, ids, mat)

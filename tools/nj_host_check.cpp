@@ -4,7 +4,8 @@
 // It builds random trees of 0 ... 2 000 samples as records (merges in round order and the star), with lengths of either sign up to
 // the ends of 64 bits and ids that need quoting, checks them (nj_records_ok: what snpgpu_write_nj_newick does first), writes them
 // (nj_put_newick into a string: the function that entry point writes its file with) and compares the line with the tree joined
-// slot by slot as strings; then the records the check must refuse.
+// slot by slot as strings; the same with bootstrap support counts (nj_support_ok, nj_joins_ok, nj_percent: what
+// snpgpu_write_nj_newick_support and snpgpu_write_nj_support check and write); then the records the check must refuse.
 // No GPU is touched and nothing but that header is compiled in.
 #include <stdio.h>
 #include <stdlib.h>
@@ -73,13 +74,14 @@ std::string length_text(int64_t x) {
 }
 
 // the text the statement gives, built the slow way: strings joined per slot
-std::string expected(const std::vector<std::string> &labels, const Records &r) {
+std::string expected(const std::vector<std::string> &labels, const Records &r, const std::vector<uint32_t> *support = nullptr, uint32_t replicates = 0) {
     const uint32_t n = (uint32_t)labels.size();
     if (n == 0) return ";\n";
     if (n == 1) return labels[0] + ";\n";
     std::vector<std::string> text(labels);
     for (size_t e = 0; e < r.a.size(); ++e) {
-        text[r.a[e]] = "(" + text[r.a[e]] + ":" + length_text(r.la[e]) + "," + text[r.b[e]] + ":" + length_text(r.lb[e]) + ")";
+        text[r.a[e]] = "(" + text[r.a[e]] + ":" + length_text(r.la[e]) + "," + text[r.b[e]] + ":" + length_text(r.lb[e]) + ")" +
+                       (support ? std::to_string((200ull * (*support)[e] + replicates) / (2ull * replicates)) : std::string());
         text[r.b[e]].clear();
     }
     std::string out = "(";
@@ -129,7 +131,25 @@ int main() {
             Text t;
             nj_put_newick(t, ids.data(), off.data(), n, r.a.data(), r.b.data(), r.la.data(), r.lb.data(), m, r.star, r.star_len);
             expect(t.s == expected(labels, r), "nj_put_newick differs from the tree joined slot by slot", n, kind);
+            // the same line with bootstrap support (what snpgpu_write_nj_newick_support writes), counts at both ends of their range
+            for (uint32_t replicates : {1u, 3u, 8u, 1000u, 0xFFFFFFFFu}) {
+                std::vector<uint32_t> support(m);
+                for (uint32_t e = 0; e < m; ++e) support[e] = e == 0 ? 0u : e == 1 ? replicates : rnd(replicates) + (rnd(2) ? 1u : 0u);
+                expect(nj_support_ok(support.data(), m, replicates) && nj_joins_ok(n, r.a.data(), r.b.data(), m), "counts within the replicates are refused", n, kind);
+                Text with;
+                nj_put_newick(with, ids.data(), off.data(), n, r.a.data(), r.b.data(), r.la.data(), r.lb.data(), m, r.star, r.star_len, m ? support.data() : nullptr, replicates);
+                expect(with.s == expected(labels, r, &support, replicates), "nj_put_newick with support differs from the tree joined slot by slot", n, kind);
+                expect(m > 0 || with.s == t.s, "without a join the line with support is the line without", n, kind);
+                if (m && replicates < 0xFFFFFFFFu) {
+                    support[m - 1] = replicates + 1;
+                    expect(!nj_support_ok(support.data(), m, replicates), "a count above the replicates is refused", n, kind);
+                }
+                expect(!nj_support_ok(support.data(), m, 0) && (m == 0 || !nj_support_ok(nullptr, m, replicates)), "no replicate, or no counts beside a join, is refused", n, kind);
+            }
+            expect(nj_percent(0, 7) == 0 && nj_percent(7, 7) == 100 && nj_percent(1, 8) == 13 && nj_percent(1, 3) == 33 && nj_percent(0xFFFFFFFFu, 0xFFFFFFFFu) == 100,
+                   "the percentage is half up and exact at the ends of 32 bits", n, kind);
             if (n >= 5) {                                            // what is not a tree is refused before anything is indexed with it
+                expect(!nj_joins_ok(n, r.b.data(), r.a.data(), m) && !nj_joins_ok(n - 1, r.a.data(), r.b.data(), m), "joins that are no tree are refused", n, kind);
                 Records bad = r;
                 bad.b[m - 1] = n + 5;
                 expect(!ok(n, bad), "an index past n is refused", n, kind);
