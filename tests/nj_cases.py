@@ -80,10 +80,11 @@ def nj(mat):
     return merges, star, star_len
 
 
-def nj_numpy(mat, want_lowest=False):
+def nj_numpy(mat, want_lowest=False, rounds=None):
     """The same tree with int64 arrays: the live slots are kept together in their order, so the first least entry of the upper
     triangle in row-major order is the least (Q, i, j).  The asserted bound is what makes int64 enough.  want_lowest adds the
-    largest and the lowest working value ever held, in units of 2^-F."""
+    largest and the lowest working value ever held, in units of 2^-F.  With `rounds` it stops after that many joins and returns
+    their records alone (nj_prefix)."""
     mat = np.asarray(mat)
     n = mat.shape[0]
     assert mat.shape == (n, n) and not refused(mat)
@@ -94,7 +95,7 @@ def nj_numpy(mat, want_lowest=False):
     slots = np.arange(n)
     merges = []
     highest, lowest = (int(w.max()), int(w.min())) if n else (0, 0)
-    while len(slots) > 3:
+    while len(slots) > 3 and (rounds is None or len(merges) < rounds):
         r = len(slots)
         R = w.sum(axis=1)
         q = (r - 2) * w - R[:, None] - R[None, :]
@@ -112,9 +113,139 @@ def nj_numpy(mat, want_lowest=False):
         slots = slots[keep]
         assert int(np.abs(w).max()) <= bound
         highest, lowest = max(highest, int(w.max())), min(lowest, int(w.min()))
+    if rounds is not None:
+        return merges
     star, star_len = _star([[int(x) for x in row] for row in w], list(range(len(slots))), n)
     star = tuple(None if s is None else int(slots[s]) for s in star)
     return (merges, star, star_len) + ((highest, lowest) if want_lowest else ())
+
+
+def nj_prefix(mat, rounds):
+    """The first `rounds` join records of nj_numpy(mat): the same code, stopping there."""
+    return nj_numpy(mat, rounds=rounds)
+
+
+# ---- checking a tree without building it --------------------------------------------------------------------------------------
+class Replay(object):
+    """The state of the statement while given joins are applied to it: the full n x n working matrix (rows and columns of retired
+    slots stay and are never read), the live mask, and R kept incrementally: a join moves R(k) by new - w(a,k) - w(b,k) for every
+    other live k and gives R(a) the sum of the new values.  tests/test_nj_cpu.py shows that this R is the statement's sum over the
+    live k in every round.  A join costs O(n); ``ranked`` is the r^2 pass that finds the least pairs."""
+
+    def __init__(self, mat):
+        mat = np.asarray(mat)
+        self.n = n = mat.shape[0]
+        assert mat.shape == (n, n) and not refused(mat)
+        self.bound = limit(n)
+        self.w = mat.astype(np.int64) << F
+        np.fill_diagonal(self.w, 0)
+        assert np.array_equal(self.w, self.w.T)
+        self.live = np.ones(n, dtype=bool)
+        self.R = self.w.sum(axis=1)
+        self.r = n
+
+    def summed_R(self):
+        """R as the statement has it: the sum of w(i,k) over live k != i, for the live i (0 elsewhere)."""
+        return np.where(self.live, (self.w * self.live[None, :]).sum(axis=1), 0)
+
+    def ranked(self, count=1):
+        """The first `count` live pairs i < j in the order (Q, i, j)."""
+        idx = np.flatnonzero(self.live)
+        r = len(idx)
+        assert r == self.r and count <= r * (r - 1) // 2
+        q = self.w[idx][:, idx]
+        q *= r - 2
+        q -= self.R[idx][:, None]
+        q -= self.R[idx][None, :]
+        q[np.tri(r, dtype=bool)] = np.iinfo(np.int64).max           # the diagonal and below: row-major argmin is then the order
+        out = []
+        for _ in range(count):
+            i, j = divmod(int(np.argmin(q)), r)
+            out.append((int(idx[i]), int(idx[j])))
+            q[i, j] = np.iinfo(np.int64).max
+        return out
+
+    def lengths(self, a, b):
+        wab = int(self.w[a, b])
+        la = ((self.r - 2) * wab + int(self.R[a]) - int(self.R[b])) // (2 * (self.r - 2))
+        return la, wab - la
+
+    def join(self, a, b):
+        w, R = self.w, self.R
+        others = self.live.copy()
+        others[a] = others[b] = False
+        fresh = np.where(others, (w[a] + w[b] - w[a, b]) >> 1, 0)
+        assert int(np.abs(fresh).max()) <= self.bound
+        R += np.where(others, fresh - w[a] - w[b], 0)
+        R[a] = fresh.sum()
+        R[b] = 0
+        w[a, :] = fresh
+        w[:, a] = fresh
+        self.live[b] = False
+        self.r -= 1
+
+    def star(self):
+        slots = [int(i) for i in np.flatnonzero(self.live)]
+        sub = [[int(self.w[i, k]) for k in slots] for i in slots]
+        star, star_len = _star(sub, list(range(len(slots))), self.n)
+        return tuple(None if s is None else slots[s] for s in star), star_len
+
+
+def check_tree(mat, tree, argmin_rounds=(), summed_R=False):
+    """Is `tree` the tree of the statement?  The recorded joins are replayed: every round must name two live slots a < b with the
+    lengths the statement gives that pair in the replayed state, the star and its lengths must be the statement's, and in the rounds
+    of `argmin_rounds` the pair must be the least (Q, i, j) of all live pairs.  A wrong state after any round shows in the lengths of
+    the rounds behind it; a wrong choice from a right state shows only in an argmin round.  With summed_R the incremental R is
+    compared with the sum over the live slots in every round.  Raises AssertionError naming the round."""
+    merges, star, star_len = tree
+    mat = np.asarray(mat)
+    n = mat.shape[0]
+    assert len(merges) == max(n - 3, 0), "the tree has %d joins, not %d" % (len(merges), max(n - 3, 0))
+    argmin_rounds = set(argmin_rounds)
+    assert all(0 <= t < len(merges) for t in argmin_rounds), "an argmin round that is no round"
+    state = Replay(mat)
+    for t, (a, b, la, lb) in enumerate(merges):
+        assert 0 <= a < b < n and state.live[a] and state.live[b], "round %d: (%d, %d) are not two live slots a < b" % (t, a, b)
+        if summed_R:
+            assert np.array_equal(state.R, state.summed_R()), "round %d: the incremental R is not the sum over the live slots" % t
+        if t in argmin_rounds:
+            least = state.ranked(1)[0]
+            assert least == (a, b), "round %d: (%d, %d) joined, the least (Q, i, j) is (%d, %d)" % ((t, a, b) + least)
+        want = state.lengths(a, b)
+        assert (la, lb) == want, "round %d: the lengths of (%d, %d) are (%d, %d), not (%d, %d)" % ((t, a, b, la, lb) + want)
+        state.join(a, b)
+    want = state.star()
+    assert (tuple(star), tuple(star_len)) == want, "the star: %r %r, not %r %r" % ((tuple(star), tuple(star_len)) + want)
+
+
+def far_cherries(n, seed, pairs):
+    """Symmetric random entries in 40 ... 60 with a 1 planted at each of the disjoint `pairs`.  A row sum is about 50 r (r live slots;
+    it scatters by some 6 sqrt(r)), so Q of a planted pair is about (r - 2) - 100 r = -99 r and that of any other pair 40 r - 100 r =
+    -60 r at best: the first len(pairs) rounds join exactly the planted pairs, in an order their row sums decide, and the new node's
+    distances are floor((w(a,k) + w(b,k) - 1) / 2), ordinary again.  tests/test_nj_cpu.py asserts that for the lists the GPU tests
+    use (tests/nj_geometry.py).  Where a pair lies decides which loop turn of a kernel finds it."""
+    pairs = [(int(i), int(j)) for i, j in pairs]
+    assert all(0 <= i < j < n for i, j in pairs) and len({x for p in pairs for x in p}) == 2 * len(pairs)
+    rng = np.random.default_rng(seed)
+    m = np.triu(rng.integers(40, 61, size=(n, n)), 1).astype(np.int32)
+    m = m + m.T
+    for i, j in pairs:
+        m[i, j] = m[j, i] = 1
+    assert not refused(m) and (60 << F) <= limit(n)                  # (the update never grows an entry: test_nj_cpu.py)
+    return m
+
+
+def compaction_rounds(n, num, den):
+    """[(round, m before, m after)]: the rounds before which the device moves the live columns together, by the arithmetic of
+    nj_run's loop: when r den <= m num."""
+    out, m, r, t = [], n, n, 0
+    while r > 3:
+        if r * den <= m * num:
+            out.append((t, m, r))
+            m = r
+        r -= 1
+        t += 1
+    return out
 
 
 def negative_lengths(tree):
@@ -177,6 +308,46 @@ def additive_tree(n, seed, longest=9):
         mat[leaf] = [seen[k] for k in range(n)]
     assert np.array_equal(mat, mat.T)
     return mat
+
+
+def additive_tree_by_rows(n, seed, longest=9):
+    """The matrix of additive_tree(n, seed, longest), drawn with the same calls, from a node-to-node table kept while the tree grows
+    instead of a walk per leaf: a node on the edge (u, v) is min(d(u, .) + first, d(v, .) + rest) from everything, a leaf its node's
+    row plus its edge.  Fast enough for 2 100 leaves."""
+    assert n >= 3
+    rng = np.random.default_rng(seed)
+    d = np.zeros((2 * n - 2, 2 * n - 2), dtype=np.int64)             # rows and columns of nodes that do not exist yet are rewritten when they appear
+
+    def place(x, row):
+        d[x, :] = row
+        d[:, x] = row
+        d[x, x] = 0
+
+    inner = n
+    edges = [[i, inner, int(rng.integers(1, longest + 1))] for i in range(3)]
+    edges[int(rng.integers(0, 3))][2] = int(rng.integers(2, longest + 1))
+    for i in range(3):
+        place(i, np.zeros(2 * n - 2, dtype=np.int64))
+    for i, _, length in edges:
+        d[i, inner] = d[inner, i] = length
+    for i in range(3):
+        for k in range(i):
+            d[i, k] = d[k, i] = edges[i][2] + edges[k][2]
+    for leaf in range(3, n):
+        long_enough = [e for e in edges if e[2] >= 2]
+        e = long_enough[int(rng.integers(0, len(long_enough)))]
+        first = int(rng.integers(1, e[2]))
+        inner += 1
+        u, v, length = e
+        e[1], e[2] = inner, first
+        edges.append([inner, v, length - first])
+        place(inner, np.minimum(d[u] + first, d[v] + (length - first)))
+        d[u, inner] = d[inner, u] = first                            # (u's own row holds 0 for itself: the minimum is right there too; written for clarity)
+        hang = int(rng.integers(2, longest + 1))
+        edges.append([leaf, inner, hang])
+        place(leaf, d[inner] + hang)
+        d[leaf, inner] = d[inner, leaf] = hang
+    return np.ascontiguousarray(d[:n, :n]).astype(np.int32)
 
 
 # the matrices the GPU tests give to the device, by name; tests/test_nj_cpu.py asserts the range bound on every one of them

@@ -104,7 +104,9 @@ def test_an_additive_tree_is_recovered_exactly(n):
 def test_more_rows_than_the_grid_of_the_row_kernels_and_through_the_compactions():
     """2 100 rows go round the grid-stride loops of k_nj_init, k_nj_rows and k_nj_compact, k_nj_update takes nine workgroups, and the
     live columns move together every time an eighth of the stored slots have retired.  With every entry 2 the tree is known without
-    building it: the ids break every tie."""
+    building it: the ids break every tie.  What this does not show: the winning row is always 0 and the winning column among the first
+    few, so the later sub-steps and turns of k_nj_rows' column loop and the later rows of k_nj_pick never decide a join, and every value
+    a compaction moves is a 2 beside another 2.  tests/test_gpu_nj_edges.py sends matrices whose values differ everywhere."""
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     src = open(os.path.join(root, "snp_pipeline_amd", "csrc", "nj.hip")).read()
     cap = int(re.search(r"#define NJ_ROW_GRID_CAP (\d+)", src).group(1))

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 from tests import nj_cases as nc
+from tests import nj_geometry as ng
 
 ONE = nc.ONE
 
@@ -204,3 +205,175 @@ def test_the_new_option_keeps_the_reference_namespace():
     assert "amdNjFile" in full and set(full) == set(plain) and plain["amdNjFile"] is None and full["amdNjFile"] == "tree.nwk"
     batch = vars(cli.parse_command_line("hot_path_batch dirs.txt ref.fasta --nj"))
     assert batch["nj"] is True and vars(cli.parse_command_line("hot_path_batch dirs.txt ref.fasta"))["nj"] is False
+
+
+# ---- the checker of tests/nj_cases.py: check_tree, nj_prefix, far_cherries, compaction_rounds -------------------------------------
+CHECKED = [(name, n) for name in sorted(nc.MATRICES) for n in (4, 5, 64, 65, 130)]      # ("largest" stays within 2^61 / n up to 1 024 samples)
+
+
+def _matrix(name, n):
+    return np.asarray(nc.MATRICES[name](n))
+
+
+@pytest.mark.parametrize("name,n", CHECKED)
+def test_check_tree_accepts_the_trees_of_both_forms_with_every_round_checked(name, n):
+    """... and the incremental R of the replay is the statement's sum over the live slots in every round (summed_R)."""
+    mat = _matrix(name, n)
+    tree = nc.nj_numpy(mat)
+    nc.check_tree(mat, tree, range(n - 3), summed_R=True)
+    nc.check_tree(mat, tree)
+    nc.check_tree(mat, nc.nj(mat), range(n - 3), summed_R=True)
+
+
+def test_check_tree_accepts_the_smallest_trees_and_rejects_their_wrong_stars():
+    for n in (0, 1, 2, 3):
+        mat = nc.random_matrix(n, 5, high=40)
+        tree = nc.nj(mat)
+        nc.check_tree(mat, tree)
+        if n >= 2:
+            for s in range(n):
+                lengths = list(tree[2])
+                lengths[s] += 1
+                with pytest.raises(AssertionError, match="the star"):
+                    nc.check_tree(mat, (tree[0], tree[1], tuple(lengths)))
+    with pytest.raises(AssertionError, match="joins"):
+        nc.check_tree(nc.random_matrix(5, 5, high=40), ([], (0, 1, 2), (0, 0, 0)))
+
+
+def _state_at(mat, merges, t):
+    state = nc.Replay(mat)
+    for a, b, _, _ in merges[:t]:
+        state.join(a, b)
+    return state
+
+
+def _raises_in_round(mat, tree, rounds, t, what):
+    with pytest.raises(AssertionError) as ei:
+        nc.check_tree(mat, tree, rounds)
+    assert str(ei.value).startswith("round %d: " % t) and what in str(ei.value), str(ei.value)
+
+
+@pytest.mark.parametrize("name,n", [("random", 64), ("ties3", 65), ("wide", 130), ("additive", 65)])
+def test_check_tree_rejects_every_single_change_and_names_the_round(name, n):
+    mat = _matrix(name, n)
+    merges, star, star_len = nc.nj_numpy(mat)
+    every = range(n - 3)
+    for t in (0, 1, n // 2, n - 5, n - 4):
+        a, b, la, lb = merges[t]
+        state = _state_at(mat, merges, t)
+        # the second-best pair with the lengths that are right for it: only the choice is wrong
+        best, second = state.ranked(2)
+        assert best == (a, b)
+        wrong = merges[:t] + [second + state.lengths(*second)] + merges[t + 1:]
+        _raises_in_round(mat, (wrong, star, star_len), every, t, "the least (Q, i, j)")
+        # a and b swapped
+        _raises_in_round(mat, (merges[:t] + [(b, a, la, lb)] + merges[t + 1:], star, star_len), every, t, "not two live slots")
+        # a length moved by one unit from one branch to the other
+        _raises_in_round(mat, (merges[:t] + [(a, b, la + 1, lb - 1)] + merges[t + 1:], star, star_len), every, t, "the lengths")
+        _raises_in_round(mat, (merges[:t] + [(a, b, la + 1, lb - 1)] + merges[t + 1:], star, star_len), (), t, "the lengths")
+        # two consecutive joins exchanged: the later one is not the least of the earlier round (or names a slot that has retired)
+        if t + 1 < n - 3:
+            swapped = merges[:t] + [merges[t + 1], merges[t]] + merges[t + 2:]
+            with pytest.raises(AssertionError) as ei:
+                nc.check_tree(mat, (swapped, star, star_len), every)
+            assert str(ei.value).startswith("round %d: " % t), str(ei.value)     # (on an additive matrix only the choice tells: the lengths of two cherries are right in either order)
+    for s in range(3):
+        lengths = list(star_len)
+        lengths[s] -= 1
+        with pytest.raises(AssertionError, match="the star"):
+            nc.check_tree(mat, (merges, star, tuple(lengths)))
+        retired = merges[-1][1]
+        slots = list(star)
+        slots[s] = retired
+        with pytest.raises(AssertionError, match="the star"):
+            nc.check_tree(mat, (merges, tuple(slots), star_len))
+
+
+def test_a_record_changed_in_a_round_that_is_not_sampled_fails_a_later_length_check():
+    """What makes sampling the argmin rounds sound against a corrupted state: every later round's lengths come from w(a,b), R(a) and
+    R(b) of the replayed state, and a wrong join moves R of every live slot.  Here round t takes the second-best pair with the lengths
+    that are right for it, so round t itself passes when it is no argmin round; the records behind it are the true tree's."""
+    n = 96
+    mat = nc.random_matrix(n, 21, high=40)
+    merges, star, star_len = nc.nj_numpy(mat)
+    for t in (0, 7, 40, 80):
+        state = _state_at(mat, merges, t)
+        best, second = state.ranked(2)
+        assert best == merges[t][:2]
+        wrong = merges[:t] + [second + state.lengths(*second)] + merges[t + 1:]
+        sampled = set(range(0, n - 3, 32)) - {t} | {n - 4}
+        with pytest.raises(AssertionError) as ei:
+            nc.check_tree(mat, (wrong, star, star_len), sampled - {t})
+        later = int(str(ei.value).split(":")[0].split()[1])
+        assert str(ei.value).startswith("round ") and t < later <= t + 2, str(ei.value)
+
+
+@pytest.mark.parametrize("name,n", [("random", 65), ("ties3", 130), ("equal2", 64), ("zero", 9)])
+def test_the_prefix_is_the_head_of_the_tree(name, n):
+    mat = _matrix(name, n)
+    merges = nc.nj_numpy(mat)[0]
+    for rounds in (0, 1, 8, n - 4, n - 3, n):
+        assert nc.nj_prefix(mat, rounds) == merges[:rounds]
+
+
+def test_the_planted_pairs_of_far_cherries_are_the_first_joins():
+    small = [(0, 39), (1, 20), (5, 6), (37, 38)]
+    for n, pairs in [(40, small)] + sorted(ng.CHERRIES.items()):
+        mat = nc.far_cherries(n, ng.CHERRY_SEED, pairs)
+        assert np.array_equal(mat, mat.T) and not mat.diagonal().any() and not nc.refused(mat)
+        off = mat[~np.eye(n, dtype=bool)]
+        assert sorted(np.unique(off).tolist()) == [1] + list(range(40, 61)) and int((off == 1).sum()) == 2 * len(pairs)
+        head = nc.nj_prefix(mat, len(pairs) + 1)
+        assert sorted(m[:2] for m in head[:len(pairs)]) == sorted(pairs), n
+        assert head[len(pairs)][:2] not in pairs and all(m[2] + m[3] == nc.ONE for m in head[:len(pairs)])
+    assert np.array_equal(nc.far_cherries(40, 7, small), nc.far_cherries(40, 7, small))
+    assert not np.array_equal(nc.far_cherries(40, 7, small), nc.far_cherries(40, 8, small))
+
+
+def test_the_planted_pairs_fall_where_the_loops_of_the_kernels_turn():
+    """Written over the constants of csrc/nj.hip, so the conditions move with them."""
+    c = ng.kernel_constants()
+    turn = 2 * c["THREADS"] * c["UNROLL"]                            # the columns of one turn of k_nj_rows' outer loop
+    assert turn == 2048 and c["PICK_THREADS"] == 1024 and c["ROW_GRID_CAP"] == 2048 and 0 < c["COMPACT_NUM"] < c["COMPACT_DEN"]
+    for n, pairs in ng.CHERRIES.items():
+        steps = {ng.row_step(i, k, c) for i, k in pairs}
+        reachable = min(c["UNROLL"], (n - 1) // (2 * c["THREADS"]) + 1)       # the sub-steps a row of n columns has at all
+        assert {u for turn_, u in steps if turn_ == 0} == set(range(reachable)), n
+        assert {2, reachable - 1} <= {u for _, u in steps}
+        assert any(i >= c["PICK_THREADS"] for i, _ in pairs)                  # a second row of a thread of k_nj_pick wins
+        assert any(i >= n - 4 and k >= n - 2 for i, k in pairs)               # the last rows
+        assert any(i <= 1 and k == n - 1 for i, k in pairs)                   # the first row against the last column
+    pairs = ng.CHERRIES[2100]
+    assert any(i <= 1 and k >= turn + 2 and ng.row_step(i, k, c)[0] == 1 for i, k in pairs)      # the second turn of the outer loop
+    assert {ng.row_step(i, k, c)[1] for i, k in pairs if ng.row_step(i, k, c)[0] == 0} == {0, 1, 2, 3}
+    assert any(i >= c["ROW_GRID_CAP"] for i, _ in pairs)                      # a row of the grid-stride turn
+    assert any(3 in ng.row_step(i, k, c) for i, k in ng.CHERRIES[1600]) and any(i >= 1024 for i, _ in ng.CHERRIES[1600])
+
+
+def test_the_compaction_rounds_are_those_of_the_host_loop():
+    assert nc.compaction_rounds(16, 7, 8) == [(2, 16, 14), (4, 14, 12), (6, 12, 10), (8, 10, 8), (9, 8, 7), (10, 7, 6), (11, 6, 5), (12, 5, 4)]
+    assert nc.compaction_rounds(3, 7, 8) == [] and nc.compaction_rounds(100, 0, 8) == []
+    c = ng.kernel_constants()
+    for n in (1100, 1600, 2100):
+        rounds = nc.compaction_rounds(n, c["COMPACT_NUM"], c["COMPACT_DEN"])
+        assert rounds[0][1] == n and all(x[2] == y[1] for x, y in zip(rounds, rounds[1:])) and all(0 < t < n - 3 for t, _, _ in rounds)
+        assert all(after * c["COMPACT_DEN"] <= before * c["COMPACT_NUM"] < (after + 1) * c["COMPACT_DEN"] for _, before, after in rounds)
+        assert all(before - after == t - s for (s, _, _), (t, before, after) in zip([(0, 0, 0)] + rounds, rounds))   # a round retires one slot
+        assert rounds == ng.compactions(n)
+        wanted = ng.argmin_schedule(n, 16, rounds)
+        ng.assert_schedule(n, 16, rounds, wanted)
+        assert len(wanted) >= 64 and all({t - 1, t, t + 1} <= wanted for t, _, _ in rounds if t + 1 < n - 3)
+    with pytest.raises(AssertionError):                              # a schedule that dropped one round of a compaction is refused
+        ng.assert_schedule(n, 16, rounds, wanted - {rounds[1][0] + 1})
+    with pytest.raises(AssertionError):
+        ng.assert_schedule(n, 16, rounds, wanted - {64})
+
+
+def test_the_additive_matrix_by_rows_is_the_additive_matrix():
+    for n in (3, 4, 5, 17, 65, 130):
+        for seed in (1, 2, 7):
+            assert np.array_equal(nc.additive_tree_by_rows(n, seed), nc.additive_tree(n, seed)), (n, seed)
+    assert np.array_equal(nc.additive_tree_by_rows(40, 3, longest=3), nc.additive_tree(40, 3, longest=3))
+    big = nc.additive_tree_by_rows(2100, 7)
+    assert big.shape == (2100, 2100) and np.array_equal(big, big.T) and not big.diagonal().any() and not nc.refused(big)
+    assert int(big[~np.eye(2100, dtype=bool)].min()) >= 2           # two leaves are at least two edges apart
