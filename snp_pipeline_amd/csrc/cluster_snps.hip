@@ -27,7 +27,7 @@
 // at or beyond n_sites is taken whatever the planes hold.  Traffic: one sweep of the packed matrix (16 B per 32 sites and row)
 // for the counts, one for the cluster SNPs of a labelling (counts and presence together); P is C / n_rows of the matrix, written
 // once and read twice.
-#include "internal.h"
+#include "pair_tiles.h"
 #include "prims.h"
 
 #define CS_THREADS 256
@@ -299,7 +299,7 @@ __global__ __launch_bounds__(CS_THREADS) void k_cluster_offsets(const uint64_t *
     for (uint64_t c = (uint64_t)blockIdx.x * CS_THREADS + threadIdx.x; c <= n_clusters; c += (uint64_t)gridDim.x * CS_THREADS) cluster_off[c] = off[c * n_tiles];
 }
 
-inline uint32_t words_of(uint32_t n_sites) { return (uint32_t)(snpgpu_packed_row_bytes(n_sites) / 16); }
+inline uint32_t words_of(uint32_t n_sites) { return padded_words(n_sites); }
 inline uint32_t tiles_of(uint32_t n_sites) { return (uint32_t)(((uint64_t)n_sites + 32 * CS_TILE_WORDS - 1) / (32 * CS_TILE_WORDS)); }
 inline unsigned grid_for(const snpgpu_ctx *ctx, uint64_t waves) {
     const uint64_t b = (waves + CS_WAVES - 1) / CS_WAVES, cap = (uint64_t)ctx->n_cu * CS_GRID_CAP_PER_CU;

@@ -10,25 +10,20 @@
 //      of the destination is written: the padding is zero whatever lay there, and no bit at or beyond n_sites is taken whatever
 //      the packed matrix holds.  A lane per output word, coalesced on both sides.
 //   b. k_compared: the q x n block of two planes (the same plane twice: the symmetric matrix, upper-triangle tiles and their
-//      mirror images, as k_distance) on 128 x 128 tiles, 8 x 8 pairs per lane.  The slab scheme of k_distance — LDS-DMA
-//      (global_load_lds_dwordx4) one slab ahead of the arithmetic into a double buffer, one barrier per slab, XOR-swizzled
-//      16-byte slots — with the same LDS geometry: a row contributes 4 slots per slab, 32 KiB in all.  But a slot holds four
-//      words of the plane instead of one packed record, so a ds_read_b128 feeds 4 words x 8 partners x 2 VALU ops (v_and,
-//      v_bcnt with accumulate) = 64 lane-ops where k_distance's feeds 32: half its LDS reads per VALU op, half its VALU ops per
-//      32 sites.  Rows past either matrix read that matrix's last row and are never stored.
+//      mirror images, as k_distance): the slab scheme pair_tiles.h describes, a slot of which holds four words of the plane here.
 //      No split over the word range for shapes of few tiles (k_distance's kSplit): 125 samples x 50 000 sites are microseconds
 //      of work on one CU.
 //   c. k_compared_pairs: Compared of listed pairs (a[p], b[p]) — a indexes the rows of one plane, b of a second, possibly the
 //      same — without the matrix: a wave per pair (grid-stride over the pairs), 16 bytes of each row per lane and step, a wave
 //      sum, out[p].  No atomic: every output position is its pair's index.  A pass over the lists refuses a pair that names a
 //      row outside its matrix before anything is written.
-#include "internal.h"
+#include "pair_tiles.h"
 #include "prims.h"
 
 #define CMP_TILE 128
-#define CMP_KW 16                // words (of 32 sites) per slab: 4 slots of 16 bytes, the slab geometry of k_distance
-#define CMP_SLOTS (CMP_KW / 4)
-#define CMP_THREADS 256
+#define CMP_KW 16                // words (of 32 sites) per slab of the tile kernel: 4 to a 16-byte slot
+static_assert(CMP_TILE == PAIR_TILE && CMP_KW == 4 * PAIR_SLOTS, "the geometry of pair_tiles.h under the names the plane is padded by");
+#define CMP_THREADS 256          // the plane and pair kernels
 #define CMP_PAIR_WAVES (CMP_THREADS / 64)
 #define CMP_PAIR_GRID_CAP 1024   // workgroups: more pairs than 4 x this go round the grid-stride loop
 
@@ -52,28 +47,6 @@ __global__ __launch_bounds__(CMP_THREADS) void k_valid_plane(const uint4 *packed
     }
 }
 
-struct CmpArgs {
-    const uint4 *pq, *pdb;          // the planes, 4 words to a slot
-    uint32_t q, n, slots;           // slots per row: a multiple of CMP_SLOTS
-    uint32_t tiles_n;               // tiles along the database (square: along either side)
-    uint64_t total_tiles;
-    int32_t *out;
-    uint64_t stride;
-};
-
-__device__ __forceinline__ void triangle_coords(uint64_t t, uint32_t nt, uint32_t &bi, uint32_t &bj) {
-    // row-major enumeration of the upper triangle, as distance.hip: row b starts at b*nt - b*(b-1)/2
-    double fn = (double)nt + 0.5;
-    int64_t b = (int64_t)(fn - sqrt(fn * fn - 2.0 * (double)t));
-    if (b < 0) b = 0;
-    if (b >= nt) b = nt - 1;
-    auto start = [&](int64_t r) { return (uint64_t)r * nt - (uint64_t)r * (uint64_t)(r - 1) / 2; };
-    while (b > 0 && start(b) > t) --b;
-    while (b + 1 < (int64_t)nt && start(b + 1) <= t) ++b;
-    bi = (uint32_t)b;
-    bj = (uint32_t)(b + (t - start(b)));
-}
-
 // acc + popcount(m) in the one instruction that does both.  Written out: left to itself the compiler regroups the four sums of a
 // slot into popcounts onto zero and two three-operand adds — 5 VALU ops per 2 words instead of 4 (seen in the ISA, and as 21.9 ms
 // against 17.6 ms for the 10 000 x 200 000 matrix, profiles/r22/compared.md).
@@ -92,17 +65,17 @@ __device__ __forceinline__ int32_t both_valid(const uint4 &x, const uint4 &y, in
 
 // kSquare: pq == pdb, q == n; the tiles of the upper triangle, each stored with its mirror image.
 template <bool kSquare>
-__global__ __launch_bounds__(CMP_THREADS, 3) void k_compared(CmpArgs a) {
+__global__ __launch_bounds__(PAIR_THREADS, 3) void k_compared(PairArgs a) {
     // [buffer][operand][row][slot]; a wave's 64 DMA lanes fill 64 consecutive 16-byte slots
-    __shared__ uint4 slab[2][2][CMP_TILE][CMP_SLOTS];
-    constexpr int kPieces = CMP_TILE * CMP_SLOTS / CMP_THREADS;
+    __shared__ uint4 slab[2][2][PAIR_TILE][PAIR_SLOTS];
+    constexpr int kPieces = PAIR_TILE * PAIR_SLOTS / PAIR_THREADS;
     const uint32_t tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     for (uint64_t t = blockIdx.x; t < a.total_tiles; t += gridDim.x) {
         uint32_t bi, bj;
         if (kSquare) triangle_coords(t, a.tiles_n, bi, bj);
         else { bi = (uint32_t)(t / a.tiles_n); bj = (uint32_t)(t % a.tiles_n); }
-        const uint32_t r0 = bi * CMP_TILE, c0 = bj * CMP_TILE;
+        const uint32_t r0 = bi * PAIR_TILE, c0 = bj * PAIR_TILE;
         int32_t acc[8][8];
 #pragma unroll
         for (int i = 0; i < 8; ++i)
@@ -114,7 +87,7 @@ __global__ __launch_bounds__(CMP_THREADS, 3) void k_compared(CmpArgs a) {
         uint32_t row_of[2][kPieces], kk_of[kPieces];
 #pragma unroll
         for (int e = 0; e < kPieces; ++e) {
-            const uint32_t p = e * CMP_THREADS + tid, rr = p >> 2;
+            const uint32_t p = e * PAIR_THREADS + tid, rr = p >> 2;
             kk_of[e] = (p & 3u) ^ ((rr >> 2) & 3u);
             row_of[0][e] = r0 + rr < a.q ? r0 + rr : a.q - 1;
             row_of[1][e] = c0 + rr < a.n ? c0 + rr : a.n - 1;
@@ -125,20 +98,18 @@ __global__ __launch_bounds__(CMP_THREADS, 3) void k_compared(CmpArgs a) {
 #pragma unroll
                 for (int e = 0; e < kPieces; ++e) {
                     const uint4 *gp = (op ? a.pdb : a.pq) + ((size_t)row_of[op][e] * a.slots + (k0 + kk_of[e]));
-                    const uint32_t m0v = __builtin_amdgcn_readfirstlane(
-                        (uint32_t)(uintptr_t)((__attribute__((address_space(3))) char *)&slab[buf][op][0][0]) + (e * CMP_THREADS + wave * 64) * 16);
-                    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(gp), "s"(m0v) : "memory");
+                    lds_dma16(gp, (uint32_t)(uintptr_t)((__attribute__((address_space(3))) char *)&slab[buf][op][0][0]) + (e * PAIR_THREADS + wave * 64) * 16);
                 }
         };
         __syncthreads();                                            // the previous tile's last slab has been read
         request(0, 0);
         int buf = 0;
-        for (uint32_t k0 = 0; k0 < a.slots; k0 += CMP_SLOTS, buf ^= 1) {
+        for (uint32_t k0 = 0; k0 < a.slots; k0 += PAIR_SLOTS, buf ^= 1) {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // my part of this slab has landed ...
             __syncthreads();                                        // ... everybody's has, and the slab before has been read
-            if (k0 + CMP_SLOTS < a.slots) request(k0 + CMP_SLOTS, buf ^ 1);
+            if (k0 + PAIR_SLOTS < a.slots) request(k0 + PAIR_SLOTS, buf ^ 1);
 #pragma unroll
-            for (int kk = 0; kk < CMP_SLOTS; ++kk) {
+            for (int kk = 0; kk < PAIR_SLOTS; ++kk) {
                 uint4 x[8], y[8];
 #pragma unroll
                 for (int i = 0; i < 8; ++i) { const uint32_t r = ty + 16 * i; x[i] = slab[buf][0][r][kk ^ ((r >> 2) & 3u)]; }
@@ -196,7 +167,7 @@ int snpgpu_valid_plane_dev(snpgpu_ctx *ctx, const void *d_packed, uint32_t n_row
     const uint32_t words = plane_words(n_sites);
     const uint64_t blocks = ((uint64_t)n_rows * words + CMP_THREADS - 1) / CMP_THREADS, cap = (uint64_t)ctx->n_cu * 32;
     k_valid_plane<<<(unsigned)(blocks < cap ? blocks : cap), CMP_THREADS, 0, ctx->stream>>>((const uint4 *)d_packed, n_rows, n_sites,
-                                                                                           (uint32_t)(snpgpu_packed_row_bytes(n_sites) / 16), (uint32_t *)d_plane, words);
+                                                                                           padded_words(n_sites), (uint32_t *)d_plane, words);
     HIP_TRY(ctx, hipGetLastError());
     return SNPGPU_OK;
 }
@@ -214,21 +185,25 @@ int snpgpu_compared_rect_dev(snpgpu_ctx *ctx, const void *d_plane_q, uint32_t q,
         HIP_TRY(ctx, hipMemset2DAsync(d_out, out_stride * 4, 0, (size_t)n * 4, q, st));
         return SNPGPU_OK;
     }
-    CmpArgs a;
+    PairArgs a;
     a.pq = (const uint4 *)d_plane_q;
     a.pdb = (const uint4 *)d_plane_db;
     a.q = q;
     a.n = n;
     a.slots = plane_words(n_sites) / 4;
+    a.tile_rank = 0;
+    a.tile_nranks = 1;
+    a.k_parts = 1;
+    a.k_chunk = a.slots;
     a.out = d_out;
     a.stride = out_stride;
-    a.tiles_n = (n + CMP_TILE - 1) / CMP_TILE;
+    a.tiles_n = (n + PAIR_TILE - 1) / PAIR_TILE;
     const bool square = d_plane_q == d_plane_db && q == n;
-    a.total_tiles = square ? (uint64_t)a.tiles_n * (a.tiles_n + 1) / 2 : (uint64_t)((q + CMP_TILE - 1) / CMP_TILE) * a.tiles_n;
+    a.total_tiles = square ? (uint64_t)a.tiles_n * (a.tiles_n + 1) / 2 : (uint64_t)((q + PAIR_TILE - 1) / PAIR_TILE) * a.tiles_n;
     const uint64_t cap = (uint64_t)ctx->n_cu * 64;
     const unsigned grid = (unsigned)(a.total_tiles < cap ? a.total_tiles : cap);
-    if (square) k_compared<true><<<grid, CMP_THREADS, 0, st>>>(a);
-    else k_compared<false><<<grid, CMP_THREADS, 0, st>>>(a);
+    if (square) k_compared<true><<<grid, PAIR_THREADS, 0, st>>>(a);
+    else k_compared<false><<<grid, PAIR_THREADS, 0, st>>>(a);
     HIP_TRY(ctx, hipGetLastError());
     return SNPGPU_OK;
 }

@@ -6,11 +6,11 @@
 // distance.hip counts (utils.py:1135-1165): both bytes in ACGT after upper-casing, and different.
 //
 //   a. k_distance_rect_*: the q x n block of distances of two packed matrices (snpgpu_pack_matrix_dev, the same n_sites) into an
-//      int32 matrix with a row pitch.  The slab scheme of k_distance — LDS-DMA (global_load_lds_dwordx4) one slab ahead of the
-//      arithmetic into a double buffer, one barrier per slab, XOR-swizzled slots — with two operand bases and two row counts, and
-//      no mirror image.  Rows past either matrix read that matrix's last row and are never stored.  Two tile shapes:
-//        tile    128 query rows x 128 database rows, slabs of 4 words, 8 x 8 pairs per lane: k_distance's shape, VALU-bound.
-//        narrow  16 query rows x 64 database rows, slabs of 16 words, 16 pairs per lane: the four lanes 4 r .. 4 r + 3 share
+//      int32 matrix with a row pitch.  Rows past either matrix read that matrix's last row and are never stored.  Two tile shapes:
+//        tile    128 query rows x 128 database rows, 8 x 8 pairs per lane: the sweep pair_tiles.h describes on a plain grid of tiles,
+//                VALU-bound.
+//        narrow  the slab scheme of that sweep (LDS-DMA one slab ahead into a double buffer, one barrier per slab) in another
+//                geometry: 16 query rows x 64 database rows, slabs of 16 words, 16 pairs per lane: the four lanes 4 r .. 4 r + 3 share
 //                database row r of the tile, lane 4 r + p takes the words 4 j + p of a slab against all 16 queries, and the four
 //                partial sums meet in two lane exchanges at the end of the tile.  A database row contributes 256 contiguous
 //                bytes per slab (16 lanes of one DMA instruction); the query words of a step are read from LDS at four
@@ -19,20 +19,16 @@
 //                workgroups per CU, whose barriers fall at different times, keep the loads of a CU in flight.  Few queries
 //                make the sweep of the database HBM-bound; this shape does an eighth of the vector work of the
 //                tile shape per database word.
-//      Split-K as in k_distance: fewer tiles than CUs and at least 4 slabs of the route -> the word range is cut, every part adds
-//      into the zeroed output with integer atomics (sums of integers: the order does not matter).
+//      Split-K on both routes (pair_split_plan): fewer tiles than CUs and at least 4 slabs of the route.
 //   b. k_nearest_rows: per row of such a matrix the entries <= T, ordered by (d, column), the first K of them.  A workgroup per
 //      row: count the entries <= T; when K cuts them, find the K-th smallest value d* by a radix select (4 passes of 8 bits over
 //      the keys with the sign bit flipped, a 256-bin LDS histogram per pass); the row keeps every entry < d* and the first
 //      K - less entries == d* in column order.  The row counts go through a scan (one wait for the total), an emit pass places
 //      every kept entry by workgroup prefix sums in column order, and prim_sort — stable — by (row, d) leaves (row, d, column).
 //      No atomic decides a position: the same matrix gives the same bytes.
-#include "internal.h"
+#include "pair_tiles.h"
 #include "prims.h"
 
-#define RECT_THREADS 256
-#define RECT_TILE 128                    // tile route: rows of either operand
-#define RECT_TILE_KW 4                   // ... words per slab (DIST_KW of distance.hip: the padding unit of a packed row)
 #define RECT_NQ 16                       // narrow route: query rows
 #define RECT_NDB 64                      // ... database rows: four lanes each
 #define RECT_NKW 16                      // ... words per slab: 256 contiguous bytes of a row (a power of two, 16 ... 64)
@@ -46,41 +42,18 @@
 
 namespace {
 
-struct RectArgs {
-    const uint4 *pq, *pdb;
-    uint32_t q, n, words;
-    uint32_t tiles_n;               // tiles along the database
-    uint64_t total_tiles;
-    uint32_t k_parts, k_chunk;      // split-K: the words are cut in k_parts ranges of k_chunk words
-    int32_t *out;
-    uint64_t stride;
-};
-
-__device__ __forceinline__ void lds_dma16(const uint4 *gp, uint32_t lds_byte) {
-    const uint32_t m0v = __builtin_amdgcn_readfirstlane(lds_byte);
-    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(gp), "s"(m0v) : "memory");
-}
-
-__device__ __forceinline__ int32_t pair_word(const uint4 &x, const uint4 &y) {
-    // ((xh ^ yh) | (xl ^ yl)) & xv & yv as v_xor + two 3-input bit ops (truth tables 0xBE, 0x80)
-    const uint32_t u = __builtin_amdgcn_bitop3_b32(x.y, y.y, x.z ^ y.z, 0xBE);
-    return __popc(__builtin_amdgcn_bitop3_b32(u, x.x, y.x, 0x80));
-}
-
 template <bool kSplit>
-__global__ __launch_bounds__(RECT_THREADS, 3) void k_distance_rect_tile(RectArgs a) {
+__global__ __launch_bounds__(PAIR_THREADS, 3) void k_distance_rect_tile(PairArgs a) {
     // [buffer][operand][row][slot]; a wave's 64 DMA lanes fill 64 consecutive 16-byte slots
-    __shared__ uint4 slab[2][2][RECT_TILE][RECT_TILE_KW];
-    constexpr int kPieces = RECT_TILE * RECT_TILE_KW / RECT_THREADS;
+    __shared__ uint4 slab[2][2][PAIR_TILE][PAIR_SLOTS];
+    constexpr int kPieces = PAIR_TILE * PAIR_SLOTS / PAIR_THREADS;
     const uint32_t tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     for (uint64_t gg = blockIdx.x;; gg += gridDim.x) {
-        const uint64_t t = kSplit ? gg / a.k_parts : gg;
-        const uint32_t part = kSplit ? (uint32_t)(gg % a.k_parts) : 0;
+        uint32_t k_begin, k_end;
+        const uint64_t t = pair_part<kSplit>(gg, a, k_begin, k_end);
         if (t >= a.total_tiles) break;
-        const uint32_t k_begin = kSplit ? part * a.k_chunk : 0;                      // multiples of RECT_TILE_KW
-        const uint32_t k_end = kSplit ? (k_begin + a.k_chunk < a.words ? k_begin + a.k_chunk : a.words) : a.words;
-        const uint32_t r0 = (uint32_t)(t / a.tiles_n) * RECT_TILE, c0 = (uint32_t)(t % a.tiles_n) * RECT_TILE;
+        const uint32_t r0 = (uint32_t)(t / a.tiles_n) * PAIR_TILE, c0 = (uint32_t)(t % a.tiles_n) * PAIR_TILE;
         int32_t acc[8][8];
 #pragma unroll
         for (int i = 0; i < 8; ++i)
@@ -91,7 +64,7 @@ __global__ __launch_bounds__(RECT_THREADS, 3) void k_distance_rect_tile(RectArgs
         uint32_t row_of[2][kPieces], kk_of[kPieces];
 #pragma unroll
         for (int e = 0; e < kPieces; ++e) {
-            const uint32_t p = e * RECT_THREADS + tid, rr = p >> 2;
+            const uint32_t p = e * PAIR_THREADS + tid, rr = p >> 2;
             kk_of[e] = (p & 3u) ^ ((rr >> 2) & 3u);
             row_of[0][e] = r0 + rr < a.q ? r0 + rr : a.q - 1;
             row_of[1][e] = c0 + rr < a.n ? c0 + rr : a.n - 1;
@@ -101,19 +74,19 @@ __global__ __launch_bounds__(RECT_THREADS, 3) void k_distance_rect_tile(RectArgs
             for (int op = 0; op < 2; ++op)
 #pragma unroll
                 for (int e = 0; e < kPieces; ++e) {
-                    const uint4 *gp = (op ? a.pdb : a.pq) + ((size_t)row_of[op][e] * a.words + (k0 + kk_of[e]));
-                    lds_dma16(gp, (uint32_t)(uintptr_t)((__attribute__((address_space(3))) char *)&slab[buf][op][0][0]) + (e * RECT_THREADS + wave * 64) * 16);
+                    const uint4 *gp = (op ? a.pdb : a.pq) + ((size_t)row_of[op][e] * a.slots + (k0 + kk_of[e]));
+                    lds_dma16(gp, (uint32_t)(uintptr_t)((__attribute__((address_space(3))) char *)&slab[buf][op][0][0]) + (e * PAIR_THREADS + wave * 64) * 16);
                 }
         };
         __syncthreads();                                            // the previous tile's last slab has been read
         request(k_begin, 0);
         int buf = 0;
-        for (uint32_t k0 = k_begin; k0 < k_end; k0 += RECT_TILE_KW, buf ^= 1) {
+        for (uint32_t k0 = k_begin; k0 < k_end; k0 += PAIR_SLOTS, buf ^= 1) {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // my part of this slab has landed ...
             __syncthreads();                                        // ... everybody's has, and the slab before has been read
-            if (k0 + RECT_TILE_KW < k_end) request(k0 + RECT_TILE_KW, buf ^ 1);
+            if (k0 + PAIR_SLOTS < k_end) request(k0 + PAIR_SLOTS, buf ^ 1);
 #pragma unroll
-            for (int kk = 0; kk < RECT_TILE_KW; ++kk) {
+            for (int kk = 0; kk < PAIR_SLOTS; ++kk) {
                 uint4 x[8], y[8];
 #pragma unroll
                 for (int i = 0; i < 8; ++i) { const uint32_t r = ty + 16 * i; x[i] = slab[buf][0][r][kk ^ ((r >> 2) & 3u)]; }
@@ -122,7 +95,7 @@ __global__ __launch_bounds__(RECT_THREADS, 3) void k_distance_rect_tile(RectArgs
 #pragma unroll
                 for (int i = 0; i < 8; ++i)
 #pragma unroll
-                    for (int j = 0; j < 8; ++j) acc[i][j] += pair_word(x[i], y[j]);
+                    for (int j = 0; j < 8; ++j) acc[i][j] = DistanceWord()(x[i], y[j], acc[i][j]);
             }
         }
 #pragma unroll
@@ -141,7 +114,7 @@ __global__ __launch_bounds__(RECT_THREADS, 3) void k_distance_rect_tile(RectArgs
 }
 
 template <bool kSplit>
-__global__ __launch_bounds__(RECT_THREADS) void k_distance_rect_narrow(RectArgs a) {
+__global__ __launch_bounds__(PAIR_THREADS) void k_distance_rect_narrow(PairArgs a) {
     // [buffer][row][slot]: rows 0 .. 63 the database rows of the tile, 64 .. 79 the query rows
     extern __shared__ uint4 rect_lds[];
     const uint32_t tid = threadIdx.x;
@@ -150,16 +123,14 @@ __global__ __launch_bounds__(RECT_THREADS) void k_distance_rect_narrow(RectArgs 
     // DMA: chunk p = e * 256 + tid of a slab is slot p % RECT_NKW of row p / RECT_NKW: RECT_NKW consecutive lanes read the
     // contiguous bytes a row contributes.  The first pieces are database rows, the last RECT_NQ * RECT_NKW / 256 the query
     // rows; neither the slot nor (row & 3) depends on e.
-    constexpr int kPieces = RECT_NROWS * RECT_NKW / RECT_THREADS, kDbPieces = RECT_NDB * RECT_NKW / RECT_THREADS, kRowsPerPiece = RECT_THREADS / RECT_NKW;
+    constexpr int kPieces = RECT_NROWS * RECT_NKW / PAIR_THREADS, kDbPieces = RECT_NDB * RECT_NKW / PAIR_THREADS, kRowsPerPiece = PAIR_THREADS / RECT_NKW;
     const uint32_t dma_row = tid / RECT_NKW, word_of = (tid % RECT_NKW) ^ ((dma_row & 3u) << 2);
     // arithmetic: the four lanes 4 r .. 4 r + 3 share database row r of the tile; lane 4 r + p takes the words 4 j + p
     const uint32_t my_row = tid >> 2, my_part = tid & 3u, my_swizzle = (my_row & 3u) << 2;
     for (uint64_t gg = blockIdx.x;; gg += gridDim.x) {
-        const uint64_t t = kSplit ? gg / a.k_parts : gg;
-        const uint32_t part = kSplit ? (uint32_t)(gg % a.k_parts) : 0;
+        uint32_t k_begin, k_end;                                    // words: a slot of the packed matrix is one word
+        const uint64_t t = pair_part<kSplit>(gg, a, k_begin, k_end);
         if (t >= a.total_tiles) break;
-        const uint32_t k_begin = kSplit ? part * a.k_chunk : 0;                      // multiples of RECT_NKW
-        const uint32_t k_end = kSplit ? (k_begin + a.k_chunk < a.words ? k_begin + a.k_chunk : a.words) : a.words;
         const uint32_t r0 = (uint32_t)(t / a.tiles_n) * RECT_NQ, c0 = (uint32_t)(t % a.tiles_n) * RECT_NDB;
         int32_t acc[RECT_NQ];
 #pragma unroll
@@ -168,20 +139,20 @@ __global__ __launch_bounds__(RECT_THREADS) void k_distance_rect_narrow(RectArgs 
 #pragma unroll
         for (int e = 0; e < kDbPieces; ++e) {
             const uint32_t c = c0 + e * kRowsPerPiece + dma_row;
-            row_ptr[e] = a.pdb + (size_t)(c < a.n ? c : a.n - 1) * a.words;
+            row_ptr[e] = a.pdb + (size_t)(c < a.n ? c : a.n - 1) * a.slots;
         }
 #pragma unroll
         for (int e = kDbPieces; e < kPieces; ++e) {
             const uint32_t r = r0 + (e - kDbPieces) * kRowsPerPiece + dma_row;
-            row_ptr[e] = a.pq + (size_t)(r < a.q ? r : a.q - 1) * a.words;
+            row_ptr[e] = a.pq + (size_t)(r < a.q ? r : a.q - 1) * a.slots;
         }
         auto request = [&](uint32_t k0, int buf) {
             // the last slab of a range may be short (rows are padded to 4 words, not to a slab): its missing words read the
             // row's last word instead and are never used
-            const uint32_t w = k0 + word_of < a.words ? k0 + word_of : a.words - 1;
+            const uint32_t w = k0 + word_of < a.slots ? k0 + word_of : a.slots - 1;
 #pragma unroll
             for (int e = 0; e < kPieces; ++e)
-                lds_dma16(row_ptr[e] + w, lds0 + ((uint32_t)buf * RECT_NROWS * RECT_NKW + e * RECT_THREADS + wave * 64) * 16);
+                lds_dma16(row_ptr[e] + w, lds0 + ((uint32_t)buf * RECT_NROWS * RECT_NKW + e * PAIR_THREADS + wave * 64) * 16);
         };
         __syncthreads();                                            // the previous tile's last slab has been read
         request(k_begin, 0);
@@ -195,7 +166,7 @@ __global__ __launch_bounds__(RECT_THREADS) void k_distance_rect_narrow(RectArgs 
             for (uint32_t k = my_part; k < nw; k += 4) {
                 const uint4 y = db[k ^ my_swizzle];
 #pragma unroll
-                for (uint32_t i = 0; i < RECT_NQ; ++i) acc[i] += pair_word(qs[i * RECT_NKW + (k ^ ((i & 3u) << 2))], y);
+                for (uint32_t i = 0; i < RECT_NQ; ++i) acc[i] = DistanceWord()(qs[i * RECT_NKW + (k ^ ((i & 3u) << 2))], y, acc[i]);
             }
         }
 #pragma unroll
@@ -357,25 +328,24 @@ int snpgpu_distance_rect_packed_dev(snpgpu_ctx *ctx, const void *d_packed_q, uin
         return snpgpu_set_error(ctx, SNPGPU_E_ARG, "a packed matrix is null or not 16-byte aligned");
     HIP_TRY(ctx, snpgpu_enter(ctx));
     hipStream_t st = ctx->stream;
-    RectArgs a;
+    PairArgs a;
     a.pq = (const uint4 *)d_packed_q;
     a.pdb = (const uint4 *)d_packed_db;
     a.q = q;
     a.n = n;
-    a.words = (uint32_t)(snpgpu_packed_row_bytes(n_sites) / 16);
+    a.slots = padded_words(n_sites);
+    a.tile_rank = 0;
+    a.tile_nranks = 1;
     a.out = d_out;
     a.stride = out_stride;
-    if (a.words == 0) {                                         // no sites at all: every distance is 0
+    if (a.slots == 0) {                                         // no sites at all: every distance is 0
         HIP_TRY(ctx, hipMemset2DAsync(d_out, out_stride * 4, 0, (size_t)n * 4, q, st));
         return SNPGPU_OK;
     }
     const bool narrow = route == 1 || (route == 0 && q <= RECT_AUTO_NARROW_MAX_Q);
-    const uint32_t kw = narrow ? RECT_NKW : RECT_TILE_KW;
-    const uint32_t tiles_q = narrow ? (q + RECT_NQ - 1) / RECT_NQ : (q + RECT_TILE - 1) / RECT_TILE;
-    a.tiles_n = narrow ? (n + RECT_NDB - 1) / RECT_NDB : (n + RECT_TILE - 1) / RECT_TILE;
+    const uint32_t tiles_q = narrow ? (q + RECT_NQ - 1) / RECT_NQ : (q + PAIR_TILE - 1) / PAIR_TILE;
+    a.tiles_n = narrow ? (n + RECT_NDB - 1) / RECT_NDB : (n + PAIR_TILE - 1) / PAIR_TILE;
     a.total_tiles = (uint64_t)tiles_q * a.tiles_n;
-    a.k_parts = 1;
-    a.k_chunk = a.words;
     const uint64_t cap = (uint64_t)ctx->n_cu * 64;
     const size_t lds = narrow ? RECT_NARROW_LDS : 0;
     if (narrow) {                                               // (per device; the call is cheap)
@@ -383,22 +353,18 @@ int snpgpu_distance_rect_packed_dev(snpgpu_ctx *ctx, const void *d_packed_q, uin
         HIP_TRY(ctx, hipFuncSetAttribute((const void *)k_distance_rect_narrow<true>, hipFuncAttributeMaxDynamicSharedMemorySize, RECT_NARROW_LDS));
     }
     hipEvent_t ta = snpgpu_time_begin(ctx);
-    if (a.total_tiles < (uint64_t)ctx->n_cu && a.words >= 4 * kw) {      // too few tiles to fill the chip: split the word range
-        // tile: k_distance's count.  narrow: as many parts as keep every workgroup resident at once (LDS bounds them per CU) —
-        // a part more would start a second round of workgroups that a few CUs run alone; at least 4 parts, for tiles < n_cu
-        uint64_t parts = narrow ? (uint64_t)ctx->n_cu * RECT_NARROW_PER_CU / a.total_tiles : ((uint64_t)ctx->n_cu * 2 + a.total_tiles - 1) / a.total_tiles;
-        const uint64_t max_parts = a.words / (2 * kw);
-        if (parts > max_parts) parts = max_parts;
-        a.k_chunk = (uint32_t)(((a.words + parts - 1) / parts + kw - 1) / kw * kw);
-        a.k_parts = (a.words + a.k_chunk - 1) / a.k_chunk;
+    // the parts wanted.  tile: k_distance's count.  narrow: as many as keep every workgroup resident at once (LDS bounds them per CU) —
+    // a part more would start a second round of workgroups that a few CUs run alone; at least 4 parts, for tiles < n_cu
+    const uint64_t parts = narrow ? (uint64_t)ctx->n_cu * RECT_NARROW_PER_CU / a.total_tiles : ((uint64_t)ctx->n_cu * 2 + a.total_tiles - 1) / a.total_tiles;
+    if (pair_split_plan(a.slots, narrow ? RECT_NKW : PAIR_SLOTS, a.total_tiles, ctx->n_cu, parts, &a.k_chunk, &a.k_parts)) {
         HIP_TRY(ctx, hipMemset2DAsync(d_out, out_stride * 4, 0, (size_t)n * 4, q, st));
         const unsigned grid = (unsigned)(a.total_tiles * a.k_parts);
-        if (narrow) k_distance_rect_narrow<true><<<grid, RECT_THREADS, lds, st>>>(a);
-        else k_distance_rect_tile<true><<<grid, RECT_THREADS, 0, st>>>(a);
+        if (narrow) k_distance_rect_narrow<true><<<grid, PAIR_THREADS, lds, st>>>(a);
+        else k_distance_rect_tile<true><<<grid, PAIR_THREADS, 0, st>>>(a);
     } else {
         const unsigned grid = (unsigned)(a.total_tiles < cap ? a.total_tiles : cap);
-        if (narrow) k_distance_rect_narrow<false><<<grid, RECT_THREADS, lds, st>>>(a);
-        else k_distance_rect_tile<false><<<grid, RECT_THREADS, 0, st>>>(a);
+        if (narrow) k_distance_rect_narrow<false><<<grid, PAIR_THREADS, lds, st>>>(a);
+        else k_distance_rect_tile<false><<<grid, PAIR_THREADS, 0, st>>>(a);
     }
     snpgpu_time_end(ctx, SNPGPU_K_DISTANCE, ta);
     HIP_TRY(ctx, hipGetLastError());

@@ -40,7 +40,7 @@
 // 24 SGPRs; k_nj_splits 16 VGPRs, 42 SGPRs; k_split_iota 4 VGPRs; k_split_count 12 VGPRs, 46 SGPRs; none of them uses LDS.  The two sorts of
 // prims.h as instantiated here: tile sort 12 (columns) / 22 (rows) VGPRs and 12 288 bytes of LDS, merge pass 46 VGPRs and 8 208 bytes.  No
 // spill and no scratch in any of them.
-#include "internal.h"
+#include "pair_tiles.h"
 #include "nj_host.h"
 #include "prims.h"
 
@@ -76,7 +76,7 @@ __global__ __launch_bounds__(BOOT_THREADS) void k_boot_max(const uint32_t *cols,
     if ((threadIdx.x & 63) == 0 && most) atomicMax(flag, most);
 }
 
-// dst_words is a multiple of DIST_KW = 4, so a row is dst_words / 2 groups of 64 sites; every column is below 32 * src_words
+// dst_words is a multiple of PAIR_SLOTS = 4 (padded_words of pair_tiles.h), so a row is dst_words / 2 groups of 64 sites; every column is below 32 * src_words
 __global__ __launch_bounds__(BOOT_THREADS) void k_boot_resample(const uint4 *src, uint32_t n_rows, uint32_t src_words, const uint32_t *cols, uint32_t n_cols,
                                                                 uint4 *dst, uint32_t dst_words) {
     const uint32_t lane = threadIdx.x & 63, grp = blockIdx.x * (BOOT_THREADS / 64) + (threadIdx.x >> 6);
@@ -169,7 +169,7 @@ __global__ __launch_bounds__(BOOT_THREADS) void k_split_count(const uint64_t *ma
     }
 }
 
-inline uint32_t packed_words(uint32_t n_sites) { return (uint32_t)(snpgpu_packed_row_bytes(n_sites) / 16); }
+inline uint32_t packed_words(uint32_t n_sites) { return padded_words(n_sites); }
 inline uint32_t split_words(uint32_t n) { return (n + 63) / 64; }
 
 void columns_run(snpgpu_ctx *ctx, uint64_t seed, uint32_t replicate, uint32_t s, uint32_t *d_cols) {

@@ -14,7 +14,7 @@
 // No atomic decides a position: the bytes of the result are a function of the input alone.  The zero words a row is padded with
 // never match (valid is 0 there), and no bit at or beyond n_sites is taken whatever the planes hold.  A pair that names a row
 // >= n_rows has no entries and raises the status word; a == b has none either.
-#include "internal.h"
+#include "pair_tiles.h"
 #include "prims.h"
 
 #define PAIR_SITES_THREADS 256
@@ -89,7 +89,7 @@ inline unsigned grid_for(uint64_t pairs) {
     return (unsigned)(b < 1 ? 1 : b < PAIR_SITES_GRID_CAP ? b : PAIR_SITES_GRID_CAP);
 }
 
-inline uint32_t words_of(uint32_t n_sites) { return (uint32_t)(snpgpu_packed_row_bytes(n_sites) / 16); }
+inline uint32_t words_of(uint32_t n_sites) { return padded_words(n_sites); }
 
 // The count pass and the scan into the context's scratch: *d_off = n_pairs + 1 offsets there, *total on the host (waits for the
 // stream).  SNPGPU_E_ARG when a pair names a row >= n_rows or the total reaches 2^32.

@@ -17,7 +17,7 @@ import sys
 import torch
 import torch.distributed as dist
 
-DIST_TILE = 128          # csrc/distance.hip
+DIST_TILE = 128          # PAIR_TILE of csrc/pair_tiles.h
 
 # The device whose context holds this rank's RCCL communicator behind the C ABI (csrc/comm.hip), once use_abi_comm() has set it
 # up.  With it every exchange of the step is a library call on the context's stream — ncclAllGather / grouped ncclSend + ncclRecv

@@ -185,6 +185,25 @@ def test_the_square_block_is_symmetric_with_the_own_counts_on_its_diagonal(every
     assert np.array_equal(d.compared(sym), want)
 
 
+@pytest.mark.parametrize("every_byte", [False, True])
+def test_the_square_and_the_rectangular_sweep_store_the_same_block(every_byte):
+    """257 samples at one site past a slab: three tile rows, the last one row deep, and a second slab that is nearly empty.  The
+    same plane twice takes the upper-triangle tiles and their mirror images; a copy of it at another address takes the plain grid."""
+    d = get_device()
+    n, s, pitch = 2 * TILE + 1, SLAB + 1, 300
+    sym = pc.random_symbols(n, s, 83, every_byte)
+    pl = _plane(d, sym)
+    other = pl.clone()
+    assert other.data_ptr() != pl.data_ptr()
+    square = _rect(d, pl, n, pl, n, s, pitch_extra=pitch - n)
+    rect = _rect(d, pl, n, other, n, s, pitch_extra=pitch - n)
+    assert square.shape == (n + 2, pitch) and np.array_equal(square, rect)
+    want = pc.compared_rect(sym, sym)
+    assert want.min() < want.max()
+    _check(square, want, "square")
+    _check(rect, want, "rectangular")
+
+
 def test_a_matrix_of_bases_alone_is_compared_everywhere():
     d = get_device()
     sym = np.frombuffer(b"ACGTacgt", dtype=np.uint8)[np.random.default_rng(82).integers(0, 8, size=(130, 1025))]

@@ -14,7 +14,7 @@ from oracle import steps_oracle as so
 
 pytestmark = pytest.mark.gpu
 
-TILE, KW = 128, 4                      # DIST_TILE, DIST_KW
+TILE, KW = 128, 4                      # PAIR_TILE, PAIR_SLOTS of csrc/pair_tiles.h
 I64_MAX = np.iinfo(np.int64).max
 MARK = -7
 
