@@ -102,27 +102,51 @@ def _id_table(ids):
     return b"".join(names), off
 
 
+class _Ids(object):
+    """The ids of a table among the arguments of _write: its bytes, its offsets and its count."""
+    def __init__(self, ids):
+        self.ids = ids
+
+
+def _as(dtype, *arrays):
+    return [np.ascontiguousarray(x, dtype=dtype) for x in arrays]
+
+
+def _opt(x):
+    """An array the library wants to see as NULL when it is empty."""
+    return x if x.size else None
+
+
+def _write(entry, path, args, arg_error=None):
+    """One call of a writer of csrc/tsv_out.hip.  args, behind the path: _Ids for an id table, an array for its address, anything
+    else as it is.  E_IO raises IOError, E_ARG ValueError(arg_error) when the writer has one, every other failure RuntimeError."""
+    from . import _lib as L
+    flat, keep = [], []
+    for x in args:
+        if isinstance(x, _Ids):
+            blob, off = _id_table(x.ids)
+            keep.append(off)
+            flat += [blob, off.ctypes.data, len(x.ids)]
+        else:
+            flat.append(x.ctypes.data if isinstance(x, np.ndarray) else x)
+    rc = getattr(L.load(), entry)(path.encode(), *flat)
+    if rc == L.E_IO:
+        raise IOError("cannot write %s" % path)
+    if rc == L.E_ARG and arg_error is not None:
+        raise ValueError(arg_error)
+    if rc != 0:
+        raise RuntimeError("%s failed (%d)" % (entry, rc))
+
+
 def write_pair_rows(path, a_ids, b_ids, a, b, dist, compared):
     """Header and "id\tid\tdistance\tcompared" rows of pair lists in the order given (csrc/tsv_out.hip): a names ids of a_ids, b of
     b_ids — the rows of a close-pairs, tree or nearest file with the fourth column of --amdCompared."""
-    from . import _lib as L
-    a_blob, a_off = _id_table(a_ids)
-    b_blob, b_off = _id_table(b_ids)
-    a = np.ascontiguousarray(a, dtype=np.uint32)
-    b = np.ascontiguousarray(b, dtype=np.uint32)
-    d = np.ascontiguousarray(dist, dtype=np.int32)
-    c = np.ascontiguousarray(compared, dtype=np.int32)
+    a, b = _as(np.uint32, a, b)
+    d, c = _as(np.int32, dist, compared)
     if not len(a) == len(b) == len(d) == len(c):
         raise ValueError("a, b, dist and compared hold one entry per row")
-    opt = lambda x: x.ctypes.data if len(x) else None          # noqa: E731
-    rc = L.load().snpgpu_write_pair_rows_tsv(path.encode(), a_blob, a_off.ctypes.data, len(a_ids), b_blob, b_off.ctypes.data, len(b_ids), opt(a), opt(b), opt(d), opt(c),
-                                             len(a))
-    if rc == L.E_IO:
-        raise IOError("cannot write %s" % path)
-    if rc == L.E_ARG:
-        raise ValueError("a row names a sample outside the %d and %d ids" % (len(a_ids), len(b_ids)))
-    if rc != 0:
-        raise RuntimeError("snpgpu_write_pair_rows_tsv failed (%d)" % rc)
+    _write("snpgpu_write_pair_rows_tsv", path, [_Ids(a_ids), _Ids(b_ids), _opt(a), _opt(b), _opt(d), _opt(c), len(a)],
+           "a row names a sample outside the %d and %d ids" % (len(a_ids), len(b_ids)))
 
 
 def rows_of_csr(row_off):
@@ -136,29 +160,14 @@ def write_close_pairs(path, ids, row_off, col, dist, compared=None):
     compared (one count per entry): a fourth column."""
     if compared is not None:
         return write_pair_rows(path, ids, ids, rows_of_csr(row_off), col, dist, compared)
-    from . import _lib as L
-    blob, off = _id_table(ids)
-    ro = np.ascontiguousarray(row_off, dtype=np.uint64)
-    c = np.ascontiguousarray(col, dtype=np.uint32)
-    d = np.ascontiguousarray(dist, dtype=np.int32)
-    rc = L.load().snpgpu_write_close_pairs_tsv(path.encode(), blob, off.ctypes.data, len(ids), ro.ctypes.data, c.ctypes.data, d.ctypes.data)
-    if rc == L.E_IO:
-        raise IOError("cannot write %s" % path)
-    if rc != 0:
-        raise RuntimeError("snpgpu_write_close_pairs_tsv failed (%d)" % rc)
+    _write("snpgpu_write_close_pairs_tsv", path, [_Ids(ids)] + _as(np.uint64, row_off) + _as(np.uint32, col) + _as(np.int32, dist))
 
 
 def write_clusters(path, ids, thresholds, numbers):
     """"Id" and the thresholds, then per id its cluster number at each threshold; numbers: (len(thresholds), len(ids)) uint32."""
-    from . import _lib as L
-    blob, off = _id_table(ids)
-    thr = np.ascontiguousarray(thresholds, dtype=np.int32)
-    num = np.ascontiguousarray(numbers, dtype=np.uint32).reshape(len(thr), len(ids))
-    rc = L.load().snpgpu_write_clusters_tsv(path.encode(), blob, off.ctypes.data, len(ids), thr.ctypes.data, len(thr), num.ctypes.data)
-    if rc == L.E_IO:
-        raise IOError("cannot write %s" % path)
-    if rc != 0:
-        raise RuntimeError("snpgpu_write_clusters_tsv failed (%d)" % rc)
+    thr, = _as(np.int32, thresholds)
+    num = _as(np.uint32, numbers)[0].reshape(len(thr), len(ids))
+    _write("snpgpu_write_clusters_tsv", path, [_Ids(ids), thr, len(thr), num])
 
 
 def write_pairs_and_clusters(dev, ids, row_off, col, dist, pairs_file, max_pair_distance, clusters_file, thresholds, pairs_compared=None, want_numbers=False):
@@ -209,18 +218,8 @@ def mst_of_edges(n, u, v, dist):
 
 
 def _write_tree(entry, path, ids, u, v, dist):
-    from . import _lib as L
-    blob, off = _id_table(ids)
-    u = np.ascontiguousarray(u, dtype=np.uint32)
-    v = np.ascontiguousarray(v, dtype=np.uint32)
-    d = np.ascontiguousarray(dist, dtype=np.int32)
-    rc = getattr(L.load(), entry)(path.encode(), blob, off.ctypes.data, len(ids), u.ctypes.data, v.ctypes.data, d.ctypes.data, len(u))
-    if rc == L.E_IO:
-        raise IOError("cannot write %s" % path)
-    if rc == L.E_ARG:
-        raise ValueError("the edges are not a spanning tree of the %d ids in ascending order" % len(ids))
-    if rc != 0:
-        raise RuntimeError("%s failed (%d)" % (entry, rc))
+    u, v = _as(np.uint32, u, v)
+    _write(entry, path, [_Ids(ids), u, v] + _as(np.int32, dist) + [len(u)], "the edges are not a spanning tree of the %d ids in ascending order" % len(ids))
 
 
 def write_mst(path, ids, u, v, dist, compared=None):
@@ -237,7 +236,7 @@ def write_dendrogram(path, ids, u, v, dist):
 
 
 def _merge_arrays(a, b, size_a, size_b, num):
-    arrays = [np.ascontiguousarray(x, dtype=np.uint32) for x in (a, b, size_a, size_b)] + [np.ascontiguousarray(num, dtype=np.uint64)]
+    arrays = _as(np.uint32, a, b, size_a, size_b) + _as(np.uint64, num)
     if len(set(len(x) for x in arrays)) != 1:
         raise ValueError("a, b, size_a, size_b and num hold one entry per merge")
     return arrays
@@ -260,18 +259,10 @@ def linkage_cut(kind, n, a, b, size_a, size_b, num, thresholds):
 
 
 def _write_linkage(entry, path, ids, kind, a, b, size_a, size_b, num):
-    from . import _lib as L
     from .device import Device
-    blob, off = _id_table(ids)
     arrays = _merge_arrays(a, b, size_a, size_b, num)
-    opt = lambda x: x.ctypes.data if x.size else None          # noqa: E731
-    rc = getattr(L.load(), entry)(path.encode(), blob, off.ctypes.data, len(ids), Device._linkage_kind(kind), *([opt(x) for x in arrays] + [len(arrays[0])]))
-    if rc == L.E_IO:
-        raise IOError("cannot write %s" % path)
-    if rc == L.E_ARG:
-        raise ValueError("the merges are not those of a tree of the %d ids" % len(ids))
-    if rc != 0:
-        raise RuntimeError("%s failed (%d)" % (entry, rc))
+    _write(entry, path, [_Ids(ids), Device._linkage_kind(kind)] + [_opt(x) for x in arrays] + [len(arrays[0])],
+           "the merges are not those of a tree of the %d ids" % len(ids))
 
 
 def write_linkage_merges(path, ids, kind, a, b, size_a, size_b, num):
@@ -310,49 +301,30 @@ def write_nj(path, ids, a, b, len_a, len_b, star, star_len, support=None, replic
     """The neighbour-joining tree (the values of Device.nj) as one Newick line: a trifurcation at the top, lengths in SNPs written
     from integer millionths (csrc/nj_host.h).  With support (the last value of Device.nj_bootstrap) and replicates every join node
     carries floor((200 support + replicates) / (2 replicates)) between its ")" and its ":"."""
-    from . import _lib as L
-    blob, off = _id_table(ids)
-    a, b = (np.ascontiguousarray(x, dtype=np.uint32) for x in (a, b))
-    len_a, len_b = (np.ascontiguousarray(x, dtype=np.int64) for x in (len_a, len_b))
+    a, b = _as(np.uint32, a, b)
+    len_a, len_b = _as(np.int64, len_a, len_b)
     if not len(a) == len(b) == len(len_a) == len(len_b) or len(star) != 3 or len(star_len) != 3:
         raise ValueError("a, b, len_a and len_b hold one entry per merge, the star three slots and three lengths")
     star = np.asarray([0xFFFFFFFF if s is None else int(s) for s in star], dtype=np.uint32)
     star_len = np.asarray([int(x) for x in star_len], dtype=np.int64)
-    opt = lambda x: x.ctypes.data if x.size else None          # noqa: E731
+    args = [_Ids(ids), _opt(a), _opt(b), _opt(len_a), _opt(len_b), len(a), star, star_len]
+    wrong = "the merges and the star are not a neighbour-joining tree of the %d ids" % len(ids)
     if support is None:
-        name = "snpgpu_write_nj_newick"
-        rc = L.load().snpgpu_write_nj_newick(path.encode(), blob, off.ctypes.data, len(ids), opt(a), opt(b), opt(len_a), opt(len_b), len(a), star.ctypes.data,
-                                             star_len.ctypes.data)
+        _write("snpgpu_write_nj_newick", path, args, wrong)
     else:
-        name = "snpgpu_write_nj_newick_support"
         support = _support_counts(support, replicates, len(a))
-        rc = L.load().snpgpu_write_nj_newick_support(path.encode(), blob, off.ctypes.data, len(ids), opt(a), opt(b), opt(len_a), opt(len_b), len(a), star.ctypes.data,
-                                                     star_len.ctypes.data, opt(support), int(replicates))
-    if rc == L.E_IO:
-        raise IOError("cannot write %s" % path)
-    if rc == L.E_ARG:
-        raise ValueError("the merges and the star are not a neighbour-joining tree of the %d ids%s" % (len(ids), "" if support is None else ", or a count exceeds the replicates"))
-    if rc != 0:
-        raise RuntimeError("%s failed (%d)" % (name, rc))
+        _write("snpgpu_write_nj_newick_support", path, args + [_opt(support), int(replicates)], wrong + ", or a count exceeds the replicates")
 
 
 def write_nj_support(path, ids, a, b, support, replicates):
     """The support table of the joins (a, b of Device.nj_bootstrap, its counts) in round order: Seq1, Seq2 the ids of the two slots,
     Size the leaves under the new node, Support the count, Replicates."""
-    from . import _lib as L
-    blob, off = _id_table(ids)
-    a, b = (np.ascontiguousarray(x, dtype=np.uint32) for x in (a, b))
+    a, b = _as(np.uint32, a, b)
     if len(a) != len(b):
         raise ValueError("a and b hold one entry per merge")
     support = _support_counts(support, replicates, len(a))
-    opt = lambda x: x.ctypes.data if x.size else None          # noqa: E731
-    rc = L.load().snpgpu_write_nj_support(path.encode(), blob, off.ctypes.data, len(ids), opt(a), opt(b), len(a), opt(support), int(replicates))
-    if rc == L.E_IO:
-        raise IOError("cannot write %s" % path)
-    if rc == L.E_ARG:
-        raise ValueError("the merges are not the joins of a neighbour-joining tree of the %d ids, or a count exceeds the replicates" % len(ids))
-    if rc != 0:
-        raise RuntimeError("snpgpu_write_nj_support failed (%d)" % rc)
+    _write("snpgpu_write_nj_support", path, [_Ids(ids), _opt(a), _opt(b), len(a), _opt(support), int(replicates)],
+           "the merges are not the joins of a neighbour-joining tree of the %d ids, or a count exceeds the replicates" % len(ids))
 
 
 def pairs_of_csr(row_off, col, dist, threshold):
@@ -397,87 +369,55 @@ def site_table(snp_list):
 def write_pair_sites(path, ids, a, b, pair_off, site, bases, snp_list=None):
     """One row per differing site of every pair, in the order given (csrc/tsv_out.hip): "id\tid\tcolumn\tbase\tbase" with
     1-based columns, or — snp_list: the (chrom, pos) of every column — "id\tid\tchrom\tpos\tbase\tbase"."""
-    from . import _lib as L
-    blob, off = _id_table(ids)
-    a = np.ascontiguousarray(a, dtype=np.uint32)
-    b = np.ascontiguousarray(b, dtype=np.uint32)
-    po = np.ascontiguousarray(pair_off, dtype=np.uint64)
-    st = np.ascontiguousarray(site, dtype=np.uint32)
-    bs = np.ascontiguousarray(bases, dtype=np.uint8)
+    a, b = _as(np.uint32, a, b)
+    po, = _as(np.uint64, pair_off)
+    st, = _as(np.uint32, site)
+    bs, = _as(np.uint8, bases)
     if len(a) != len(b) or len(po) != len(a) + 1 or len(st) != len(bs) or int(po[-1]) != len(st):
         raise ValueError("pair_off holds one offset per pair and one more, site and bases one entry per offset")
-    table = (None, None, None, None)
-    keep = None
-    if snp_list is not None:
-        if len(st) and int(st.max()) >= len(snp_list):
-            raise ValueError("a site lies beyond the %d columns of the site list" % len(snp_list))
-        keep = site_table(snp_list)
-        table = (keep[0], keep[1].ctypes.data, keep[2].ctypes.data if len(keep[2]) else None, keep[3].ctypes.data if len(keep[3]) else None)
-        if table[2] is None:                                   # a list without columns: the writer still wants to see a table
-            keep = keep + (np.zeros(1, dtype=np.uint32), np.zeros(1, dtype=np.uint64))
-            table = (keep[0], keep[1].ctypes.data, keep[4].ctypes.data, keep[5].ctypes.data)
-    opt = lambda x: x.ctypes.data if len(x) else None          # noqa: E731
-    rc = L.load().snpgpu_write_pair_sites_tsv(path.encode(), blob, off.ctypes.data, len(ids), opt(a), opt(b), len(a), po.ctypes.data, opt(st), opt(bs), *table)
-    if rc == L.E_IO:
-        raise IOError("cannot write %s" % path)
-    if rc == L.E_ARG:
-        raise ValueError("a pair names a sample outside the %d ids, or the offsets do not rise from 0" % len(ids))
-    if rc != 0:
-        raise RuntimeError("snpgpu_write_pair_sites_tsv failed (%d)" % rc)
+    if snp_list is not None and len(st) and int(st.max()) >= len(snp_list):
+        raise ValueError("a site lies beyond the %d columns of the site list" % len(snp_list))
+    _write("snpgpu_write_pair_sites_tsv", path, [_Ids(ids), _opt(a), _opt(b), len(a), po, _opt(st), _opt(bs)] + _site_table_args(snp_list, len(snp_list or ())),
+           "a pair names a sample outside the %d ids, or the offsets do not rise from 0" % len(ids))
 
 
 def _site_table_args(snp_list, columns):
-    """The last four arguments of the site writers: all None without a list; (arrays to keep alive, arguments) otherwise."""
+    """The last four arguments of the site writers: all None without a list, else the arrays of site_table."""
     if snp_list is None:
-        return None, (None, None, None, None)
+        return [None, None, None, None]
     if len(snp_list) != columns:
         raise ValueError("the site list names %d sites, the matrix has %d columns" % (len(snp_list), columns))
-    keep = site_table(snp_list)
+    table = list(site_table(snp_list))
     if columns == 0:                                           # a list without columns: the writer still wants to see a table
-        keep = keep[:2] + (np.zeros(1, dtype=np.uint32), np.zeros(1, dtype=np.uint64))
-    return keep, (keep[0], keep[1].ctypes.data, keep[2].ctypes.data, keep[3].ctypes.data)
+        table[2:] = [np.zeros(1, dtype=np.uint32), np.zeros(1, dtype=np.uint64)]
+    return table
 
 
 def write_site_counts(path, counts, n_rows, snp_list=None):
     """"Site\tA\tC\tG\tT\tOther" and one row per column of counts ((s, 4): the rows that hold A, C, G, T), Other = n_rows minus
     the four (csrc/tsv_out.hip); 1-based columns, or — snp_list: the (chrom, pos) of every column — Chrom and Pos in their place."""
-    from . import _lib as L
-    c = np.ascontiguousarray(counts, dtype=np.int32).reshape(-1, 4)
-    keep, table = _site_table_args(snp_list, len(c))
-    rc = L.load().snpgpu_write_site_counts_tsv(path.encode(), c.ctypes.data if len(c) else None, len(c), int(n_rows), *table)
-    if rc == L.E_IO:
-        raise IOError("cannot write %s" % path)
-    if rc == L.E_ARG:
-        raise ValueError("the counts of a column are negative or exceed the %d rows" % int(n_rows))
-    if rc != 0:
-        raise RuntimeError("snpgpu_write_site_counts_tsv failed (%d)" % rc)
+    c = _as(np.int32, counts)[0].reshape(-1, 4)
+    _write("snpgpu_write_site_counts_tsv", path, [_opt(c), len(c), int(n_rows)] + _site_table_args(snp_list, len(c)),
+           "the counts of a column are negative or exceed the %d rows" % int(n_rows))
 
 
 def write_cluster_snps(path, thresholds, sizes, cluster_off, site, base, members, columns, snp_list=None):
     """"Threshold\tCluster\tSite\tBase\tMembers\tSize" and one row per entry of Device.cluster_snps, labelling t under
     thresholds[t]: sizes and cluster_off are lists with one array per labelling (the sizes of its clusters; their offsets and
     one more).  columns: the width of the matrix.  snp_list as for write_site_counts."""
-    from . import _lib as L
-    thr = np.ascontiguousarray(thresholds, dtype=np.int32)
+    thr, = _as(np.int32, thresholds)
     if not len(thr) == len(sizes) == len(cluster_off) or any(len(o) != len(z) + 1 for o, z in zip(cluster_off, sizes)):
         raise ValueError("one array of sizes and one of offsets (one more) per threshold")
     ncl = np.asarray([len(z) for z in sizes], dtype=np.uint32)
-    sz = np.ascontiguousarray(np.concatenate([np.asarray(z, dtype=np.uint32) for z in sizes]) if len(sizes) else np.zeros(0), dtype=np.uint32)
-    off = np.ascontiguousarray(np.concatenate([np.asarray(o, dtype=np.uint64) for o in cluster_off]) if len(sizes) else np.zeros(0), dtype=np.uint64)
-    st = np.ascontiguousarray(site, dtype=np.uint32)
-    bs = np.ascontiguousarray(base, dtype=np.uint8)
-    mb = np.ascontiguousarray(members, dtype=np.uint32)
+    sz, = _as(np.uint32, np.concatenate([np.asarray(z, dtype=np.uint32) for z in sizes]) if len(sizes) else np.zeros(0))
+    off, = _as(np.uint64, np.concatenate([np.asarray(o, dtype=np.uint64) for o in cluster_off]) if len(sizes) else np.zeros(0))
+    st, mb = _as(np.uint32, site, members)
+    bs, = _as(np.uint8, base)
     if not len(st) == len(bs) == len(mb) or (len(off) and int(off[-1]) != len(st)):
         raise ValueError("site, base and members hold one entry per offset")
-    keep, table = _site_table_args(snp_list, int(columns))
-    opt = lambda x: x.ctypes.data if len(x) else None          # noqa: E731
-    rc = L.load().snpgpu_write_cluster_snps_tsv(path.encode(), opt(thr), opt(ncl), len(thr), opt(off), opt(sz), opt(st), opt(bs), opt(mb), int(columns), *table)
-    if rc == L.E_IO:
-        raise IOError("cannot write %s" % path)
-    if rc == L.E_ARG:
-        raise ValueError("an entry names a site beyond the %d columns or a base above 3, or the offsets do not rise from 0" % int(columns))
-    if rc != 0:
-        raise RuntimeError("snpgpu_write_cluster_snps_tsv failed (%d)" % rc)
+    _write("snpgpu_write_cluster_snps_tsv", path,
+           [_opt(thr), _opt(ncl), len(thr), _opt(off), _opt(sz), _opt(st), _opt(bs), _opt(mb), int(columns)] + _site_table_args(snp_list, int(columns)),
+           "an entry names a site beyond the %d columns or a base above 3, or the offsets do not rise from 0" % int(columns))
 
 
 def write_cluster_snps_of_numbers(device_of, path, rows, thresholds, numbers, snp_list=None):
@@ -541,35 +481,20 @@ def write_nearest(path, q_ids, db_ids, row_off, col, dist, compared=None):
         if len(row_off) != len(q_ids) + 1:
             raise ValueError("row_off holds one offset per query and one more")
         return write_pair_rows(path, q_ids, db_ids, rows_of_csr(row_off), col, dist, compared)
-    from . import _lib as L
-    q_blob, q_off = _id_table(q_ids)
-    db_blob, db_off = _id_table(db_ids)
-    ro = np.ascontiguousarray(row_off, dtype=np.uint64)
-    c = np.ascontiguousarray(col, dtype=np.uint32)
-    d = np.ascontiguousarray(dist, dtype=np.int32)
+    ro, = _as(np.uint64, row_off)
+    c, = _as(np.uint32, col)
+    d, = _as(np.int32, dist)
     if len(ro) != len(q_ids) + 1 or len(c) != len(d) or int(ro[-1]) != len(c):
         raise ValueError("row_off holds one offset per query and one more, col and dist one entry per offset")
-    opt = lambda x: x.ctypes.data if len(x) else None          # noqa: E731
-    rc = L.load().snpgpu_write_nearest_tsv(path.encode(), q_blob, q_off.ctypes.data, len(q_ids), db_blob, db_off.ctypes.data, len(db_ids), ro.ctypes.data, opt(c), opt(d))
-    if rc == L.E_IO:
-        raise IOError("cannot write %s" % path)
-    if rc == L.E_ARG:
-        raise ValueError("a column names a sample outside the %d database ids, or the offsets do not rise from 0" % len(db_ids))
-    if rc != 0:
-        raise RuntimeError("snpgpu_write_nearest_tsv failed (%d)" % rc)
+    _write("snpgpu_write_nearest_tsv", path, [_Ids(q_ids), _Ids(db_ids), ro, _opt(c), _opt(d)],
+           "a column names a sample outside the %d database ids, or the offsets do not rise from 0" % len(db_ids))
 
 
 def _write_tsv(path, layout, ids, mat):
     """distance.py:100-114 through the library's host formatter (csrc/tsv_out.hip): at 10 000 samples the pairwise file has
     10^8 lines, ~35 s of Python string formatting for 38 ms of kernel."""
-    from . import _lib as L
-    blob, off = _id_table(ids)
-    m = np.ascontiguousarray(mat, dtype=np.int32)
-    rc = L.load().snpgpu_write_distance_tsv(path.encode(), layout, blob, off.ctypes.data, len(ids), m.ctypes.data, m.shape[1] if m.ndim == 2 else 0)
-    if rc == L.E_IO:
-        raise IOError("cannot write %s" % path)
-    if rc != 0:
-        raise RuntimeError("snpgpu_write_distance_tsv failed (%d)" % rc)
+    m, = _as(np.int32, mat)
+    _write("snpgpu_write_distance_tsv", path, [layout, _Ids(ids), m, m.shape[1] if m.ndim == 2 else 0])
 
 
 def compared_of_matrix(device_of, file_ids, sym, lens):

@@ -111,6 +111,14 @@ def test_host_writers_against_the_text_statements(tmp_path):
     distance.write_close_pairs(path, ids, row_off, col, dist)
     text = open(path).read()
     assert text.count("\n") == n * n + 1 and text == cc.pairwise_text(ids, mat)
+    # the same for the clusters file: n * k values over 2^22, cluster numbers of 1 ... 7 digits
+    n, thresholds = 850000, [0, 3, 17, 250, 10000]
+    ids = ["s%d" % i for i in range(n)]
+    numbers = (rng.integers(1, 10, size=(len(thresholds), n)) * 10 ** rng.integers(0, 7, size=(len(thresholds), n))).astype(np.uint32)
+    assert n * len(thresholds) > 1 << 22 and numbers.min() < 10 and numbers.max() >= 10 ** 6
+    distance.write_clusters(path, ids, thresholds, numbers)
+    rows = map("\t".join, zip(ids, *(map(str, row.tolist()) for row in numbers)))
+    assert open(path).read() == "Id\t0\t3\t17\t250\t10000\n" + "\n".join(rows) + "\n"
     with pytest.raises(IOError):
         distance.write_close_pairs(str(tmp_path / "no_such_dir" / "p.tsv"), ["a"], [0, 1], [0], [0])
     with pytest.raises(IOError):

@@ -1,6 +1,7 @@
 """The statement of the compared-site counts (tests/compared_cases.py) pinned against a brute-force loop and the bundled listeria
 matrix, the host writer of the four-column pair files, and the options of ``distance --amdComparedMatrix / --amdCompared``, whose
 errors must reach the user before a device is needed.  No GPU."""
+import itertools
 import os
 
 import numpy as np
@@ -82,6 +83,14 @@ def test_the_writer_gives_the_text_of_the_statement(tmp_path):
             a %= len(b_ids)
             assert _written(tmp_path, b_ids, b_ids, a, b, dist, compared) == pc.pair_rows_text(b_ids, b_ids, a, b, dist, compared), m
     assert _written(tmp_path, [], [], [], [], [], []) == pc.HEADER == "Seq1\tSeq2\tDistance\tCompared\n"
+    # enough rows for the writer's threads (over 2^22): the block offsets must add up.  Two id tables, both numbers of 1 ... 10 digits
+    m = (1 << 22) + 1001
+    a_tab, b_tab = ["q%d" % i for i in range(300)] + ["séü"], ["sample_%d" % (j * j) for j in range(77)]
+    a, b = rng.integers(0, len(a_tab), size=m), rng.integers(0, len(b_tab), size=m)
+    dist, compared = (np.minimum(rng.integers(1, 10, size=m) * 10 ** rng.integers(0, 10, size=m), 2 ** 31 - 1) for _ in range(2))
+    fields = [(np.asarray(t, dtype=object) + "\t")[x].tolist() for t, x in ((a_tab, a), (b_tab, b))] + [map(str, dist.tolist()), map(str, compared.tolist())]
+    rows = zip(fields[0], fields[1], fields[2], itertools.repeat("\t"), fields[3], itertools.repeat("\n"))
+    assert _written(tmp_path, a_tab, b_tab, a, b, dist, compared) == pc.HEADER + "".join(map("".join, rows))
     # the three writers with the fourth column: the rows of the three-column file and one more field
     mat = rng.integers(0, 40, size=(6, 11)).astype(np.int32)
     csr = nc.nearest_of_matrix(mat, 3, 30)

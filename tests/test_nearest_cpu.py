@@ -1,6 +1,7 @@
 """The statement of the nearest-neighbour output (tests/nearest_cases.py) pinned against the reference's own table and the
 site-by-site oracle, the host writer of the file, and the global errors of ``distance --amdQuery / --amdNearest``, which must
 reach the user before a device is needed.  No GPU."""
+import itertools
 import os
 
 import numpy as np
@@ -92,6 +93,24 @@ def test_the_writer_gives_the_text_of_the_statement(tmp_path):
     distance.write_nearest(path, [], db_ids, [0], [], [])
     with open(path) as f:
         assert f.read() == nc.HEADER
+    # enough entries for the writer's threads (over 2^22): the block offsets must add up.  Rows of 0 ... all database samples, ids
+    # of unequal byte lengths, distances from negative to 10 digits
+    n_db = 2100
+    db_ids = ["d" * (j % 7) + "%d" % j for j in range(n_db)]
+    db_ids[5] = "dé5"
+    lens = np.arange(2 * (n_db + 1)) % (n_db + 1)
+    q_ids = ["query%d" % i if i % 3 else "q%d" % i for i in range(len(lens))]
+    row_off = np.concatenate(([0], np.cumsum(lens))).astype(np.uint64)
+    total = int(row_off[-1])
+    assert total > 1 << 22 and lens[0] == 0 and lens[-1] == n_db
+    col = rng.integers(0, n_db, size=total).astype(np.uint32)
+    dist = np.minimum(rng.integers(1, 10, size=total) * 10 ** rng.integers(0, 10, size=total), 2 ** 31 - 1) * rng.choice([-1, 1], size=total)
+    dist[:2] = 0, -(2 ** 31)
+    distance.write_nearest(path, q_ids, db_ids, row_off, col, dist)
+    db_field = np.asarray(["\t%s\t" % name for name in db_ids], dtype=object)
+    rows = zip(np.repeat(np.asarray(q_ids, dtype=object), lens).tolist(), db_field[col].tolist(), map(str, dist.tolist()), itertools.repeat("\n"))
+    with open(path, "rb") as f:
+        assert f.read().decode("utf-8") == nc.HEADER + "".join(map("".join, rows))
     with pytest.raises(ValueError):
         distance.write_nearest(path, ["a"], ["b"], [0, 1], [1], [0])          # a column outside the database
     with pytest.raises(IOError):
